@@ -1,8 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark: M quadrature-point updates/s (stress + consistent tangent, fp64).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, settling launches and warm-up, the K timed steps, the outputs of
+the last timed step if --dump-outputs is given, and the JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, and `roofline` figures derived from the HIP events of the timed steps).  Everything else -- the box
+telemetry, the live rocprofv3 traffic passes, the stream and copy probes, `other_laws`, `host_path`, `cpu_baseline` and,
+for N > 1, the gather-inclusive legs and the cfg 3 block -- runs only with --full (each still switched off by its --no-*
+option).
+
+--dump-outputs DIR writes what the last timed step handed its caller, on a fixed seeded sample of DUMP_ROWS points
+(all points when there are fewer), as fp64 DIR/<name>.npy: `stress` (S,6), `tangent` (S,36) and the new internal state
+variables (`p` (S,1), `epsp` (S,6)).  Rank 0's block only.  Same arguments, same inputs: the strain history is seeded.
 
 Workload (BASELINE.json configs[1], SURVEY.md section 8(d) cfg 2): small-strain J2 plasticity with
 linear isotropic hardening (E=70e3, nu=0.3, sig0=250, H=5e3), 1e7 Gauss points PER GPU (weak
@@ -50,6 +61,7 @@ sys.path.insert(0, ROOT)
 E, NU, SIG0, H = 70e3, 0.3, 250.0, 5e3
 ALG_BYTES = 496  # read eps 6 + eps_p 6 + p 1, write sig 6 + eps_p 6 + p 1 + Ct 36
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_ROWS, DUMP_SEED = 1 << 17, 20240  # --dump-outputs: 131072 points x 49 fp64 = 51 MB
 
 
 def history(n, seed, sig0=None):
@@ -912,6 +924,28 @@ def to_cpu(t):
     return pin.clone()
 
 
+def dump_outputs(torch, out_dir, n, m, flux, ct, stream):
+    """`--dump-outputs`: what the last integrate on handle `m` handed its caller -- stress, tangent and the new internal state
+    variables (state s1, packed AoS by the library) -- on the same DUMP_ROWS rows in every run, as fp64 .npy files."""
+    from dolfinx_materials_amd._lib import S1
+
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    idx = torch.from_numpy(rows).to(flux.device)
+    names = m.internal_state_variables
+    isv = torch.empty((n, sum(names.values())), dtype=torch.float64, device=flux.device)
+    m.isv_device(S1, isv.data_ptr(), stream)   # the state the step computed
+    torch.cuda.synchronize()
+    arrays = {"stress": flux, "tangent": ct}
+    col = 0
+    for name, dim in names.items():
+        arrays[name] = isv[:, col:col + dim]
+        col += dim
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), to_cpu(a.index_select(0, idx)).numpy().astype(np.float64))
+    del isv, idx
+
+
 def free_port():
     import socket
 
@@ -1030,6 +1064,11 @@ def main():
     ap.add_argument("--no-other-laws", action="store_true", help="skip the per-law context numbers")
     ap.add_argument("--no-host-path", action="store_true", help="skip the PCIe-inclusive host-buffer figure")
     ap.add_argument("--cpu-sample", type=int, default=2_000_000)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: box telemetry, live traffic passes, stream / copy probes, other laws, "
+                         "host path, CPU baseline and, for N > 1, the gather legs and the cfg 3 block")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (a fixed seeded sample of DUMP_ROWS points) as fp64 DIR/<name>.npy")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not run the two rocprofv3 --pmc passes for roofline.traffic (falls back to the stamped profiles/pmc_traffic.json)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -1052,7 +1091,7 @@ def main():
         raise SystemExit(launch_ranks(args, sys.argv[1:]))
     # the box, from its own side, before this process touches the GPU (rank 0; pure sysfs + rocm-smi child processes)
     telemetry, box_before = None, None
-    if not args.no_telemetry and int(os.environ.get("RANK", "0")) == 0:
+    if args.full and not args.no_telemetry and int(os.environ.get("RANK", "0")) == 0:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import box_telemetry as telemetry
@@ -1061,8 +1100,8 @@ def main():
         except Exception as exc:   # context only
             telemetry, box_before = None, {"error": repr(exc)}
     # roofline.traffic: measured now, before this process initialises the GPU (rank 0 of a 1-GPU run only)
-    traffic, traffic_detail = None, None
-    if args.gpus == 1 and not args.no_live_traffic and "WORLD_SIZE" not in os.environ:
+    traffic, traffic_detail = None, None if args.full else "not run: a plain run; --full measures it"
+    if args.full and args.gpus == 1 and not args.no_live_traffic and "WORLD_SIZE" not in os.environ:
         traffic, traffic_detail = live_traffic(args)
 
     import torch
@@ -1112,11 +1151,12 @@ def main():
     n = args.points
     K, W = args.steps, args.warmup
     seed = 1234 + rank
-    run_cfg3 = world > 1 and not args.no_cfg3 and args.law == "j2_linear"
+    run_cfg3 = args.full and world > 1 and not args.no_cfg3 and args.law == "j2_linear"
+    gather = args.full and grouped and not args.no_gather
     # (the debug share mode keeps all ranks on one GPU and gathers through gloo on the host: never the full size there)
     n3 = args.cfg3_points if args.cfg3_points else (min(n, 50_000, 100_000_000 // world) if share else 100_000_000 // world)
     if world > 1:
-        blocks = {"headline": hbm_plan(args.law, n, 1 if share else world, grouped and not args.no_gather and not share, rank == 0 and not share)}
+        blocks = {"headline": hbm_plan(args.law, n, 1 if share else world, gather and not share, args.full and rank == 0 and not share)}
         if run_cfg3:
             blocks["cfg3"] = hbm_plan("j2_voce", n3, 1 if share else world, not args.no_gather and not share, False)
         if share:   # all ranks of the debug mode allocate on GPU 0
@@ -1125,7 +1165,7 @@ def main():
         budget = check_hbm_budget(torch, dev, rank, world, blocks)
     else:
         budget = None
-    head = run_workload(c, args.law, n, K, W, max(1, args.gather_steps), gather=grouped and not args.no_gather, copy_probe=True)
+    head = run_workload(c, args.law, n, K, W, max(1, args.gather_steps), gather=gather, copy_probe=args.full, dump=args.dump_outputs)
     # N > 1: cfg 3 of SURVEY.md 8(d) beside the weak-scaling headline -- J2 + Voce, 1e8 points sharded over the ranks,
     # compute-only and the three reassembly schedules
     cfg3 = None
@@ -1239,19 +1279,19 @@ def main():
                             "on every rank by the RCCL all-gather, by the point-to-point schedule and as coefficients rebuilt locally",
                 }
             out["cfg3"] = cfg3
-        if world == 1 and not args.no_other_laws:
+        if args.full and world == 1 and not args.no_other_laws:
             try:
                 torch.cuda.empty_cache()
                 out["other_laws"] = other_laws(torch, jm, JAXMaterial, dev, n, blocks_per_cu=args.blocks_per_cu)
             except Exception as exc:  # context only: never lose the headline line
                 out["other_laws"] = {"error": repr(exc)}
-        if world == 1 and not args.no_host_path and args.law == "j2_linear":
+        if args.full and world == 1 and not args.no_host_path and args.law == "j2_linear":
             try:
                 torch.cuda.empty_cache()
                 out["host_path"] = host_path(jm, JAXMaterial, dev_index, n, seed)
             except Exception as exc:  # context only
                 out["host_path"] = {"error": repr(exc)}
-        if not args.no_cpu_baseline and args.law == "j2_linear":
+        if args.full and not args.no_cpu_baseline and args.law == "j2_linear":
             out["cpu_baseline"] = cpu_baseline(min(args.cpu_sample, n), seed)
         print(json.dumps(out), flush=True)
 
@@ -1262,10 +1302,11 @@ def workload_name(law, n):
             + f"{n:.3g} Gauss points per GPU, stress + 6x6 consistent tangent, load/unload history increments 2-4")
 
 
-def run_workload(c, law, n, K, W, G, gather, copy_probe=False):
+def run_workload(c, law, n, K, W, G, gather, copy_probe=False, dump=None):
     """One law at n points per rank: set-up (three load-step contexts), W warm-up steps, K timed steps
     bracketed by barrier + synchronize (max over ranks), then -- in a process group -- the same steps followed by the
-    reassembly of stress and tangent on every rank, three ways.  Everything it allocated is released on return."""
+    reassembly of stress and tangent on every rank, three ways.  `dump`: directory for the outputs of the last timed step
+    (rank 0).  Everything it allocated is released on return."""
     torch, dist, jm, JAXMaterial, args = c.torch, c.dist, c.jm, c.JAXMaterial, c.args
     rank, world, dev, share, grouped = c.rank, c.world, c.dev, c.share, c.grouped
     sig0 = SIG0 if law == "j2_linear" else 350.0   # demos/jax/elastoplasticity/plane_elastoplasticity.py:60-71
@@ -1370,6 +1411,8 @@ def run_workload(c, law, n, K, W, G, gather, copy_probe=False):
     elapsed = t1 - t0
     per_launch = [a.elapsed_time(b) for a, b in ev]
     kern_ms = float(np.mean(per_launch))
+    if dump and rank == 0 and K > 0:   # before any context leg writes flux / ct again
+        dump_outputs(torch, dump, n, mats[(K - 1) % 3], flux, ct, stream)
     box_during = None
     if tel is not None:
         try:

@@ -19,6 +19,8 @@ Fixtures
                      (E=70e3, nu=0.3, H=1e-6, sig0=250, 50 steps to eps_xx=2e-2, eps_zz=0,
                      sig_yy=0): strain path and stresses from the oracle; the known answer
                      2/sqrt(3)*[sig0, 0, sig0/2] (rtol 1e-2) is asserted at generation time.
+  elastic_live_ref.npz  LinearElasticIsotropic(210e3, 0.25) through the reference's Material.integrate:
+                     eps (40,6) = 1e-3 x default_rng(5) normals -> sig, Ct, isv.        [reference output]
   fefp_self.npz      SELF-golden (parity unpinned): the build's FeFp oracle along the path of
                      tests/test_FeFp_jax.py:21-33 (Nbatch=10, 19 steps).
 """
@@ -48,6 +50,16 @@ def make_elastic():
     sig, isv, Ct = mat.integrate(eps)
     assert isv.shape == (64, 0)
     np.savez(os.path.join(HERE, "elastic_ref.npz"), E=E, nu=nu, eps=eps, sig=np.array(sig), Ct=np.array(Ct))
+
+
+def make_elastic_live():
+    E, nu = 210e3, 0.25
+    rng = np.random.default_rng(5)
+    eps = 1e-3 * rng.standard_normal((40, 6))
+    mat = python_materials.LinearElasticIsotropic(E, nu)
+    mat.set_data_manager(40)
+    sig, isv, Ct = mat.integrate(eps)
+    np.savez(os.path.join(HERE, "elastic_live_ref.npz"), E=E, nu=nu, eps=eps, sig=np.array(sig), isv=np.array(isv), Ct=np.array(Ct))
 
 
 class J2Reference(generic.Material):
@@ -161,6 +173,7 @@ def make_fefp_self():
 if __name__ == "__main__":
     make_fefp_self()
     make_elastic()
+    make_elastic_live()
     make_protocol()
     make_uniaxial()
     for f in sorted(os.listdir(HERE)):

@@ -129,7 +129,6 @@ def test_cfg5_host_assembly_loop_at_32_cubed():
     assert 8 <= total <= 20
 
 
-@pytest.mark.skipif(os.environ.get("DXM_TEST_CFG5_HOST_64") != "1", reason="opt-in (DXM_TEST_CFG5_HOST_64=1): 64^3 host assembly takes ~3 minutes")
 def test_cfg5_host_assembly_loop_at_64_cubed():
     from uniaxial_tension_3d import run
 

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 # the box, from its own side, before any profiler is around (sysfs + SMI tools; tools/box_telemetry.py refuses under a profiler)
 python3 $R/tools/box_telemetry.py > $TOP/box.json 2> $TOP/box.err
 # an unprofiled bench line of the same lease (the figures the summaries are compared with)
-python3 $R/bench.py --no-cpu-baseline --no-host-path > $TOP/bench.json 2> $TOP/bench.err
+python3 $R/bench.py --full --no-cpu-baseline --no-host-path > $TOP/bench.json 2> $TOP/bench.err
 
 OUT=$TOP/j2_linear; mkdir -p $OUT
 ARGS="--no-cpu-baseline --no-other-laws --no-host-path --no-live-traffic --no-stream-probe --no-telemetry"
