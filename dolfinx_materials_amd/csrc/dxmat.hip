@@ -28,6 +28,7 @@
 #include "fefp.hpp"
 #include "gradient.hpp"
 #include "small_strain.hpp"
+#include "ramberg_osgood.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -105,6 +106,9 @@ static const LawDesc kLaws[DXM_LAW_COUNT] = {
      "fefp_kernel<1"},
     {9, 9, 4, 2, 3, {1, 6, 6, 0}, {"p", "be_bar", "cp_bar_inv", nullptr}, {FEFP_SLOT_P, FEFP_SLOT_BE, FEFP_SLOT_CPI, 0}, FEFP_NSLOTS, 976,
      "fefp_kernel<0"},
+    // stateless: the elastic law's stream (48 B in, 48 + 288 B out), with per-point tangent coefficients like J2
+    {6, 6, 5, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 384,
+     "small_strain_kernel<3"},
 };
 
 static int tangent_size(const dxm_material* m);
@@ -248,11 +252,30 @@ static int build_params(dxm_material* m, const double* p, int np) {
       q.sig0 = p[2]; q.h1 = p[3]; q.h2 = p[4];
 #endif
       break;
+    case DXM_LAW_RAMBERG_OSGOOD: {
+      // [E, nu, sig0, alpha, n]; the local Newton's monotone convergence needs a convex f, i.e. n >= 1
+      const double sig0 = p[2], alpha = p[3], n = p[4];
+      if (!(sig0 > 0.0)) return fail(-1, "Ramberg-Osgood: sig0 must be > 0, got %g", sig0);
+      if (!(alpha > 0.0)) return fail(-1, "Ramberg-Osgood: alpha must be > 0, got %g", alpha);
+      if (!(n >= 1.0) || !std::isfinite(n)) return fail(-1, "Ramberg-Osgood: n must be a finite number >= 1, got %g", n);
+      q.sig0 = sig0;
+      q.kappa = E / (3.0 * (1.0 - 2.0 * nu));   // the .mfront file's K
+      q.c[RO_I3MU] = 1.0 / (3.0 * q.mu);
+      q.c[RO_BETA] = alpha * sig0 / E;
+      q.c[RO_ISIG0] = 1.0 / sig0;
+      q.c[RO_N] = n;
+      q.c[RO_INVN] = 1.0 / n;
+      q.c[RO_ESIG] = E * RO_EPS;
+      q.h1 = 3.0 * q.mu;
+      q.h2 = n * q.c[RO_BETA];
+      break;
+    }
   }
   q.maxit = m->maxit;
   // relative to the initial yield stress, floored so that a law with R(0) = 0 keeps a reachable tolerance
   q.rtol = m->rtol;
   q.tol = m->rtol * fmax(fabs(q.sig0), 2e-8 * q.mu);
+  if (m->law == DXM_LAW_RAMBERG_OSGOOD) q.tol = q.c[RO_I3MU] * RO_EPS;   // no residual tolerance: the floor of f' (small_strain.hpp)
   m->prm = q;
   m->raw_params.assign(p, p + np);
   return 0;
@@ -379,6 +402,13 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
     return nullptr;
   }
   if (device < 0 || device >= ndev) { fail(-1, "device %d out of range [0,%d)", device, ndev); return nullptr; }
+#ifdef DXM_CUSTOM_HARDENING
+  // a library built for a user-supplied hardening law carries the hardening kernels only
+  if (law == DXM_LAW_RAMBERG_OSGOOD) {
+    fail(-1, "Ramberg-Osgood has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build");
+    return nullptr;
+  }
+#endif
   dxm_material* m = new dxm_material();
   m->law = law;
   m->device = device;
@@ -422,6 +452,9 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
       case DXM_LAW_J2_LINEAR: fn = (const void*)small_strain_kernel<LAW_J2_LINEAR, TL_FULL>; break;
       case DXM_LAW_J2_VOCE: fn = (const void*)small_strain_kernel<LAW_J2_VOCE, TL_FULL>; break;
       case DXM_LAW_FEFP_J2_LINEAR: fn = (const void*)fefp_kernel<0, 0>; break;
+#ifndef DXM_CUSTOM_HARDENING
+      case DXM_LAW_RAMBERG_OSGOOD: fn = ramberg_osgood_kernel(); break;
+#endif
       default: fn = (const void*)fefp_kernel<1, 0>; break;
     }
     // residency from the kernel's own resources (the occupancy API over-reports on ROCm 7.2):
@@ -443,6 +476,8 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
     // it -- Voce +3 %, FeFp +2.5 % over the persistent grids above at 1e7 points (profiles/archive/r03_grid_size_by_law.txt); the
     // linear-hardening kernel, whose tiles all cost the same, loses 2.5 % with it and keeps 32.
     if (law == DXM_LAW_J2_VOCE || law == DXM_LAW_FEFP_J2_VOCE || law == DXM_LAW_FEFP_J2_LINEAR) m->blocks_per_cu = 256;
+    // Ramberg-Osgood: RO_BLOCKS_PER_CU (DESIGN.md section "Ramberg-Osgood")
+    if (law == DXM_LAW_RAMBERG_OSGOOD) m->blocks_per_cu = RO_BLOCKS_PER_CU;
   }
   // one record per workgroup and launch.  A single launch has at most num_cu * 256 workgroups (the largest grid
   // dxm_set_option("blocks_per_cu") allows); the chunked host path appends the records of up to DXM_MAX_CHUNKS
@@ -803,7 +838,7 @@ static void launch_small_strain(dxm_material* m, int grid, hipStream_t st, int64
                                  else if (g == 2) DXM_LAUNCH_SS(TL, 2); else DXM_LAUNCH_SS(TL, 3); } while (0)
   if (tl == TL_SYM) DXM_LAUNCH_SS_G(TL_SYM);
   else if (tl == TL_FULL) DXM_LAUNCH_SS_G(TL_FULL);
-  else if constexpr (LAW != LAW_ELASTIC) { if (tl == TL_PACK4) DXM_LAUNCH_SS_G(TL_PACK4); else DXM_LAUNCH_SS_G(TL_COEF); }
+  else if constexpr (ss_has_coef<LAW>) { if (tl == TL_PACK4) DXM_LAUNCH_SS_G(TL_PACK4); else DXM_LAUNCH_SS_G(TL_COEF); }
 #undef DXM_LAUNCH_SS_G
 #undef DXM_LAUNCH_SS
 }
@@ -824,6 +859,13 @@ static int launch_range(dxm_material* m, int64_t off, int64_t cnt, const double*
     case DXM_LAW_ELASTIC_ISO: launch_small_strain<LAW_ELASTIC>(m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl); break;
     case DXM_LAW_J2_LINEAR: launch_small_strain<LAW_J2_LINEAR>(m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl); break;
     case DXM_LAW_J2_VOCE: launch_small_strain<LAW_J2_VOCE>(m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl); break;
+#ifndef DXM_CUSTOM_HARDENING
+    case DXM_LAW_RAMBERG_OSGOOD: {   // ramberg_osgood.hip
+      const MeshSource none{};
+      ramberg_osgood_launch(tl, fused ? fused->kind : 0, grid, st, m->prm, cnt, grad, flux, ct, m->d_stats + stats_off, fused ? *fused : none);
+      break;
+    }
+#endif
     case DXM_LAW_FEFP_J2_VOCE:
     case DXM_LAW_FEFP_J2_LINEAR: {
       const double* s0 = m->state[0] + off;

@@ -1,12 +1,13 @@
 // Small-strain constitutive updates for gfx950: isotropic elasticity, J2 plasticity with linear or
-// Voce isotropic hardening.  One fused kernel per law: trial state, yield test, local Newton,
-// stress, consistent tangent and state write-back.
+// Voce isotropic hardening, Ramberg-Osgood nonlinear elasticity.  One fused kernel per law: trial state,
+// yield test, local Newton, stress, consistent tangent and state write-back.
 //
 // Replaces, per Gauss point, what the reference obtains from
 //   vmap(jacfwd(behavior.constitutive_update))      dolfinx_materials/jaxmat.py:147-164
 // Arithmetic spec (the only in-tree statement of the return mapping):
 //   tests/mfront/IsotropicLinearHardeningPlasticity.mfront:49-77
 //   python_materials/elasticity.py:12-24 (elastic), tests/test_FeFp_jax.py:14-15 (Voce law)
+//   tests/mfront/RambergOsgoodNonLinearElasticity.mfront (Ramberg-Osgood; DESIGN.md section "Ramberg-Osgood")
 //
 // Mapping (HBM-bound streaming kernel, ~1 flop/B fp64, no MFMA):
 //   * one thread per Gauss point, one wave per tile of 64 points, grid-stride over tiles;
@@ -25,7 +26,18 @@
 
 namespace dxm {
 
-enum { LAW_ELASTIC = 0, LAW_J2_LINEAR = 1, LAW_J2_VOCE = 2 };
+enum { LAW_ELASTIC = 0, LAW_J2_LINEAR = 1, LAW_J2_VOCE = 2, LAW_RAMBERG_OSGOOD = 3 };
+
+// What a law streams besides strain, stress and tangent: the J2 laws read and write the SoA state (p, eps_p); every law but
+// the elastic one writes per-point tangent coefficients (c1, c2, c3, w).  Ramberg-Osgood has coefficients and no state.
+template <int LAW> constexpr bool ss_has_state = LAW == LAW_J2_LINEAR || LAW == LAW_J2_VOCE;
+template <int LAW> constexpr bool ss_has_coef = LAW != LAW_ELASTIC;
+
+// Ramberg-Osgood parameters in LawParams (the c[] slots serve user hardening laws in JIT builds only, which never
+// instantiate this law), per-handle constants of the local Newton computed on the host: products formed in the kernel
+// would be held in vector registers (c[] below, and h1 = 3 mu, h2 = n beta, tol = e_eps / (3 mu), the floor of f')
+constexpr int RO_I3MU = 0, RO_BETA = 1, RO_ISIG0 = 2, RO_N = 3, RO_INVN = 4, RO_ESIG = 5;
+constexpr double RO_EPS = 1e-12;   // MFront's NumericalThreshold e_eps
 
 // state slots (SoA, leading dimension ld): 0 = p, 1..6 = eps_p (Mandel)
 constexpr int SS_NSLOTS = 7;
@@ -58,6 +70,86 @@ __device__ __forceinline__ double hardening_dR(const LawParams& prm, double p) {
     return DXM_MUL((prm.h1 - prm.sig0) * prm.h2, exp(DXM_MUL(-prm.h2, p)));
 #endif
   }
+}
+
+// Ramberg-Osgood nonlinear elasticity (tests/mfront/RambergOsgoodNonLinearElasticity.mfront): stress s of the total strain e
+// and the coefficients of Ct = c1 1x1 + c2 I + c3 n x n, n = dev(s) wn (c1..wn hold the linear-branch values on entry).
+//   eps_e = sqrt(2/3 dev(e):dev(e)), ne = 2 dev(e) / (3 max(eps_e, e_eps)), sigma = K tr(e) 1 + sig_e ne,
+//   sig_e the root of f(x) = x / (3 mu) + beta (x / sig0)^n - eps_e (linear branch: 3 mu eps_e below e_eps).
+// Two deviations from the .mfront integrator: Newton starts from min(3 mu eps_e, sig0 (eps_e / beta)^(1/n)), an
+// upper bound of the root from which it converges monotonically (f increasing and convex for n >= 1), and stops on the
+// step relative to the iterate, |dx| <= rtol x.  The tangent slope d sig_e / d eps_e = 1 / f' is taken from the last
+// evaluation (one power per iteration, none after the loop); its change over a step of <= rtol x is n rtol relative.
+// (x / sig0)^n is exp(n log(x / sig0)), not pow: with pow inlined the fused-gradient instantiations spill 2-5 VGPRs at the
+// 128 of __launch_bounds__ (with exp / log none does).  The rounding of n log(.) costs about n |log(.)| ulp in the power
+// term, i.e. <= 1e-15 of it on the reference curve; the root moves by that divided by n.
+// `park`: this lane's three LDS pairs of the stress staging (step 5 stores the stress there).  The strain waits in them
+// while the local Newton runs: 12 registers fewer live through the inlined exp / log.
+__device__ __forceinline__ void ramberg_osgood_update(const LawParams& prm, const double mu, const double* e, double2_t* park,
+                                                      double* s, double& c1, double& c2, double& c3, double& wn, const bool valid,
+                                                      unsigned long long& c_plastic, unsigned long long& c_notconv,
+                                                      unsigned long long& c_maxit) {
+  park[0] = double2_t{e[0], e[1]};
+  park[1] = double2_t{e[2], e[3]};
+  park[2] = double2_t{e[4], e[5]};
+  double eq;
+  {
+    const double third = (e[0] + e[1] + e[2]) * (1.0 / 3.0);
+    const double d[6] = {e[0] - third, e[1] - third, e[2] - third, e[3], e[4], e[5]};
+    double dd = 0.0;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) dd += d[c] * d[c];
+    eq = sqrt((2.0 / 3.0) * dd);
+  }
+  double se;
+  if (eq < RO_EPS) {
+    se = 3.0 * mu * eq;                                   // linear branch: c1 = lambda, c2 = 2 mu, c3 = 0, wn = 0
+  } else {
+    const double i3mu = prm.c[RO_I3MU], beta = prm.c[RO_BETA], isig0 = prm.c[RO_ISIG0], n = prm.c[RO_N];
+    const double nbeta = prm.h2;
+    double x = fmin(prm.h1 * eq, prm.sig0 * exp(log(eq / beta) * prm.c[RO_INVN]));
+    double df;
+    unsigned iters = 0;
+    for (;;) {
+      const double r = exp(n * log(x * isig0));
+      const double f = x * i3mu + beta * r - eq;
+      df = i3mu + nbeta * r / fmax(prm.c[RO_ESIG], x);
+      const double dx = f / df;
+      x -= dx;
+      ++iters;
+      if (fabs(dx) <= prm.rtol * x) break;
+      if (iters >= (unsigned)prm.maxit) { if (valid) ++c_notconv; break; }
+    }
+    se = x;
+    const double dse = 1.0 / fmax(df, prm.tol);
+    const double sr = se / eq;
+    // K 1x1 + dse ne x ne + sr (2/3 P - ne x ne),  P = I - 1/3 1x1
+    c1 = prm.kappa - (2.0 / 9.0) * sr;
+    c2 = (2.0 / 3.0) * sr;
+    c3 = dse - sr;
+    wn = 1.0 / se;
+    if (valid) {
+      ++c_plastic;
+      c_maxit = iters > c_maxit ? iters : c_maxit;
+    }
+  }
+  asm volatile("" ::: "memory");   // the strain is read back from LDS, not kept in registers
+  double et[6];
+  {
+    const double2_t a = park[0], b = park[1], c = park[2];
+    et[0] = a.x; et[1] = a.y; et[2] = b.x; et[3] = b.y; et[4] = c.x; et[5] = c.y;
+  }
+  const double tr = et[0] + et[1] + et[2];
+  const double third = tr * (1.0 / 3.0);
+  const double d[6] = {et[0] - third, et[1] - third, et[2] - third, et[3], et[4], et[5]};
+  const double g = se * (2.0 / 3.0) / fmax(eq, RO_EPS);   // sig_e ne = g dev(e)
+  const double ktr = prm.kappa * tr;
+  s[0] = ktr + g * d[0];
+  s[1] = ktr + g * d[1];
+  s[2] = ktr + g * d[2];
+  s[3] = g * d[3];
+  s[4] = g * d[4];
+  s[5] = g * d[5];
 }
 
 // GRAD = 0: the strain comes from the (N,6) array `eps`.  GRAD = 1: it is evaluated in the kernel from
@@ -118,9 +210,10 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
        tile += tile_stride) {
     const int64_t base = tile * WAVE;
     const int npts = (n - base) < WAVE ? (int)(n - base) : WAVE;
-    if constexpr (LAW == LAW_J2_VOCE) {
+    if constexpr (LAW == LAW_J2_VOCE || LAW == LAW_RAMBERG_OSGOOD) {
       // the lane index is re-read through an opaque copy once per tile: per-lane invariants hoisted out of the
-      // tile loop otherwise push the Voce kernels over their 128-register budget (2-8 spilled VGPRs)
+      // tile loop otherwise push the Voce kernels over their 128-register budget (2-8 spilled VGPRs; the fused
+      // Ramberg-Osgood kernels, whose inlined exp / log are live at the same time, 2-16)
       asm volatile("" : "+v"(lane));
       lane &= WAVE - 1;
     }
@@ -143,7 +236,7 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
         for (int k = 0; k < 3; ++k) stage2[k * WAVE + lane] = v[k];
       }
       // ---- old state, SoA (issued before the LDS round trip completes) -------------------------
-      if constexpr (LAW != LAW_ELASTIC) {
+      if constexpr (ss_has_state<LAW>) {
         if (valid) {
           p_n = stream_load<3>(s0 + gi);
 #pragma unroll
@@ -207,7 +300,7 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
         e[3] = r * (Hd[1] + Hd[3]); e[4] = r * (Hd[2] + Hd[6]); e[5] = r * (Hd[5] + Hd[7]);
       }
       // old state only now: 14 registers fewer live through the gradient evaluation
-      if constexpr (LAW != LAW_ELASTIC) {
+      if constexpr (ss_has_state<LAW>) {
         if (valid) {
           p_n = stream_load<3>(s0 + gi);
 #pragma unroll
@@ -220,7 +313,7 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
     double c1 = lambda, c2 = 2.0 * mu, c3 = 0.0;
     double wn = 0.0;   // n = dev(sigma) wn: the direction the tangent is built with (0 for an elastic point)
     double p_new = p_n;
-    if constexpr (LAW != LAW_ELASTIC) {
+    if constexpr (ss_has_state<LAW>) {
       // trial elastic strain                                   mfront:52  eel += deto
 #pragma unroll
       for (int c = 0; c < 6; ++c) e[c] -= ep[c];
@@ -295,12 +388,17 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
     // sigma = lambda tr(eel) 1 + 2 mu eel                                      mfront:76
     const double ltr = lambda * (e[0] + e[1] + e[2]);
     double s[6];
+    if constexpr (LAW == LAW_RAMBERG_OSGOOD) {
+      // no state: stress and tangent coefficients of the total strain
+      ramberg_osgood_update(prm, mu, e, stage2 + lane * 3, s, c1, c2, c3, wn, valid, c_plastic, c_notconv, c_maxit);
+    } else {
     s[0] = ltr + 2.0 * mu * e[0];
     s[1] = ltr + 2.0 * mu * e[1];
     s[2] = ltr + 2.0 * mu * e[2];
     s[3] = 2.0 * mu * e[3];
     s[4] = 2.0 * mu * e[4];
     s[5] = 2.0 * mu * e[5];
+    }
     {
       // stress, p and what the tangent is made of (quadrature_map.py:322-324 asserts on flux, state and Ct): a hardening
       // slope that is not finite at the returned state leaves the stress finite and c3 not
@@ -309,7 +407,7 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
     }
 
     // ---- 4. new state, SoA -------------------------------------------------------------------
-    if constexpr (LAW != LAW_ELASTIC) {
+    if constexpr (ss_has_state<LAW>) {
       if (valid) {
         stream_store<1>(s1 + gi, p_new);
 #pragma unroll
@@ -321,11 +419,11 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
     stage2[lane * 3 + 0] = double2_t{s[0], s[1]};
     stage2[lane * 3 + 1] = double2_t{s[2], s[3]};
     stage2[lane * 3 + 2] = double2_t{s[4], s[5]};
-    if constexpr (LAW != LAW_ELASTIC && TL == TL_PACK4) {
+    if constexpr (ss_has_coef<LAW> && TL == TL_PACK4) {
       double2_t* c4 = reinterpret_cast<double2_t*>(coef) + lane * 2;
       c4[0] = double2_t{c1, c2};
       c4[1] = double2_t{c3, wn};
-    } else if constexpr (LAW != LAW_ELASTIC) {
+    } else if constexpr (ss_has_coef<LAW>) {
       double* cf = coef + lane * 9;
       cf[0] = c1; cf[1] = c2; cf[2] = c3;
       // n = dev(sigma) wn, every operation individually rounded (the host rebuilds it with the same three lines)
@@ -348,7 +446,7 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
     }
     // ---- 7. coalesced tangent store: entry pair (i, j..j+1) of point q ---------------------------
     if constexpr (TL == TL_PACK4) {
-      static_assert(LAW != LAW_ELASTIC, "the elastic tangent is a constant: nothing to write");
+      static_assert(ss_has_coef<LAW>, "the elastic tangent is a constant: nothing to write");
       if (npts == WAVE) {   // 64 x 4 doubles: two 1 KiB wave stores
         double2_t* gct = reinterpret_cast<double2_t*>(ct + base * 4);
         const double2_t* c4 = reinterpret_cast<const double2_t*>(coef);
@@ -362,7 +460,7 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
       }
     } else if constexpr (TL == TL_COEF) {
       // the staged coefficients as they are: 64 x 9 doubles, contiguous (4.5 KiB per tile)
-      static_assert(LAW != LAW_ELASTIC, "the elastic tangent is a constant: nothing to write");
+      static_assert(ss_has_coef<LAW>, "the elastic tangent is a constant: nothing to write");
       if (npts == WAVE) {
         double2_t* gct = reinterpret_cast<double2_t*>(ct + base * 9);
         const double2_t* c2 = reinterpret_cast<const double2_t*>(coef);
@@ -464,6 +562,7 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
   store_block_stats(stats, c_plastic, c_notconv, c_nan, c_maxit, red);
 }
 
+#ifndef DXM_UPDATE_KERNELS_ONLY   // (ramberg_osgood.hip: the rebuild kernels below are dxmat.hip's)
 // coefficients (N, 9) -> full tangent (N, 36), both in HBM: what a rank runs after all-gathering the 72 B/point
 // coefficient form of the J2 tangent instead of its 288 B/point block (sharding.allgather_tangent): 360 B/point of
 // HBM traffic buy 216 B/point less on the xGMI links.  Same staging and store loops as step 7 of the update kernel.
@@ -582,5 +681,6 @@ expand_pack4_kernel(const int64_t n, const double* __restrict__ sig, const doubl
     wave_lds_sync();
   }
 }
+#endif  // DXM_UPDATE_KERNELS_ONLY
 
 }  // namespace dxm

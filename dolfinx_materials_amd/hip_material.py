@@ -84,9 +84,9 @@ class HIPMaterial:
         ``tangent_layout="sym"`` (small-strain laws only) makes ``integrate`` return the 21
         upper-triangle entries per point, ``(N, 21)``, instead of the full ``(N, 6, 6)`` block the
         reference's ``jacobian_flatten`` expects (``conventions.unpack_sym_tangent`` expands it);
-        ``"coef"`` (J2 laws) the nine coefficients ``(c1, c2, c3, n[6])`` of ``Ct = c1 1x1 + c2 I + c3 n x n``,
+        ``"coef"`` (J2 laws and Ramberg-Osgood) the nine coefficients ``(c1, c2, c3, n[6])`` of ``Ct = c1 1x1 + c2 I + c3 n x n``,
         ``(N, 9)`` (``conventions.tangent_from_coefficients``; an assembly can use the rank structure directly);
-        ``"pack4"`` only ``(c1, c2, c3, w)``, ``(N, 4)``: the flow direction is ``n = dev(stress) w`` by construction of the
+        ``"pack4"`` (the same laws) only ``(c1, c2, c3, w)``, ``(N, 4)``: the flow direction is ``n = dev(stress) w`` by construction of the
         kernels, so a consumer that holds the stress of the same update rebuilds the block bit for bit
         (``conventions.tangent_from_pack4``, ``dxm_expand_tangent_pack4_device``; 80 B/point of stress + tangent).
 
@@ -217,12 +217,20 @@ class HIPMaterial:
                 "Split the domain into one QuadratureMap per material (QuadratureMap(mesh, deg, material, cells=...), as the "
                 "reference's multi-material demo does) -- the reference's own JAX back-end ignores per-point values altogether")
         value = float(arr[0])
+        old, old_prop = getattr(obj, parts[-1]), self.material_properties.get(key)
         setattr(obj, parts[-1], value)
         self.material_properties[key] = value
         if self._parts:
             prm = np.asarray(self.behavior.params(), dtype=np.float64)
-            for h, *_ in self._parts:
-                self._chk(self._lib.dxm_set_params(h, prm.ctypes.data_as(C.POINTER(C.c_double)), prm.size))
+            try:
+                for h, *_ in self._parts:
+                    self._chk(self._lib.dxm_set_params(h, prm.ctypes.data_as(C.POINTER(C.c_double)), prm.size))
+            except DxmError:
+                # refused (the handle keeps its parameters): the descriptor keeps them too.  A material over several GPUs
+                # validates on every handle alike, so the first one refuses before any other has changed
+                setattr(obj, parts[-1], old)
+                self.material_properties[key] = old_prop
+                raise
 
     def default_properties(self):
         """``generic.py:122-123``: the base class's (empty) defaults -- the properties of a behaviour live in ``material_properties``

@@ -226,3 +226,39 @@ class FeFpJ2Plasticity(FiniteStrainBehavior):
         out = {"elasticity.E": self.elasticity.E, "elasticity.nu": self.elasticity.nu}
         out.update(_hardening_properties(self.yield_stress))
         return out
+
+
+class RambergOsgoodNonLinearElasticity(SmallStrainBehavior):
+    """Small-strain Ramberg-Osgood nonlinear elasticity, no internal state
+    (``tests/mfront/RambergOsgoodNonLinearElasticity.mfront``): the equivalent strain is
+    ``eps_e = sig_e / (3 mu) + beta (sig_e / sig0)^n`` with ``beta = alpha sig0 / E``; ``sig0 > 0``, ``alpha > 0``, ``n >= 1``.
+
+    ``JAXMaterial(RambergOsgoodNonLinearElasticity(...), gradient_name="Strain", flux_name="Stress")`` stands where the
+    reference uses ``MFrontMaterial(lib, "RambergOsgoodNonLinearElasticity", material_properties=...)``
+    (``tests/mfront/test_nonlinear_elasticity.py``); :meth:`from_mfront_properties` takes that dictionary."""
+
+    law = _lib.LAW_RAMBERG_OSGOOD
+
+    def __init__(self, elasticity: LinearElasticIsotropic, sig0: float, alpha: float, n: float):
+        self.elasticity = elasticity
+        self.sig0 = float(sig0)
+        self.alpha = float(alpha)
+        self.n = float(n)
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict):
+        """The ``material_properties`` of the reference's MFront test: ``YoungModulus``, ``PoissonRatio``,
+        ``YieldStrength``, ``alpha``, ``n``."""
+        known = {"YoungModulus", "PoissonRatio", "YieldStrength", "alpha", "n"}
+        missing, extra = known - set(props), set(props) - known
+        if missing or extra:
+            raise ValueError(f"Ramberg-Osgood material properties: missing {sorted(missing)}, unknown {sorted(extra)}")
+        el = LinearElasticIsotropic(E=float(props["YoungModulus"]), nu=float(props["PoissonRatio"]))
+        return cls(el, sig0=props["YieldStrength"], alpha=props["alpha"], n=props["n"])
+
+    def params(self):
+        return [self.elasticity.E, self.elasticity.nu, self.sig0, self.alpha, self.n]
+
+    def flat_properties(self):
+        return {"elasticity.E": self.elasticity.E, "elasticity.nu": self.elasticity.nu, "sig0": self.sig0, "alpha": self.alpha,
+                "n": self.n}

@@ -71,7 +71,17 @@ enum {
   /* the same finite-strain law with linear hardening R(p) = sig0 + H p.
    * params = [E, nu, sig0, H] */
   DXM_LAW_FEFP_J2_LINEAR = 4,
-  DXM_LAW_COUNT = 5
+  /* small-strain Ramberg-Osgood nonlinear elasticity, no internal state
+   * (tests/mfront/RambergOsgoodNonLinearElasticity.mfront): eps_e = sqrt(2/3 dev(eps):dev(eps)),
+   * sigma = K tr(eps) 1 + sig_e ne with ne = 2 dev(eps) / (3 max(eps_e, 1e-12)), sig_e the root of
+   * sig_e / (3 mu) + beta (sig_e / sig0)^n = eps_e, beta = alpha sig0 / E (3 mu eps_e below eps_e = 1e-12).
+   * Local Newton per point under dxm_set_newton(maxit, rtol): stops when |step| <= rtol sig_e.
+   * dxm_stats: n_plastic = points on the Newton branch (eps_e >= 1e-12), max_local_iters = the most Newton
+   * iterations of a point, n_not_converged = points that reached maxit, n_nan as for J2.
+   * Tangent layouts "sym", "coef" and "pack4" as for J2.  Not served by a custom-hardening build.
+   * params = [E, nu, sig0, alpha, n] with sig0 > 0, alpha > 0, n >= 1 */
+  DXM_LAW_RAMBERG_OSGOOD = 5,
+  DXM_LAW_COUNT = 6
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */
@@ -128,9 +138,9 @@ int dxm_set_params(dxm_material* m, const double* params, int n_params);
 /* Tangent layout integrate writes, doubles per point:
  *   DXM_TANGENT_FULL   n_flux*n_grad (36 / 81), row-major: what `jacobian_flatten` holds (quadrature_map.py:83-105);
  *   DXM_TANGENT_SYM    21 upper-triangle entries (i <= j), small-strain laws (symmetric tangent);
- *   DXM_TANGENT_COEF   9 = (c1, c2, c3, n[0..5]) of Ct = c1 1x1 + c2 I + c3 n x n, J2 laws
+ *   DXM_TANGENT_COEF   9 = (c1, c2, c3, n[0..5]) of Ct = c1 1x1 + c2 I + c3 n x n, J2 laws and Ramberg-Osgood
  *                      (tests/mfront/IsotropicLinearHardeningPlasticity.mfront:66-69 with M expanded);
- *   DXM_TANGENT_PACK4  4 = (c1, c2, c3, w), J2 laws: the kernels form n = dev(stress) w, so the stress of the same update
+ *   DXM_TANGENT_PACK4  4 = (c1, c2, c3, w), J2 laws and Ramberg-Osgood: the kernels form n = dev(stress) w, so the stress of the same update
  *                      and these four rebuild the block bit for bit (dxm_expand_tangent_pack4_device). */
 /* dxm_stats.upload */
 enum { DXM_UPLOAD_NONE = 0, DXM_UPLOAD_PAGE_LOCKED = 1 /* the caller's array was page-locked already: DMA */,

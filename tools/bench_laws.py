@@ -2,7 +2,13 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood]
+
+ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
+alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
+plateau of the curve).  Its line also carries the time of the arithmetic-free probe with the same three streams
+(stream_mix_elastic_shape_launch in tools/libstreammix.so, same arrays, same grid) and the ratios to it and to the elastic
+kernel when that ran in the same process.
 """
 import argparse
 import json
@@ -53,6 +59,44 @@ def cpu_port(law, ns, budget=4.0):
     return {"Mpoints_per_s": round(best[0], 2), "threads": best[1], "sample": ns, "kind": "port (oracle/oracle_c.c)"}
 
 
+# tests/mfront/test_nonlinear_elasticity.py:11-15
+RO_E, RO_NU, RO_SIG0, RO_ALPHA, RO_N = 100e3, 0.3, 500.0, 0.4, 100.0
+
+
+def ramberg_osgood_strains(n, seed=2024, emax=1e-2):
+    """Equivalent strain uniform over [0, emax], random deviatoric directions, a volumetric part of up to the same size."""
+    rng = np.random.default_rng(seed)
+    d = rng.standard_normal((n, 6))
+    d[:, :3] -= d[:, :3].mean(axis=1, keepdims=True)
+    d /= np.linalg.norm(d, axis=1, keepdims=True) * np.sqrt(2.0 / 3.0)
+    ee = rng.uniform(0.0, emax, n)
+    eps = d * ee[:, None]
+    eps[:, :3] += (ee * rng.uniform(-1.0, 1.0, n))[:, None]
+    return eps
+
+
+def probe_ms(g, flux, ct, n, blocks, reps, warmup):
+    """Median time of the arithmetic-free elastic-shape stream (48 B in, 48 + 288 B out per point) on the same arrays."""
+    import ctypes
+
+    import torch
+
+    lib = ctypes.CDLL(os.path.join(ROOT, "tools", "libstreammix.so"))
+    fn = lib.stream_mix_elastic_shape_launch
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
+    st = torch.cuda.current_stream().cuda_stream
+    for _ in range(warmup):
+        assert fn(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), n, blocks, st) == 0
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for e0, e1 in ev:
+        e0.record()
+        fn(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), n, blocks, st)
+        e1.record()
+    torch.cuda.synchronize()
+    return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -61,7 +105,11 @@ def main():
     ap.add_argument("--laws", nargs="+", default=["elastic", "j2_linear", "j2_voce", "fefp"])
     ap.add_argument("--cpu-sample", type=int, default=0, help="also time the plain-C oracle on this many points")
     ap.add_argument("--sym", action="store_true", help="symmetric-packed tangent (small-strain laws)")
+    ap.add_argument("--blocks-per-cu", type=int, nargs="+", default=None,
+                    help="ramberg_osgood: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
     a = ap.parse_args()
+    if a.cpu_sample and "ramberg_osgood" in a.laws:
+        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood law")
     import torch
 
     import dolfinx_materials_amd.materials as jm
@@ -72,8 +120,13 @@ def main():
     n = a.points
     el = jm.LinearElasticIsotropic(E=E, nu=NU)
     res = []
+    elastic_ms = None
     for law in a.laws:
-        if law == "elastic":
+        if law == "ramberg_osgood":
+            ro_eps = ramberg_osgood_strains(n)
+            beh, hist = jm.RambergOsgoodNonLinearElasticity(jm.LinearElasticIsotropic(E=RO_E, nu=RO_NU), RO_SIG0, RO_ALPHA, RO_N), [ro_eps, ro_eps]
+            del ro_eps
+        elif law == "elastic":
             beh, hist = jm.ElasticBehavior(el), j2_history(n)[1:3]
         elif law == "j2_linear":
             beh, hist = jm.vonMisesIsotropicHardening(el, jm.LinearHardening(SIG0_LIN, H_LIN)), j2_history(n)[1:3]
@@ -95,16 +148,26 @@ def main():
         st = torch.cuda.current_stream().cuda_stream
         m.integrate_device(g[0].data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
         m.data_manager.update()  # s0 = state after the first increment
-        for _ in range(a.warmup):
-            m.integrate_device(g[1].data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+
+        def timed():
+            for _ in range(a.warmup):
+                m.integrate_device(g[1].data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+            torch.cuda.synchronize()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+            for e0, e1 in ev:
+                e0.record()
+                m.integrate_device(g[1].data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+                e1.record()
+            torch.cuda.synchronize()
+            return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+        ms = timed()
         rc, stats = m.stats()
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
-        for e0, e1 in ev:
-            e0.record()
-            m.integrate_device(g[1].data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
-            e1.record()
-        torch.cuda.synchronize()
-        ms = float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+        sweep = {}
+        if law == "ramberg_osgood" and a.blocks_per_cu:   # (after the shipped grid's timing and status)
+            for b in a.blocks_per_cu:
+                m.set_option("blocks_per_cu", b)
+                sweep[b] = round(timed(), 4)
         ab = m.algorithmic_bytes_per_point - (15 * 8 if sym else 0)
         r = {
             "law": law + ("+sym21" if sym else ""), "points": n, "kernel_ms": round(ms, 4), "Mpoints_per_s": round(n / ms / 1e3, 1),
@@ -112,6 +175,18 @@ def main():
             "plastic_fraction": round(stats["n_plastic"] / n, 4), "max_local_iters": stats["max_local_iters"],
             "not_converged": stats["n_not_converged"], "rc": rc,
         }
+        if law == "elastic" and not sym:
+            elastic_ms = ms
+        if law == "ramberg_osgood":
+            r["kernel"] = m.kernel_name
+            if sweep:
+                r["kernel_ms_by_blocks_per_cu"] = sweep
+            if not sym and n % 64 == 0:
+                pms = probe_ms(g[1], flux, ct, n, 32 * torch.cuda.get_device_properties(0).multi_processor_count, a.reps, a.warmup)
+                r["probe_ms"] = round(pms, 4)
+                r["ratio_to_probe"] = round(ms / pms, 3)
+            if elastic_ms:
+                r["ratio_to_elastic"] = round(ms / elastic_ms, 3)
         if a.cpu_sample:
             r["cpu_port"] = cpu_port(law, a.cpu_sample)
         print(json.dumps(r), flush=True)
