@@ -128,6 +128,8 @@ using dxm_host::expand_coef_tangent;
 using dxm_host::expand_pack4_tangent;
 using dxm_host::expand_fefp_tangent;
 using dxm_host::fill_const_tangent;
+using dxm_host::CtRoute;
+using dxm_host::Route;
 static_assert(dxm_host::THIRD == SS_THIRD && dxm_host::FEFP_RECORD == FEFP_REC, "host rebuilds and kernels share these constants");
 
 // ------------------------------------------------------------------------------------------
@@ -1009,6 +1011,77 @@ static int ensure_host_path_buffers(dxm_material* m, bool need_grad = true) {
 
 }  // extern "C"
 
+// What a host-buffer call is asked to do (dxm_host::plan_transfer decides from it).  One pointer query per array; the rows forms
+// land flux and tangent in the library's own page-locked areas and ask about neither.
+static dxm_host::TransferRequest transfer_request(const dxm_material* m, const double* flux_aos, const double* isv_aos, const double* ct_aos,
+                                                  bool staged_grad, bool fused, bool rows) {
+  const LawDesc& d = kLaws[m->law];
+  const int64_t n = m->n;
+  dxm_host::TransferRequest r{};
+  r.law = m->law; r.n_grad = d.n_grad; r.n_flux = d.n_flux; r.n_isv_fields = d.n_isv_fields;
+  for (int f = 0; f < d.n_isv_fields; ++f) {
+    r.isv_dim[f] = d.isv_dim[f];
+    if (m->isv_out[f]) r.bound_fields |= 1u << f;
+  }
+  r.layout = m->tangent_layout; r.tangent_size = tangent_size(m); r.n = n;
+  r.flux = flux_aos != nullptr; r.isv_aos = isv_aos != nullptr; r.ct = ct_aos != nullptr;
+  r.rows = rows; r.staged_grad = staged_grad; r.fused = fused;
+  const bool any = m->opt_pageable_dma;
+  r.flux_locked = any || (!rows && page_locked(flux_aos, sizeof(double) * n * d.n_flux));
+  r.isv_locked = any || page_locked(isv_aos, sizeof(double) * n * isv_total(d));
+  r.ct_locked = any || (!rows && page_locked(ct_aos, sizeof(double) * n * r.tangent_size));
+  r.packed_transfer = m->opt_packed_transfer; r.packed_min_points = m->opt_packed_min_points;
+  r.split_streams = m->opt_split_streams; r.pipeline = m->opt_pipeline; r.max_chunks = m->opt_max_chunks;
+  return r;
+}
+
+// The streams, page-locked landing areas, worker pool, events, staging ring and field scratch a plan names (the device arrays
+// every call uses: ensure_host_path_buffers).  A regrown area is forgotten by the handle before it is freed: a failed free must
+// not leave a pointer for dxm_destroy to free again.
+static int ensure_plan_buffers(dxm_material* m, const dxm_host::TransferPlan& plan) {
+  const LawDesc& d = kLaws[m->law];
+  const int64_t n = m->n;
+  const int total = isv_total(d);
+  if (!m->pipe_stream) HIP_TRY(hipStreamCreateWithFlags(&m->pipe_stream, hipStreamNonBlocking));
+  if (m->opt_split_streams && !m->down_stream2) HIP_TRY(hipStreamCreateWithFlags(&m->down_stream2, hipStreamNonBlocking));
+  if (plan.need_pool) {
+    if (plan.need_h_coef && m->h_coef_per_point < plan.land) {
+      double* old = m->h_coef;
+      m->h_coef = nullptr;
+      m->h_coef_per_point = 0;
+      if (old) HIP_TRY(hipHostFree(old));
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_coef), sizeof(double) * n * plan.land, hipHostMallocDefault));
+      m->h_coef_per_point = plan.land;
+    }
+    if (plan.need_h_flux && !m->h_flux) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_flux), sizeof(double) * n * d.n_flux, hipHostMallocDefault));
+    if (plan.need_h_isv && !m->h_isv) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_isv), sizeof(double) * n * total, hipHostMallocDefault));
+    if (!m->pool || (int)m->pool->threads.size() != m->opt_host_threads) {
+      delete m->pool;
+      m->pool = new HostPool(m->opt_host_threads);
+    }
+    m->elastic_lm[0] = m->prm.lambda;
+    m->elastic_lm[1] = m->prm.mu;
+  }
+  for (int c = 0; c < plan.chunks.nchunks; ++c) {
+    if (!m->chunk_done[c]) HIP_TRY(hipEventCreateWithFlags(&m->chunk_done[c], hipEventDisableTiming));
+    if (plan.split && !m->kernel_done[c]) HIP_TRY(hipEventCreateWithFlags(&m->kernel_done[c], hipEventDisableTiming));
+  }
+  if (plan.req.staged_grad) {
+    const int64_t need = plan.chunks.csize * d.n_grad;
+    if (m->ring_slot_doubles < need) {
+      double* old = m->h_grad_ring;
+      m->h_grad_ring = nullptr;
+      m->ring_slot_doubles = 0;
+      if (old) HIP_TRY(hipHostFree(old));
+      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_grad_ring), sizeof(double) * need * DXM_RING, hipHostMallocDefault));
+      m->ring_slot_doubles = need;
+    }
+    for (hipEvent_t& e : m->ring_done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  if (plan.fields_own_scratch && !m->d_isv_fields) HIP_TRY(hipMalloc(&m->d_isv_fields, sizeof(double) * n * total));
+  return 0;
+}
+
 // Host-buffer form, shared by dxm_integrate and dxm_integrate_displacement.
 //   upload(off, cnt, stream) enqueues whatever produces m->d_grad[off .. off+cnt) on `stream`.
 // Large batches are cut into chunks (multiples of 256 points): the H2D and the kernel of chunk c+1 overlap the D2H of
@@ -1036,108 +1109,12 @@ static int run_and_download(dxm_material* m, Upload upload, double* flux_aos, do
   const LawDesc& d = kLaws[m->law];
   const int64_t n = m->n;
   const int total = isv_total(d);
-  // rows (dxm_integrate_rows: J2 laws, full layout, flux and tangent requested): flux_aos / ct_aos are the BASES of larger
-  // arrays, point i is their row rows[i].  Always the 32 B/point form; the stress lands in the library's own page-locked
-  // area and the worker threads that rebuild the blocks put both where they belong -- the caller's arrays see CPU stores only.
-  const bool rowmode = rows != nullptr;
-  // ... and so are the bound state fields (dxm_bind_isv_output): in the rows forms the bound pointers are the BASES of the Functions
-  // over all cells; the fields land in the library's page-locked area and the worker threads put point i into row rows[i]
-  bool isv_rows = false;
-  if (rowmode) for (int f = 0; f < d.n_isv_fields; ++f) isv_rows = isv_rows || m->isv_out[f] != nullptr;
-  const bool fefp = d.n_grad == 9;
-  // a J2 handle with the "sym" layout: (c1, c2, c3, w) cross PCIe like for the full layout (32 instead of 168 B/point) and the
-  // workers rebuild the 21 upper-triangle entries from them and the stress (expand_pack4_tangent_sym); needs the stress in
-  // page-locked memory like the pack4 form below, else the kernel's own 21 entries are downloaded
-  const bool sym_packed = !rowmode && m->opt_packed_transfer >= 2 && m->tangent_layout == DXM_TANGENT_SYM && m->law != DXM_LAW_ELASTIC_ISO && !fefp &&
-                          ct_aos != nullptr && flux_aos != nullptr && n >= m->opt_packed_min_points &&
-                          (m->opt_pageable_dma || page_locked(flux_aos, sizeof(double) * n * d.n_flux));
-  const bool packed = rowmode || sym_packed || (m->opt_packed_transfer && m->tangent_layout == DXM_TANGENT_FULL && ct_aos != nullptr && n >= m->opt_packed_min_points);
-  // the rows forms of a handle whose OWN layout is packed (sym / coef / pack4): the kernel writes that layout, it lands in the
-  // library's page-locked area like the stress, and the worker threads MOVE point i to row rows[i] -- nothing is rebuilt
-  const bool rows_plain = rowmode && m->tangent_layout != DXM_TANGENT_FULL;
-  const bool constant = packed && !rows_plain && m->law == DXM_LAW_ELASTIC_ISO;
-  // small strain: (c1, c2, c3, w) only -- the direction n is rebuilt from the stress, which the caller receives in
-  // page-locked memory as part of the same chunk -- else the nine coefficients
-  const bool pack4 = packed && !constant && !fefp && !rows_plain && (rowmode || (m->opt_packed_transfer >= 2 && flux_aos != nullptr &&
-                     (m->opt_pageable_dma || page_locked(flux_aos, sizeof(double) * n * d.n_flux))));
-  const int tl = rows_plain ? m->tangent_layout : (packed && !constant ? (pack4 ? TL_PACK4 : TL_COEF) : m->tangent_layout);   // layout of this call's launches
-  const int np = rows_plain ? tangent_size(m) : (fefp ? FEFP_REC : (pack4 ? 4 : 9));   // doubles per point of what lands in h_coef
-  const int nfull = sym_packed ? 21 : d.n_flux * d.n_grad;      // doubles per point of what the workers rebuild in the caller's array
-  const int job = sym_packed ? -4 : np;                         // HostPool job code of that rebuild
-  const int nt = packed && !constant ? np : tangent_size(m);   // doubles per point in d_ct: the packed form of this call, else the handle's layout
-  if (!m->pipe_stream) HIP_TRY(hipStreamCreateWithFlags(&m->pipe_stream, hipStreamNonBlocking));
-  if (m->opt_split_streams && !m->down_stream2) HIP_TRY(hipStreamCreateWithFlags(&m->down_stream2, hipStreamNonBlocking));
-  if (packed || host_grad) {
-    const int land = fefp ? FEFP_REC : (np > 9 ? np : 9);   // (9 covers both packed forms of the J2 laws; a "sym" handle in the rows forms lands 21)
-    if (packed && !constant && m->h_coef_per_point < land) {
-      if (m->h_coef) HIP_TRY(hipHostFree(m->h_coef));
-      m->h_coef = nullptr;
-      m->h_coef_per_point = 0;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_coef), sizeof(double) * n * land, hipHostMallocDefault));
-      m->h_coef_per_point = land;
-    }
-    if (rowmode && !m->h_flux) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_flux), sizeof(double) * n * d.n_flux, hipHostMallocDefault));
-    if (isv_rows && !m->h_isv) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_isv), sizeof(double) * n * total, hipHostMallocDefault));
-    if (!m->pool || (int)m->pool->threads.size() != m->opt_host_threads) {
-      delete m->pool;
-      m->pool = new HostPool(m->opt_host_threads);
-    }
-    m->elastic_lm[0] = m->prm.lambda;
-    m->elastic_lm[1] = m->prm.mu;
-  }
-  // short chunks (up to 64) whenever little crosses PCIe per point -- the packed forms of this call AND a handle whose own layout
-  // is packed (sym / coef / pack4: 168 / 72 / 32 B/point of tangent): with 8 long chunks the first result lands after 5 of the
-  // 28 ms of a 1e7-point pack4 call (profiles/r06_packed_update.md); the full 288 B/point block keeps its 8
-  const bool short_chunks = packed || (m->tangent_layout != DXM_TANGENT_FULL && ct_aos != nullptr);
-  // Three streams instead of two (option split_streams, default on) when every chunk starts with a DMA upload from page-locked
-  // memory: uploads + kernels of all chunks on one stream, the downloads of chunk c on one of two others behind the chunk's
-  // kernel_done event.  An upload queued on the stream that also carries a chunk's downloads costs the device-to-host
-  // direction -- 80 to 136 B/point against 48 up -- 4-8 ms per 1e7 points (raw HIP calls: 27-32 ms against 24-25); split,
-  // the 1.36 GB of a pack4 update with its state fields land in 25.4 ms (53 GB/s) instead of 27.4-30.6, the 0.8 GB of the lazy
-  // mode in 15.6 ms instead of 20-24, and the times stop moving from call to call.  With too many chunks the same scheme runs at
-  // a third of the link rate (1e7 points: from 32 chunks of four downloads, or 64 of two, on; profiles/r06_packed_update.md):
-  // the number of chunks is capped below.
-  // Staged uploads (a pageable gradient array through the ring) and the fused displacement form (no per-chunk upload at
-  // all) keep the two alternating streams.
-  const bool split_ok = m->opt_split_streams && m->opt_pipeline && host_grad == nullptr && fused == nullptr;
-  // How many chunks the three-stream scheme takes before it turns slower than the two alternating streams grows with the batch
-  // (profiles/r06_hostpath_split_chunk_sweep.jsonl, 3e5 ... 1e7 points x 2 ... 24 chunks): 6 at 3e5 points, 8 at 1e6, 12 at
-  // 2-3e6, 16 at 5e6, 24 at 1e7 -- one chunk more and the call takes up to 1.7 x as long.  7 sqrt(n / 1e6) stays on the good
-  // side at every size measured (4, 7, 9-12, 15, 22), where the scheme beats alternating chunks by 8-25 %.
-  int split_cap = (int)(7.0 * std::sqrt((double)n / 1e6));
-  split_cap = split_cap < 1 ? 1 : (split_cap > 24 ? 24 : split_cap);
-  const dxm_host::ChunkPlan plan = dxm_host::plan_chunks(n, short_chunks, host_grad != nullptr, split_ok && m->opt_max_chunks > split_cap ? split_cap : m->opt_max_chunks, m->opt_pipeline);
-  const int nchunks = plan.nchunks;
-  for (int c = 0; c < nchunks; ++c)
-    if (!m->chunk_done[c]) HIP_TRY(hipEventCreateWithFlags(&m->chunk_done[c], hipEventDisableTiming));
-  const bool split = split_ok && nchunks > 1;
-  if (split)
-    for (int c = 0; c < nchunks; ++c)
-      if (!m->kernel_done[c]) HIP_TRY(hipEventCreateWithFlags(&m->kernel_done[c], hipEventDisableTiming));
-  const int64_t csize = plan.csize;
-  if (host_grad) {
-    const int64_t need = csize * d.n_grad;
-    if (m->ring_slot_doubles < need) {
-      if (m->h_grad_ring) HIP_TRY(hipHostFree(m->h_grad_ring));
-      m->h_grad_ring = nullptr;
-      HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&m->h_grad_ring), sizeof(double) * need * DXM_RING, hipHostMallocDefault));
-      m->ring_slot_doubles = need;
-    }
-    for (hipEvent_t& e : m->ring_done) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  double* field_scratch = m->d_isv;
-  if (isv_aos && total > 0) {
-    bool delivering = false;
-    for (int f = 0; f < d.n_isv_fields; ++f) delivering = delivering || m->isv_out[f] != nullptr;
-    if (delivering) {
-      if (!m->d_isv_fields) HIP_TRY(hipMalloc(&m->d_isv_fields, sizeof(double) * n * total));
-      field_scratch = m->d_isv_fields;
-    }
-  }
-  const bool any = m->opt_pageable_dma;
-  const bool flux_locked = rowmode || any || page_locked(flux_aos, sizeof(double) * n * d.n_flux);   // rowmode: into h_flux
-  const bool isv_locked = any || page_locked(isv_aos, sizeof(double) * n * total);
-  const bool ct_locked = rowmode || any || page_locked(ct_aos, sizeof(double) * n * tangent_size(m));
+  const dxm_host::TransferRequest r = transfer_request(m, flux_aos, isv_aos, ct_aos, host_grad != nullptr, fused != nullptr, rows != nullptr);
+  const dxm_host::TransferPlan plan = dxm_host::plan_transfer(r);
+  const int nchunks = plan.chunks.nchunks;
+  const int64_t csize = plan.chunks.csize;
+  if (int rc = ensure_plan_buffers(m, plan)) return rc;
+  double* const field_scratch = plan.fields_own_scratch ? m->d_isv_fields : m->d_isv;
   int stats_off = 0, issued = 0, submitted = 0;
   hipStream_t streams[2] = {m->own_stream, m->pipe_stream};
   // An early return (a failing HIP call part-way through the chunk loop) leaves kernels, ring copies and downloads of
@@ -1166,8 +1143,9 @@ static int run_and_download(dxm_material* m, Upload upload, double* flux_aos, do
       for (int t = 0; t < 64; ++t) p->wait_copy(t);   // staging copies still read the caller's gradient array
       p->wait();
     }
-  } drain{(packed || host_grad) ? m->pool : nullptr};
-  if (constant && !rowmode) m->pool->submit(m->elastic_lm, ct_aos, n, 0);   // nothing to wait for
+  } drain{plan.need_pool ? m->pool : nullptr};
+  if (plan.ct == CtRoute::fill) m->pool->submit(m->elastic_lm, ct_aos, n, 0);   // nothing to wait for
+  const dxm_host::ChunkTargets targets{flux_aos, ct_aos, m->h_coef, m->h_flux, m->h_isv, m->isv_out, rows, m->elastic_lm};
   // chunk p of the caller's pageable gradient array -> its ring slot, by the worker threads, asynchronously
   auto stage_chunk = [&](int p) -> int {
     const int64_t o = (int64_t)p * csize;
@@ -1177,20 +1155,15 @@ static int run_and_download(dxm_material* m, Upload upload, double* flux_aos, do
                         sizeof(double) * ((n - o) < csize ? (n - o) : csize) * d.n_grad, p);
     return 0;
   };
-  // rows forms: the bound state fields of chunk [o, o + cnt) from the landing area to their rows, on the worker threads
-  auto scatter_fields = [&](int64_t o, int64_t cnt) {
-    for (int f = 0, before = 0; f < d.n_isv_fields; before += d.isv_dim[f], ++f)
-      if (m->isv_out[f]) m->pool->submit_scatter(m->h_isv + n * before + o * d.isv_dim[f], m->isv_out[f], rows + o, cnt, d.isv_dim[f]);
-  };
   double ms_wait_copy = 0.0, ms_first_copy = 0.0;   // option verbose: time the issue loop spent waiting for staging copies
   const int ahead = m->opt_stage_ahead;
   for (int p = 0; p < ahead; ++p) if (int rc = stage_chunk(p)) return rc;
   for (int c = 0; c < nchunks; ++c) {
-    const int64_t off = (int64_t)c * csize;
+    const int64_t off = plan.chunks.offset(c);
     if (off >= n) break;
-    const int64_t cnt = (n - off) < csize ? (n - off) : csize;
-    hipStream_t st = split ? m->own_stream : streams[c & 1];                         // upload + kernels of this chunk
-    hipStream_t sd = split ? ((c & 1) ? m->down_stream2 : m->pipe_stream) : st;      // its downloads (split: two download streams take turns)
+    const int64_t cnt = plan.chunks.count(c, n);
+    hipStream_t st = plan.split ? m->own_stream : streams[c & 1];                         // upload + kernels of this chunk
+    hipStream_t sd = plan.split ? ((c & 1) ? m->down_stream2 : m->pipe_stream) : st;      // its downloads (split: two download streams take turns)
     if (int rc = upload(off, cnt, st)) return rc;
     const double* gptr = fused ? m->d_flux : m->d_grad + off * d.n_grad;
     if (host_grad) {
@@ -1219,12 +1192,12 @@ static int run_and_download(dxm_material* m, Upload upload, double* flux_aos, do
     MeshSource src{};
     if (fused) { src = *fused; src.point0 = off; }
     if (int rc = launch_range(m, off, cnt, gptr, m->d_flux + off * d.n_flux,
-                              m->d_ct + off * nt, st, stats_off, &grid, fused ? &src : nullptr, tl))
+                              m->d_ct + off * plan.nt, st, stats_off, &grid, fused ? &src : nullptr, plan.tl))
       return rc;
     stats_off += grid;
     // device side of the chunk first (pack kernels of the internal state variables included), then its downloads (split: on
     // one of the two download streams, behind the chunk's kernel_done event)
-    if (isv_aos && total > 0) {
+    if (plan.isv != Route::none) {
       // the kernel wrote state[1]; s1_alias is cleared below, address it directly
       const bool alias = m->s1_alias;
       m->s1_alias = false;
@@ -1232,51 +1205,35 @@ static int run_and_download(dxm_material* m, Upload upload, double* flux_aos, do
       m->s1_alias = alias;
       if (rc) return rc;
     }
-    // fields of the final state bound to host rows (dxm_bind_isv_output: the x.array of the ISV Functions): an (N, total)
-    // device scratch holds them field after field, [n * sum of the dims before f] + off * dim_f -- d_isv itself when the call
-    // has no isv_aos, its own scratch when d_isv carries the interleaved rows of isv_aos (two layouts cannot share one area:
-    // the chunks overlap on two streams and a pageable isv_aos is downloaded from d_isv after the loop)
-    for (int f = 0, before = 0; f < d.n_isv_fields; before += d.isv_dim[f], ++f) {
-      if (!m->isv_out[f]) continue;
-      if (int rc = pack_isv_field_range(m, f, off, cnt, field_scratch + n * before + off * d.isv_dim[f], st)) return rc;
-    }
-    if (split) {
+    // the bound state fields (dxm_bind_isv_output: the x.array of the ISV Functions), field after field
+    for (int f = 0; f < d.n_isv_fields; ++f)
+      if (m->isv_out[f])
+        if (int rc = pack_isv_field_range(m, f, off, cnt, field_scratch + dxm_host::field_slice(r, f, off), st)) return rc;
+    if (plan.split) {
       HIP_TRY(hipEventRecord(m->kernel_done[c], st));
       HIP_TRY(hipStreamWaitEvent(sd, m->kernel_done[c], 0));
     }
-    if (flux_aos && flux_locked)
-      HIP_TRY(hipMemcpyAsync((rowmode ? m->h_flux : flux_aos) + off * d.n_flux, m->d_flux + off * d.n_flux,
+    if (plan.flux == Route::dma || plan.flux == Route::rows)
+      HIP_TRY(hipMemcpyAsync((plan.flux == Route::rows ? m->h_flux : flux_aos) + off * d.n_flux, m->d_flux + off * d.n_flux,
                              sizeof(double) * cnt * d.n_flux, hipMemcpyDeviceToHost, sd));
-    if (ct_aos && !constant && (packed || ct_locked)) {
-      double* dst = packed ? m->h_coef + off * np : ct_aos + off * nt;
-      HIP_TRY(hipMemcpyAsync(dst, m->d_ct + off * nt, sizeof(double) * cnt * nt, hipMemcpyDeviceToHost, sd));
+    if (plan.ct == CtRoute::dma || plan.ct_lands()) {
+      double* dst = plan.ct == CtRoute::dma ? ct_aos + off * plan.nt : m->h_coef + off * plan.np;
+      HIP_TRY(hipMemcpyAsync(dst, m->d_ct + off * plan.nt, sizeof(double) * cnt * plan.nt, hipMemcpyDeviceToHost, sd));
     }
-    if (isv_aos && total > 0 && isv_locked)
+    if (plan.isv == Route::dma)
       HIP_TRY(hipMemcpyAsync(isv_aos + off * total, m->d_isv + off * total, sizeof(double) * cnt * total, hipMemcpyDeviceToHost, sd));
-    for (int f = 0, before = 0; f < d.n_isv_fields; before += d.isv_dim[f], ++f) {
+    for (int f = 0; f < d.n_isv_fields; ++f) {
       if (!m->isv_out[f]) continue;
-      double* land = isv_rows ? m->h_isv + n * before + off * d.isv_dim[f] : m->isv_out[f] + off * d.isv_dim[f];
-      HIP_TRY(hipMemcpyAsync(land, field_scratch + n * before + off * d.isv_dim[f], sizeof(double) * cnt * d.isv_dim[f], hipMemcpyDeviceToHost, sd));
+      const int64_t at = dxm_host::field_slice(r, f, off);
+      double* land = plan.fields == Route::rows ? m->h_isv + at : m->isv_out[f] + off * d.isv_dim[f];
+      HIP_TRY(hipMemcpyAsync(land, field_scratch + at, sizeof(double) * cnt * d.isv_dim[f], hipMemcpyDeviceToHost, sd));
     }
     HIP_TRY(hipEventRecord(m->chunk_done[c], sd));
     issued = c + 1;
     // a pageable upload blocks this thread for its whole duration, so earlier chunks land while the later ones are
     // still being issued: hand them to the workers now, not after the loop
-    if (packed && (!constant || rowmode))
-      while (submitted < issued && hipEventQuery(m->chunk_done[submitted]) == hipSuccess) {
-        const int64_t o = (int64_t)submitted * csize;
-        if (rowmode) {
-          const int64_t cn = (n - o) < csize ? (n - o) : csize;
-          if (rows_plain) {
-            m->pool->submit_scatter(m->h_flux + o * d.n_flux, flux_aos, rows + o, cn, d.n_flux);
-            m->pool->submit_scatter(m->h_coef + o * np, ct_aos, rows + o, cn, np);
-          }
-          else m->pool->submit(constant ? m->elastic_lm : m->h_coef + o * np, ct_aos, cn, constant ? 0 : np, m->h_flux + o * d.n_flux, rows + o, flux_aos);
-          if (isv_rows) scatter_fields(o, cn);
-        }
-        else m->pool->submit(m->h_coef + o * np, ct_aos + o * nfull, (n - o) < csize ? (n - o) : csize, job, pack4 ? flux_aos + o * d.n_flux : nullptr);
-        ++submitted;
-      }
+    if (plan.chunk_jobs)
+      while (submitted < issued && hipEventQuery(m->chunk_done[submitted]) == hipSuccess) dxm_host::submit_chunk(*m->pool, plan, targets, submitted++);
   }
   (void)hipGetLastError();   // hipEventQuery reports "not ready" through the error state
   m->last_grid = stats_off;
@@ -1288,33 +1245,23 @@ static int run_and_download(dxm_material* m, Upload upload, double* flux_aos, do
   for (int c = 0; c < issued; ++c) {
     HIP_TRY(hipEventSynchronize(m->chunk_done[c]));
     if (m->opt_verbose && (c % 8 == 7 || c == 0)) fprintf(stderr, "[dxm host path] chunk %d landed at +%.2f ms after issue (issue loop took %.2f ms)\n", c, ms_since(t_issued), std::chrono::duration<double, std::milli>(t_issued - t_enter).count());
-    if (packed && (!constant || rowmode) && c >= submitted) {
-      const int64_t off = (int64_t)c * csize;
-      const int64_t cnt = (n - off) < csize ? (n - off) : csize;
-      if (rowmode) {
-        if (rows_plain) {
-          m->pool->submit_scatter(m->h_flux + off * d.n_flux, flux_aos, rows + off, cnt, d.n_flux);
-          m->pool->submit_scatter(m->h_coef + off * np, ct_aos, rows + off, cnt, np);
-        }
-        else m->pool->submit(constant ? m->elastic_lm : m->h_coef + off * np, ct_aos, cnt, constant ? 0 : np, m->h_flux + off * d.n_flux, rows + off, flux_aos);
-        if (isv_rows) scatter_fields(off, cnt);
-      }
-      else m->pool->submit(m->h_coef + off * np, ct_aos + off * nfull, cnt, job, pack4 ? flux_aos + off * d.n_flux : nullptr);
+    if (plan.chunk_jobs && c >= submitted) {
+      dxm_host::submit_chunk(*m->pool, plan, targets, c);
       submitted = c + 1;
     }
   }
   // destinations in ordinary (pageable) memory were left out above: they are filled through the page-locked staging now
   // (download_to_host; slower, and only a C caller that did not use dxm_host_alloc / dxm_host_register gets here)
-  if (flux_aos && !flux_locked)
+  if (plan.flux == Route::staged)
     if (int rc = download_to_host(flux_aos, m->d_flux, sizeof(double) * n * d.n_flux, m->own_stream)) return rc;
-  if (isv_aos && total > 0 && !isv_locked)
+  if (plan.isv == Route::staged)
     if (int rc = download_to_host(isv_aos, m->d_isv, sizeof(double) * n * total, m->own_stream)) return rc;
-  if (ct_aos && !constant && !packed && !ct_locked)
-    if (int rc = download_to_host(ct_aos, m->d_ct, sizeof(double) * n * nt, m->own_stream)) return rc;
+  if (plan.ct == CtRoute::staged)
+    if (int rc = download_to_host(ct_aos, m->d_ct, sizeof(double) * n * plan.nt, m->own_stream)) return rc;
   HIP_TRY(hipEventRecord(m->last_event, m->own_stream));   // everything of this call is complete already
   m->last_event_recorded = true;
   const auto t_landed = std::chrono::steady_clock::now();
-  if (packed) m->pool->wait();
+  if (plan.packed) m->pool->wait();
   if (m->opt_verbose && host_grad) fprintf(stderr, "[dxm host path] %d chunks of %lld points; issue loop waited %.2f ms for staging copies (first chunk %.2f ms)\n", nchunks, (long long)csize, ms_wait_copy, ms_first_copy);
   if (m->opt_verbose) fprintf(stderr, "[dxm host path] all landed at +%.2f ms, workers done %.2f ms later\n", std::chrono::duration<double, std::milli>(t_landed - t_issued).count(), ms_since(t_landed));
   inflight.completed = true;

@@ -2,8 +2,9 @@
 //
 // dxmat.hip includes it for the product; tests/host_side_harness.cpp includes the SAME file and is built twice with
 // clang++ -fsanitize=thread and -fsanitize=address,undefined (tests/test_host_side_sanitizers.py, `-m "not gpu"`), so that the
-// worker pool, the chunk / staging-ring arithmetic, the page-locked range table, the three bit-exact tangent rebuilds, the
-// threaded row moves and the upload-route state machine run under the sanitizers on the CPU box.
+// worker pool, the chunk / staging-ring arithmetic, the transfer plan of the host-buffer form and its chunk hand-off, the page-locked
+// range table, the three bit-exact tangent rebuilds, the threaded row moves and the upload-route state machine run under the
+// sanitizers on the CPU box.
 //
 // What it stands behind, in the reference: the (N, 6, 6) / (N, 9, 9) arrays `integrate` hands back
 // (dolfinx_materials/jaxmat.py:231-234, quadrature_map.py:321) and `_update_vals(field, values, cells)`
@@ -12,6 +13,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstring>
@@ -20,6 +22,8 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+
+#include "../../include/dxmat.h"   // law ids, tangent layouts (plain C)
 
 namespace dxm_host {
 
@@ -281,7 +285,7 @@ struct HostPool {
 // ------------------------------------------------------------------------------------------
 // chunk planner of the host-buffer form, ring slots, status-record capacity
 // ------------------------------------------------------------------------------------------
-// Large batches are cut into up to MAX_CHUNKS chunks (multiples of 256 points; dxmat.hip caps the three-stream scheme at 24).  The
+// Large batches are cut into up to MAX_CHUNKS chunks (multiples of 256 points; plan_transfer caps the three-stream scheme at 24).  The
 // last chunk's host expansion is not hidden behind any transfer: many small chunks keep that tail short.
 struct ChunkPlan {
   int nchunks;
@@ -321,6 +325,177 @@ inline int launch_grid(int64_t cnt, int num_cu, int blocks_per_cu) {
   const int64_t tiles = (cnt + 255) / 256;
   const int64_t cap = (int64_t)num_cu * blocks_per_cu;
   return (int)std::max<int64_t>(1, std::min<int64_t>(tiles, cap));
+}
+
+// ------------------------------------------------------------------------------------------
+// transfer plan of the host-buffer form: every decision run_and_download (dxmat.hip) executes
+// ------------------------------------------------------------------------------------------
+// What the call is asked to do, as plain values.
+struct TransferRequest {
+  int law;                                        // DXM_LAW_*
+  int n_grad, n_flux, n_isv_fields, isv_dim[DXM_MAX_STATE_FIELDS];
+  int layout, tangent_size;                       // the handle's DXM_TANGENT_* and dxm_tangent_size
+  int64_t n;
+  bool flux, isv_aos, ct;                         // the destinations the caller passed
+  bool rows;                                      // the rows forms: flux / ct / bound fields are BASES, point i goes to row rows[i]
+  bool staged_grad;                               // a pageable gradient array, staged through the ring
+  bool fused;                                     // displacement form with the gradient evaluated inside the update kernel
+  unsigned bound_fields;                          // bit f: state field f is bound to host rows (dxm_bind_isv_output)
+  bool flux_locked, isv_locked, ct_locked;        // page-locked, or option pageable_dma (the rows forms do not ask for flux and ct)
+  int packed_transfer;                            // options packed_transfer, packed_min_points, split_streams, pipeline, max_chunks
+  int64_t packed_min_points;
+  bool split_streams, pipeline;
+  int max_chunks;
+};
+
+// How a destination is written: per chunk by DMA into the caller's page-locked array; after the chunk loop through the page-locked
+// staging (download_to_host); or per chunk into the library's own page-locked area, from where the worker threads move point i to
+// row rows[i] (the rows forms).
+enum class Route { none, dma, staged, rows };
+// The tangent, besides those: `fill` the constant elastic block (one worker job, nothing downloaded); `rebuild` the packed form
+// lands in h_coef and the workers rebuild the caller's block from it.  The rows forms land in h_coef and the workers move the
+// handle's own layout into the rows, rebuild the full block there, or fill in the elastic one; the stress goes along in all three.
+enum class CtRoute { none, fill, dma, staged, rebuild, rows_move, rows_rebuild, rows_fill };
+
+struct TransferPlan {
+  TransferRequest req;
+  bool packed;              // the worker threads write the tangent (packed transfer, constant fill, every rows form)
+  int tl;                   // tangent layout of this call's launches (TL_* == DXM_TANGENT_*)
+  int nt;                   // doubles per point in d_ct
+  int np;                   // doubles per point of what lands in h_coef
+  int land;                 // doubles per point h_coef is allocated with
+  int nfull;                // doubles per point the rebuild writes into the caller's array
+  int job;                  // HostPool job code of that rebuild
+  CtRoute ct;
+  Route flux, isv, fields;  // isv: the interleaved rows of isv_aos; fields: the bound state fields
+  bool fields_own_scratch;  // the bound fields are packed into d_isv_fields instead of d_isv
+  bool chunk_jobs;          // submit_chunk has worker jobs for every landed chunk
+  bool need_h_coef, need_h_flux, need_h_isv, need_pool;
+  bool short_chunks;
+  int split_cap;
+  bool split;               // three streams: uploads + kernels on one, the downloads on two others
+  ChunkPlan chunks;
+  bool ct_lands() const { return ct == CtRoute::rebuild || ct == CtRoute::rows_move || ct == CtRoute::rows_rebuild; }   // into h_coef
+};
+
+inline TransferPlan plan_transfer(const TransferRequest& r) {
+  TransferPlan p{};
+  p.req = r;
+  const bool fefp = r.n_grad == 9, elastic = r.law == DXM_LAW_ELASTIC_ISO;
+  int total = 0;
+  for (int f = 0; f < r.n_isv_fields; ++f) total += r.isv_dim[f];
+  // rows (dxm_integrate_rows: J2 laws, full layout, flux and tangent requested): flux_aos / ct_aos are the BASES of larger
+  // arrays, point i is their row rows[i].  Always the 32 B/point form; the stress lands in the library's own page-locked
+  // area and the worker threads that rebuild the blocks put both where they belong -- the caller's arrays see CPU stores only.
+  // ... and so are the bound state fields (dxm_bind_isv_output): in the rows forms the bound pointers are the BASES of the Functions
+  // over all cells; the fields land in the library's page-locked area and the worker threads put point i into row rows[i]
+  const bool flux_locked = r.rows || r.flux_locked;
+  const bool ct_locked = r.rows || r.ct_locked;
+  // a J2 handle with the "sym" layout: (c1, c2, c3, w) cross PCIe like for the full layout (32 instead of 168 B/point) and the
+  // workers rebuild the 21 upper-triangle entries from them and the stress (expand_pack4_tangent_sym); needs the stress in
+  // page-locked memory like the pack4 form below, else the kernel's own 21 entries are downloaded
+  const bool sym_packed = !r.rows && r.packed_transfer >= 2 && r.layout == DXM_TANGENT_SYM && !elastic && !fefp && r.ct && r.flux &&
+                          r.n >= r.packed_min_points && flux_locked;
+  p.packed = r.rows || sym_packed || (r.packed_transfer && r.layout == DXM_TANGENT_FULL && r.ct && r.n >= r.packed_min_points);
+  // the rows forms of a handle whose OWN layout is packed (sym / coef / pack4): the kernel writes that layout, it lands in the
+  // library's page-locked area like the stress, and the worker threads MOVE point i to row rows[i] -- nothing is rebuilt
+  const bool rows_plain = r.rows && r.layout != DXM_TANGENT_FULL;
+  const bool constant = p.packed && !rows_plain && elastic;   // the elastic block is a constant and is only filled in
+  // small strain: (c1, c2, c3, w) only -- the direction n is rebuilt from the stress, which the caller receives in
+  // page-locked memory as part of the same chunk -- else the nine coefficients
+  const bool pack4 = p.packed && !constant && !fefp && !rows_plain && (r.rows || (r.packed_transfer >= 2 && r.flux && flux_locked));
+  p.tl = rows_plain ? r.layout : (p.packed && !constant ? (pack4 ? DXM_TANGENT_PACK4 : DXM_TANGENT_COEF) : r.layout);
+  p.np = rows_plain ? r.tangent_size : (fefp ? FEFP_RECORD : (pack4 ? 4 : 9));
+  p.land = fefp ? FEFP_RECORD : std::max(p.np, 9);   // (9 covers both packed forms of the J2 laws; a "sym" handle in the rows forms lands 21)
+  p.nfull = sym_packed ? 21 : r.n_flux * r.n_grad;
+  p.job = constant ? 0 : (sym_packed ? -4 : p.np);
+  p.nt = p.packed && !constant ? p.np : r.tangent_size;   // the packed form of this call, else the handle's layout
+  if (!r.ct) p.ct = CtRoute::none;
+  else if (r.rows) p.ct = rows_plain ? CtRoute::rows_move : (constant ? CtRoute::rows_fill : CtRoute::rows_rebuild);
+  else if (constant) p.ct = CtRoute::fill;
+  else if (p.packed) p.ct = CtRoute::rebuild;
+  else p.ct = ct_locked ? CtRoute::dma : CtRoute::staged;
+  p.flux = !r.flux ? Route::none : (r.rows ? Route::rows : (flux_locked ? Route::dma : Route::staged));
+  p.isv = !r.isv_aos || total == 0 ? Route::none : (r.isv_locked ? Route::dma : Route::staged);
+  p.fields = !r.bound_fields ? Route::none : (r.rows ? Route::rows : Route::dma);
+  // the bound fields are packed field after field into an (N, total) device scratch: d_isv itself when the call has no isv_aos, its
+  // own scratch when d_isv carries the interleaved rows of isv_aos (two layouts cannot share one area: the chunks overlap on two
+  // streams and a pageable isv_aos is downloaded from d_isv after the loop)
+  p.fields_own_scratch = p.isv != Route::none && p.fields != Route::none;
+  p.chunk_jobs = p.packed && (!constant || r.rows);
+  p.need_h_coef = p.packed && !constant;
+  p.need_h_flux = r.rows;
+  p.need_h_isv = p.fields == Route::rows;
+  p.need_pool = p.packed || r.staged_grad;
+  // short chunks (up to 64) whenever little crosses PCIe per point -- the packed forms of this call AND a handle whose own layout
+  // is packed (sym / coef / pack4: 168 / 72 / 32 B/point of tangent): with 8 long chunks the first result lands after 5 of the
+  // 28 ms of a 1e7-point pack4 call (profiles/r06_packed_update.md); the full 288 B/point block keeps its 8
+  p.short_chunks = p.packed || (r.layout != DXM_TANGENT_FULL && r.ct);
+  // Three streams instead of two (option split_streams, default on) when every chunk starts with a DMA upload from page-locked
+  // memory: uploads + kernels of all chunks on one stream, the downloads of chunk c on one of two others behind the chunk's
+  // kernel_done event.  An upload queued on the stream that also carries a chunk's downloads costs the device-to-host
+  // direction -- 80 to 136 B/point against 48 up -- 4-8 ms per 1e7 points (raw HIP calls: 27-32 ms against 24-25); split,
+  // the 1.36 GB of a pack4 update with its state fields land in 25.4 ms (53 GB/s) instead of 27.4-30.6, the 0.8 GB of the lazy
+  // mode in 15.6 ms instead of 20-24, and the times stop moving from call to call.  With too many chunks the same scheme runs at
+  // a third of the link rate (1e7 points: from 32 chunks of four downloads, or 64 of two, on; profiles/r06_packed_update.md):
+  // the number of chunks is capped below.
+  // Staged uploads (a pageable gradient array through the ring) and the fused displacement form (no per-chunk upload at
+  // all) keep the two alternating streams.
+  const bool split_ok = r.split_streams && r.pipeline && !r.staged_grad && !r.fused;
+  // How many chunks the three-stream scheme takes before it turns slower than the two alternating streams grows with the batch
+  // (profiles/r06_hostpath_split_chunk_sweep.jsonl, 3e5 ... 1e7 points x 2 ... 24 chunks): 6 at 3e5 points, 8 at 1e6, 12 at
+  // 2-3e6, 16 at 5e6, 24 at 1e7 -- one chunk more and the call takes up to 1.7 x as long.  7 sqrt(n / 1e6), truncated to an
+  // integer, stays on the good side at every size measured (3, 7, 9-12, 15, 22), where the scheme beats alternating chunks by 8-25 %.
+  p.split_cap = (int)(7.0 * std::sqrt((double)r.n / 1e6));
+  p.split_cap = p.split_cap < 1 ? 1 : (p.split_cap > 24 ? 24 : p.split_cap);
+  p.chunks = plan_chunks(r.n, p.short_chunks, r.staged_grad, split_ok && r.max_chunks > p.split_cap ? p.split_cap : r.max_chunks, r.pipeline);
+  p.split = split_ok && p.chunks.nchunks > 1;
+  return p;
+}
+
+// point `off` of state field f in a field-major (N, total) area: the fields before f take N * dim each
+inline int64_t field_slice(const TransferRequest& r, int f, int64_t off) {
+  int before = 0;
+  for (int g = 0; g < f; ++g) before += r.isv_dim[g];
+  return r.n * before + off * r.isv_dim[f];
+}
+
+// what the worker jobs of a chunk read and write
+struct ChunkTargets {
+  double* flux;             // the caller's arrays (rows forms: their bases)
+  double* ct;
+  const double* h_coef;     // the library's page-locked landing areas
+  const double* h_flux;
+  const double* h_isv;
+  double* const* isv_out;   // the bound state fields, one array per field (rows forms: their bases)
+  const int64_t* rows;
+  const double* elastic_lm; // lambda, mu of the constant block
+};
+
+// the worker jobs of chunk c once it has landed: its tangent rebuild, or in the rows forms its row moves / rebuilds and the bound
+// state fields into their rows
+inline void submit_chunk(HostPool& pool, const TransferPlan& p, const ChunkTargets& t, int c) {
+  const TransferRequest& r = p.req;
+  const int64_t o = p.chunks.offset(c), cnt = p.chunks.count(c, r.n);
+  const int nf = r.n_flux;
+  switch (p.ct) {
+    case CtRoute::rebuild:   // pack4 and sym read the stress where it landed: the caller's page-locked array
+      pool.submit(t.h_coef + o * p.np, t.ct + o * p.nfull, cnt, p.job, p.tl == DXM_TANGENT_PACK4 ? t.flux + o * nf : nullptr);
+      break;
+    case CtRoute::rows_move:
+      pool.submit_scatter(t.h_flux + o * nf, t.flux, t.rows + o, cnt, nf);
+      pool.submit_scatter(t.h_coef + o * p.np, t.ct, t.rows + o, cnt, p.np);
+      break;
+    case CtRoute::rows_rebuild:
+    case CtRoute::rows_fill:
+      pool.submit(p.ct == CtRoute::rows_fill ? t.elastic_lm : t.h_coef + o * p.np, t.ct, cnt, p.job, t.h_flux + o * nf, t.rows + o, t.flux);
+      break;
+    default:
+      break;
+  }
+  if (p.fields == Route::rows)
+    for (int f = 0; f < r.n_isv_fields; ++f)
+      if (r.bound_fields >> f & 1) pool.submit_scatter(t.h_isv + field_slice(r, f, o), t.isv_out[f], t.rows + o, cnt, r.isv_dim[f]);
 }
 
 // ------------------------------------------------------------------------------------------

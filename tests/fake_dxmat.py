@@ -14,7 +14,7 @@ test).  What it restates, with the lines it follows:
     dxm_set_state               materialize_s1 first (an aliased s1 gets its own storage and brings no copies along)
     dxm_get_io / dxm_io_held    io_mask: s1 shows the copies of s0 while it is served from it
     dxm_bind_isv_output         fields of the final state into bound rows inside every host-buffer call (the rows forms: into row rows[i]
-                                of the bound base)
+                                of the bound base; which route each destination takes: csrc/host_side.hpp plan_transfer)
 
 Entry points that are pure host code (law table, threaded copies, row scatter / gather, index range) go to the real library, which
 loads without a GPU.  Small-strain laws, full tangent layout, one device.
@@ -265,7 +265,7 @@ class FakeDxmat:
                 name, dim = self.FIELDS[field]
                 if idx is None:
                     _rows(addr, m.n, dim)[...] = m.state[1][name].reshape(m.n, dim)
-                else:   # the rows forms: the bound pointer is the base of the array over all rows (run_and_download: isv_rows)
+                else:   # the rows forms: the bound pointer is the base of the array over all rows (plan_transfer: fields route rows)
                     _rows(addr, int(idx.max()) + 1, dim)[idx] = m.state[1][name].reshape(m.n, dim)
         m.io[1] = dict(grad=np.array(grad), flux=r["sig"].copy())
         m.io_valid[1] = 3

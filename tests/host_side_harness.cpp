@@ -53,9 +53,41 @@ static bool same_bits(const std::vector<double>& a, const std::vector<double>& b
   return a.size() == b.size() && (a.empty() || memcmp(a.data(), b.data(), a.size() * sizeof(double)) == 0);
 }
 
+// ---- the law table of dxmat.hip as plan_transfer sees it, and a request with the handle's default options ----------------------
+struct LawRow { int law, n_grad, n_isv_fields, isv_dim[DXM_MAX_STATE_FIELDS]; unsigned layouts; };   // layouts: bit per DXM_TANGENT_*
+static const LawRow kLawRows[] = {
+    {DXM_LAW_ELASTIC_ISO, 6, 0, {0, 0, 0, 0}, 0x3},      // full, sym
+    {DXM_LAW_J2_LINEAR, 6, 2, {1, 6, 0, 0}, 0xf},        // all four
+    {DXM_LAW_J2_VOCE, 6, 2, {1, 6, 0, 0}, 0xf},
+    {DXM_LAW_FEFP_J2_VOCE, 9, 2, {1, 6, 0, 0}, 0x1},     // full only
+    {DXM_LAW_FEFP_J2_LINEAR, 9, 2, {1, 6, 0, 0}, 0x1},
+    {DXM_LAW_RAMBERG_OSGOOD, 6, 0, {0, 0, 0, 0}, 0xf},   // stateless
+};
+enum { ELASTIC, J2_LINEAR, J2_VOCE, FEFP_VOCE, FEFP_LINEAR, RAMBERG_OSGOOD };
+
+static TransferRequest request(int law_row, int layout, int64_t n) {
+  const LawRow& l = kLawRows[law_row];
+  TransferRequest r{};
+  r.law = l.law;
+  r.n_grad = r.n_flux = l.n_grad;
+  r.n_isv_fields = l.n_isv_fields;
+  for (int f = 0; f < DXM_MAX_STATE_FIELDS; ++f) r.isv_dim[f] = l.isv_dim[f];
+  r.layout = layout;
+  r.tangent_size = layout == DXM_TANGENT_SYM ? 21 : layout == DXM_TANGENT_COEF ? 9 : layout == DXM_TANGENT_PACK4 ? 4 : l.n_grad * l.n_grad;
+  r.n = n;
+  r.flux = r.ct = true;
+  r.flux_locked = r.isv_locked = r.ct_locked = true;
+  r.packed_transfer = 2;
+  r.packed_min_points = 32768;
+  r.split_streams = r.pipeline = true;
+  r.max_chunks = MAX_CHUNKS;
+  return r;
+}
+
 // ---- A. the chunk pipeline of run_and_download (dxmat.hip) with the device played by memcpy ---------------------------------
 // Per chunk: stage it into its ring slot on the worker threads (`ahead` chunks ahead), wait for the copy, "upload" the slot,
-// hand the chunk's packed tangent to the workers.  Returns the rebuilt blocks; checks the staged gradient arrived intact.
+// hand the chunk to the workers with the product's submit_chunk, for the plans of four rebuilt forms.  Returns the rebuilt blocks;
+// checks the staged gradient arrived intact.
 struct Rebuilt { std::vector<double> ct_coef, ct_pack4, ct_fefp, ct_const, ct_sym; };
 
 static Rebuilt run_pipeline(const Input& in, int threads, int max_chunks, int ahead, HostPool* shared = nullptr) {
@@ -68,7 +100,27 @@ static Rebuilt run_pipeline(const Input& in, int threads, int max_chunks, int ah
   out.ct_sym.assign(n * 21, -1.0);
   HostPool* own = shared ? nullptr : new HostPool(threads);
   HostPool& pool = shared ? *shared : *own;
-  const ChunkPlan plan = plan_chunks(n, true, true, max_chunks, true);
+  // a pageable gradient array staged through the ring, the packed forms at any size; the stress landed in the caller's array
+  auto plan_of = [&](int law_row, int layout, int packed_transfer) {
+    TransferRequest r = request(law_row, layout, n);
+    r.staged_grad = true;
+    r.packed_transfer = packed_transfer;
+    r.packed_min_points = 0;
+    r.max_chunks = max_chunks;
+    return plan_transfer(r);
+  };
+  std::vector<double> stress = in.sg;
+  auto targets = [&](std::vector<double>& ct, const std::vector<double>& h_coef) {
+    return ChunkTargets{stress.data(), ct.data(), h_coef.data(), nullptr, nullptr, nullptr, nullptr, in.lm.data()};
+  };
+  const TransferPlan plans[4] = {plan_of(J2_LINEAR, DXM_TANGENT_FULL, 1), plan_of(J2_VOCE, DXM_TANGENT_FULL, 2), plan_of(J2_LINEAR, DXM_TANGENT_SYM, 2),
+                                 plan_of(FEFP_LINEAR, DXM_TANGENT_FULL, 1)};
+  const ChunkTargets tgts[4] = {targets(out.ct_coef, in.coef), targets(out.ct_pack4, in.cw), targets(out.ct_sym, in.cw), targets(out.ct_fefp, in.rec)};
+  const TransferPlan constant = plan_of(ELASTIC, DXM_TANGENT_FULL, 2);
+  CHECK(plans[0].job == 9 && plans[1].job == 4 && plans[2].job == -4 && plans[3].job == 54 && constant.ct == CtRoute::fill, "pipeline plans");
+  const ChunkPlan plan = plans[0].chunks;
+  for (const TransferPlan& p : plans)
+    CHECK(p.chunks.nchunks == plan.nchunks && p.chunks.csize == plan.csize && p.chunk_jobs, "the four plans cut the batch alike");
   const int ng = 6;
   std::vector<double> ring((size_t)plan.csize * ng * RING, 0.0), d_grad((size_t)n * ng, 0.0);
   const double* host_grad = in.sg.data();   // any (n, 6) array serves as the caller's pageable gradient
@@ -80,7 +132,7 @@ static Rebuilt run_pipeline(const Input& in, int threads, int max_chunks, int ah
     slot_busy[ring_slot(p)] = true;
     pool.copy_async(host_grad + plan.offset(p) * ng, ring.data() + (size_t)ring_slot(p) * plan.csize * ng, sizeof(double) * cnt * ng, p);
   };
-  if (!shared) pool.submit(in.lm.data(), out.ct_const.data(), n, 0);   // the constant block: nothing to wait for
+  if (!shared) pool.submit(in.lm.data(), out.ct_const.data(), n, 0);   // CtRoute::fill, as run_and_download: nothing to wait for
   for (int p = 0; p < ahead; ++p) stage(p);
   for (int c = 0; c < plan.nchunks; ++c) {
     const int64_t off = plan.offset(c), cnt = plan.count(c, n);
@@ -89,10 +141,7 @@ static Rebuilt run_pipeline(const Input& in, int threads, int max_chunks, int ah
     pool.wait_copy(c);
     memcpy(d_grad.data() + off * ng, ring.data() + (size_t)ring_slot(c) * plan.csize * ng, sizeof(double) * cnt * ng);   // the copy kernel
     slot_busy[ring_slot(c)] = false;                                                                                      // ring_done[slot]
-    pool.submit(in.coef.data() + off * 9, out.ct_coef.data() + off * 36, cnt, 9);
-    pool.submit(in.cw.data() + off * 4, out.ct_pack4.data() + off * 36, cnt, 4, in.sg.data() + off * 6);
-    pool.submit(in.cw.data() + off * 4, out.ct_sym.data() + off * 21, cnt, -4, in.sg.data() + off * 6);   // "sym" handles: 21 entries per point
-    pool.submit(in.rec.data() + off * 54, out.ct_fefp.data() + off * 81, cnt, 54);
+    for (int k = 0; k < 4; ++k) submit_chunk(pool, plans[k], tgts[k], c);
   }
   if (shared) {
     pool.submit(in.lm.data(), out.ct_const.data(), n, 0);
@@ -139,15 +188,29 @@ static void test_pipeline(const Input& in, FILE* fout) {
   std::vector<double> ct_rows(M * 36, 7.0), fx_rows(M * 6, 7.0), ct9_rows(M * 81, 7.0), fx9_rows(M * 9, 7.0), ctc_rows(M * 36, 7.0), fxc_rows(M * 6, 7.0), fld6_rows(M * 6, 7.0), fld1_rows(M, 7.0);
   {
     HostPool pool(16);
-    const ChunkPlan plan = plan_chunks(n, true, false, 64, true);
-    for (int c = 0; c < plan.nchunks; ++c) {
-      const int64_t off = plan.offset(c), cnt = plan.count(c, n);
-      if (cnt == 0) break;
-      pool.submit(in.cw.data() + off * 4, ct_rows.data(), cnt, 4, in.sg.data() + off * 6, in.rows.data() + off, fx_rows.data());
-      pool.submit(in.rec.data() + off * 54, ct9_rows.data(), cnt, 54, in.pk.data() + off * 9, in.rows.data() + off, fx9_rows.data());
-      pool.submit(in.lm.data(), ctc_rows.data(), cnt, 0, in.sg.data() + off * 6, in.rows.data() + off, fxc_rows.data());
-      pool.submit_scatter(in.sg.data() + off * 6, fld6_rows.data(), in.rows.data() + off, cnt, 6);      // a bound state field of 6 components
-      pool.submit_scatter(in.cw.data() + off, fld1_rows.data(), in.rows.data() + off, cnt, 1);          // ... and a scalar one (the first n doubles of cw as an (n, 1) field)
+    // the plans of the rows forms (a pageable gradient: short chunks on two alternating streams) for J2 with both state fields
+    // bound, FeFp and the elastic law; what lands in h_coef / h_flux / h_isv is played by the input arrays
+    auto rows_plan = [&](int law_row, unsigned bound) {
+      TransferRequest r = request(law_row, DXM_TANGENT_FULL, n);
+      r.rows = r.staged_grad = true;
+      r.bound_fields = bound;
+      return plan_transfer(r);
+    };
+    const TransferPlan j2 = rows_plan(J2_LINEAR, 0x3), fefp = rows_plan(FEFP_VOCE, 0), cst = rows_plan(ELASTIC, 0);
+    CHECK(j2.ct == CtRoute::rows_rebuild && j2.job == 4 && j2.fields == Route::rows && fefp.ct == CtRoute::rows_rebuild && fefp.job == 54 &&
+              cst.ct == CtRoute::rows_fill, "rows plans");
+    std::vector<double> h_isv(in.cw.begin(), in.cw.begin() + n);   // field-major: p (the first n doubles of cw), then epsp (sg)
+    h_isv.insert(h_isv.end(), in.sg.begin(), in.sg.end());
+    double* fields[DXM_MAX_STATE_FIELDS] = {fld1_rows.data(), fld6_rows.data(), nullptr, nullptr};
+    const int64_t* rw = in.rows.data();
+    const ChunkTargets t_j2{fx_rows.data(), ct_rows.data(), in.cw.data(), in.sg.data(), h_isv.data(), fields, rw, in.lm.data()};
+    const ChunkTargets t_fefp{fx9_rows.data(), ct9_rows.data(), in.rec.data(), in.pk.data(), nullptr, nullptr, rw, in.lm.data()};
+    const ChunkTargets t_cst{fxc_rows.data(), ctc_rows.data(), nullptr, in.sg.data(), nullptr, nullptr, rw, in.lm.data()};
+    for (int c = 0; c < j2.chunks.nchunks; ++c) {
+      if (j2.chunks.count(c, n) == 0) break;
+      submit_chunk(pool, j2, t_j2, c);
+      submit_chunk(pool, fefp, t_fefp, c);
+      submit_chunk(pool, cst, t_cst, c);
     }
     pool.wait();
   }
@@ -399,6 +462,134 @@ static void test_chooser() {
   printf("ok upload chooser\n");
 }
 
+// ---- G. transfer plans of the host-buffer form ------------------------------------------------------------------------------------
+// What run_and_download does with a plan, checked against the request it came from.
+static void check_plan(const TransferPlan& p) {
+  const TransferRequest& r = p.req;
+  int total = 0;
+  for (int f = 0; f < r.n_isv_fields; ++f) total += r.isv_dim[f];
+  const bool rows_job = p.ct == CtRoute::rows_move || p.ct == CtRoute::rows_rebuild || p.ct == CtRoute::rows_fill;   // stress along
+  // every requested destination is written by exactly one route, the others by none
+  const int flux_writers = (p.flux == Route::dma) + (p.flux == Route::staged) + (p.flux == Route::rows && rows_job);
+  CHECK(flux_writers == (r.flux ? 1 : 0) && (p.flux != Route::rows || rows_job), "flux written %d times", flux_writers);
+  CHECK((p.ct != CtRoute::none) == r.ct, "tangent route %d, requested %d", (int)p.ct, (int)r.ct);
+  CHECK((p.isv != Route::none) == (r.isv_aos && total > 0) && p.isv != Route::rows, "isv route %d", (int)p.isv);
+  CHECK((p.fields != Route::none) == (r.bound_fields != 0) && p.fields != Route::staged, "field route %d", (int)p.fields);
+  // the rows forms never DMA into caller memory, the others never scatter
+  if (r.rows)
+    CHECK(p.flux == Route::rows && rows_job && p.isv == Route::none && p.fields != Route::dma, "rows form with a DMA into the caller's memory");
+  else
+    CHECK(!rows_job && p.flux != Route::rows && p.fields != Route::rows, "rows route without rows");
+  // no two layouts share one device scratch: interleaved isv rows and field-major fields never both in d_isv
+  CHECK(p.fields_own_scratch == (p.isv != Route::none && p.fields != Route::none), "field scratch");
+  // widths: d_ct holds n_flux * n_grad doubles per point, h_coef `land`
+  CHECK(p.nt >= 1 && p.nt <= r.n_flux * r.n_grad, "nt %d", p.nt);
+  CHECK(!p.need_h_coef || (p.np >= 1 && p.np <= p.land), "np %d > land %d", p.np, p.land);
+  CHECK(!p.ct_lands() || p.nt == p.np, "what the kernel writes (%d) is not what lands (%d)", p.nt, p.np);
+  CHECK(p.need_h_coef == p.ct_lands(), "h_coef needed %d, tangent lands %d", (int)p.need_h_coef, (int)p.ct_lands());
+  if (p.ct == CtRoute::none || p.ct == CtRoute::fill || p.ct == CtRoute::dma || p.ct == CtRoute::staged || p.ct == CtRoute::rows_fill)
+    CHECK(p.tl == r.layout && p.nt == r.tangent_size, "an unpacked tangent launched as layout %d", p.tl);
+  // pack4 and sym rebuilds read the stress: it lands in page-locked memory or h_flux
+  if ((p.ct == CtRoute::rebuild || p.ct == CtRoute::rows_rebuild) && (p.job == 4 || p.job == -4))
+    CHECK(p.tl == DXM_TANGENT_PACK4 && (p.flux == Route::dma || p.flux == Route::rows), "a stress-based rebuild without the stress landed");
+  // chunks
+  const int cap = std::min(r.max_chunks, MAX_CHUNKS);
+  CHECK(p.split_cap >= 1 && p.split_cap <= 24, "split cap %d", p.split_cap);
+  CHECK(p.chunks.nchunks >= 1 && p.chunks.nchunks <= cap && (r.pipeline || p.chunks.nchunks == 1), "%d chunks", p.chunks.nchunks);
+  if (p.split) CHECK(p.chunks.nchunks > 1 && p.chunks.nchunks <= std::min(p.split_cap, r.max_chunks), "split into %d chunks", p.chunks.nchunks);
+  CHECK(!p.split || (!r.staged_grad && !r.fused && r.split_streams && r.pipeline), "split with staged / fused / option off");
+  // the pool whenever a worker job or the staging ring is needed
+  const bool worker_jobs = p.ct == CtRoute::fill || p.chunk_jobs || p.fields == Route::rows;
+  CHECK(p.need_pool == (p.packed || r.staged_grad) && (!(worker_jobs || r.staged_grad) || p.need_pool), "pool");
+  CHECK(p.chunk_jobs == (p.ct == CtRoute::rebuild || rows_job), "chunk jobs %d for tangent route %d", (int)p.chunk_jobs, (int)p.ct);
+  CHECK(p.need_h_flux == (p.flux == Route::rows) && p.need_h_isv == (p.fields == Route::rows), "landing areas");
+}
+
+static void test_transfer_plans() {
+  // the whole valid product: law x layout, rows form, destinations, bound fields, gradient route, options, locked flags, sizes, caps
+  const int64_t min_points = 32768;
+  const int64_t sizes[] = {1, 255, min_points - 1, min_points, 300000, 1000003, 10000000, 100000000};
+  const int caps[] = {1, 7, MAX_CHUNKS};
+  int64_t count = 0;
+  for (int law = 0; law < (int)(sizeof(kLawRows) / sizeof(kLawRows[0])); ++law)
+    for (int layout = 0; layout < 4; ++layout) {
+      if (!(kLawRows[law].layouts >> layout & 1)) continue;
+      for (int rows = 0; rows < 2; ++rows)
+        for (int present = 0; present < 8; ++present) {   // flux, isv_aos, ct
+          const bool flux = present & 1, isv = present & 2, ct = present & 4;
+          if (rows && (!flux || !ct || isv)) continue;   // the rows forms: flux and tangent, never isv_aos
+          for (unsigned bound = 0; bound < (1u << kLawRows[law].n_isv_fields); ++bound)
+            for (int grad = 0; grad < 3; ++grad)            // page-locked (DMA), staged, fused
+              for (int pt = 0; pt < 3; ++pt)
+                for (int opts = 0; opts < 4; ++opts)        // split_streams, pipeline
+                  for (int locked = 0; locked < 8; ++locked)
+                    for (int64_t n : sizes)
+                      for (int cap : caps) {
+                        TransferRequest r = request(law, layout, n);
+                        r.rows = rows;
+                        r.flux = flux;
+                        r.isv_aos = isv;
+                        r.ct = ct;
+                        r.bound_fields = bound;
+                        r.staged_grad = grad == 1;
+                        r.fused = grad == 2;
+                        r.packed_transfer = pt;
+                        r.split_streams = opts & 1;
+                        r.pipeline = opts & 2;
+                        r.flux_locked = locked & 1;
+                        r.isv_locked = locked & 2;
+                        r.ct_locked = locked & 4;
+                        r.max_chunks = cap;
+                        check_plan(plan_transfer(r));
+                        ++count;
+                        if (g_failures > 20) return;
+                      }
+        }
+    }
+  // the routes the documentation promises
+  int pinned = 0;
+  auto pin = [&](int law, int layout, int64_t n, auto edit, auto expect, const char* what) {
+    TransferRequest r = request(law, layout, n);
+    edit(r);
+    const TransferPlan p = plan_transfer(r);
+    check_plan(p);
+    CHECK(expect(p), "pinned case: %s", what);
+    ++pinned;
+  };
+  auto none = [](TransferRequest&) {};
+  pin(J2_LINEAR, DXM_TANGENT_FULL, 1000000, none, [](const TransferPlan& p) {
+    return p.ct == CtRoute::rebuild && p.tl == DXM_TANGENT_PACK4 && p.np == 4 && p.nt == 4 && p.job == 4 && p.nfull == 36 && p.flux == Route::dma; },
+      "J2, full layout, locked flux: pack4, 4 doubles landed, job 4");
+  pin(J2_VOCE, DXM_TANGENT_SYM, 1000000, none, [](const TransferPlan& p) {
+    return p.ct == CtRoute::rebuild && p.tl == DXM_TANGENT_PACK4 && p.np == 4 && p.nfull == 21 && p.job == -4; }, "sym: 4 landed, 21 rebuilt, job -4");
+  pin(FEFP_VOCE, DXM_TANGENT_FULL, 1000000, none, [](const TransferPlan& p) {
+    return p.ct == CtRoute::rebuild && p.tl == DXM_TANGENT_COEF && p.np == 54 && p.job == 54 && p.nfull == 81 && p.land == 54; }, "FeFp: 54 building blocks");
+  pin(ELASTIC, DXM_TANGENT_FULL, 1000000, none, [](const TransferPlan& p) {
+    return p.ct == CtRoute::fill && !p.need_h_coef && !p.chunk_jobs && p.tl == DXM_TANGENT_FULL; }, "elastic full: constant fill, nothing downloaded");
+  pin(J2_LINEAR, DXM_TANGENT_FULL, 32767, none, [](const TransferPlan& p) {
+    return p.ct == CtRoute::dma && p.nt == 36 && p.tl == DXM_TANGENT_FULL && !p.need_pool; }, "below packed_min_points: DMA of the full block");
+  pin(J2_LINEAR, DXM_TANGENT_SYM, 1000000, [](TransferRequest& r) { r.packed_transfer = 0; }, [](const TransferPlan& p) {
+    return p.ct == CtRoute::dma && p.nt == 21 && p.tl == DXM_TANGENT_SYM; }, "packed_transfer 0: DMA of the handle's layout");
+  pin(J2_LINEAR, DXM_TANGENT_FULL, 1000000, [](TransferRequest& r) { r.packed_transfer = 1; }, [](const TransferPlan& p) {
+    return p.ct == CtRoute::rebuild && p.tl == DXM_TANGENT_COEF && p.np == 9 && p.job == 9; }, "packed_transfer 1: the nine coefficients");
+  pin(J2_LINEAR, DXM_TANGENT_FULL, 1000000, [](TransferRequest& r) { r.flux_locked = false; }, [](const TransferPlan& p) {
+    return p.ct == CtRoute::rebuild && p.np == 9 && p.flux == Route::staged; }, "pageable flux: the nine coefficients, stress staged");
+  pin(J2_LINEAR, DXM_TANGENT_SYM, 1000000, [](TransferRequest& r) { r.rows = true; }, [](const TransferPlan& p) {
+    return p.ct == CtRoute::rows_move && p.np == 21 && p.land == 21 && p.tl == DXM_TANGENT_SYM; }, "rows + sym: rows move of 21");
+  pin(J2_LINEAR, DXM_TANGENT_FULL, 1000000, [](TransferRequest& r) { r.rows = true; r.bound_fields = 3; }, [](const TransferPlan& p) {
+    return p.ct == CtRoute::rows_rebuild && p.job == 4 && p.flux == Route::rows && p.fields == Route::rows && p.need_h_isv; }, "rows + full: pack4 rebuilt into the rows");
+  pin(ELASTIC, DXM_TANGENT_FULL, 1000000, [](TransferRequest& r) { r.rows = true; }, [](const TransferPlan& p) {
+    return p.ct == CtRoute::rows_fill && !p.need_h_coef && p.chunk_jobs; }, "rows + elastic: constant filled into the rows");
+  pin(J2_LINEAR, DXM_TANGENT_FULL, 10000000, [](TransferRequest& r) { r.staged_grad = true; r.packed_transfer = 0; }, [](const TransferPlan& p) {
+    return !p.split && p.ct == CtRoute::dma && p.chunks.nchunks == 32; }, "staged gradient, full layout, packed_transfer 0: two alternating streams, 32 chunks");
+  pin(J2_LINEAR, DXM_TANGENT_FULL, 300000, none, [](const TransferPlan& p) { return p.split && p.split_cap == 3 && p.chunks.nchunks == 3; },
+      "3e5 points: the split cap truncates to 3");
+  pin(J2_LINEAR, DXM_TANGENT_FULL, 10000000, none, [](const TransferPlan& p) { return p.split && p.chunks.nchunks == 22; }, "1e7 points: 22 chunks split");
+  pin(J2_VOCE, DXM_TANGENT_FULL, 1000000, [](TransferRequest& r) { r.isv_aos = true; r.bound_fields = 2; }, [](const TransferPlan& p) {
+    return p.isv == Route::dma && p.fields == Route::dma && p.fields_own_scratch; }, "isv_aos and bound fields: their own scratch");
+  printf("ok transfer plans (%" PRId64 " plans, %d pinned cases)\n", count, pinned);
+}
+
 int main(int argc, char** argv) {
   if (argc < 2) { fprintf(stderr, "usage: %s input.bin [output.bin]\n", argv[0]); return 2; }
   Input in;
@@ -411,6 +602,7 @@ int main(int argc, char** argv) {
   test_copies();
   test_planner();
   test_chooser();
+  test_transfer_plans();
   // ragged and empty batches through the same pipeline
   for (int64_t n : {(int64_t)0, (int64_t)1, (int64_t)255, (int64_t)257}) {
     Input small = in;

@@ -1,5 +1,5 @@
 """The GPU-free host code of libdxmat.so (``dolfinx_materials_amd/csrc/host_side.hpp``: worker pool, chunk planner + staging ring,
-page-locked range table, the bit-exact tangent rebuilds, threaded row moves, upload-route state machine) under ThreadSanitizer
+transfer plan of the host-buffer form over its whole product of requests + the chunk hand-off, page-locked range table, the bit-exact tangent rebuilds, threaded row moves, upload-route state machine) under ThreadSanitizer
 and AddressSanitizer + UBSan, on the CPU box: ``tests/host_side_harness.cpp`` is compiled twice with clang++ and run on
 seeded inputs; its rebuilt tangent blocks are compared with ``oracle/host_rebuild_np.py`` (0 ulp against the fused-multiply-add
 emulation on a sample, 2 ulp-of-the-block against plain numpy on everything).  Also: the Python array reaper of

@@ -92,7 +92,7 @@ def main():
     ap.add_argument("--modes", nargs="+", default=["r01", "packed", "bound"])
     ap.add_argument("--threads", type=int, nargs="+", default=[0])
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--packed-min-points", type=int, default=None, help="option packed_min_points (library default 262144)")
+    ap.add_argument("--packed-min-points", type=int, default=None, help="option packed_min_points (library default 32768)")
     ap.add_argument("--law", default="j2_linear", choices=["j2_linear", "fefp"])
     ap.add_argument("--fresh-input", action="store_true", help="a newly allocated gradient array per call, as QuadratureMap.update hands over")
     ap.add_argument("--pageable-dma", action="store_true", help="option pageable_dma = 1: the runtime's pageable transfer path (faster, fragile)")
