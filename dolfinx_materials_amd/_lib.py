@@ -72,6 +72,10 @@ SYMBOLS = {
     "dxm_npoints": (C.c_int64, [_h]),
     "dxm_law": (C.c_int, [_h]),
     "dxm_set_params": (C.c_int, [_h, _dp, C.c_int]),
+    "dxm_set_param_field": (C.c_int, [_h, C.c_int, C.c_void_p]),
+    "dxm_set_param_field_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_void_p]),
+    "dxm_param_field_mask": (C.c_int, [_h]),
+    "dxm_algorithmic_bytes": (C.c_int, [_h]),
     "dxm_set_newton": (C.c_int, [_h, C.c_int, C.c_double]),
     "dxm_set_tangent_layout": (C.c_int, [_h, C.c_int]),
     "dxm_tangent_size": (C.c_int, [_h]),

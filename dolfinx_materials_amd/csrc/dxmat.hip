@@ -29,6 +29,7 @@
 #include "gradient.hpp"
 #include "small_strain.hpp"
 #include "ramberg_osgood.hpp"
+#include "param_fields.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -212,9 +213,15 @@ struct dxm_material {
   hipEvent_t ring_done[DXM_RING] = {};
   int opt_stage_ahead = 3;
   double unregister_ms = 0.0;   // what releasing the call-scoped page-lock of the gradient array took in the last call
+  // per-point parameter fields (dxm_set_param_field; the two small-strain J2 laws): bit i of pf_mask = params[i] is a field.
+  // The kernels read streams of KERNEL parameters; E and nu fields are kept as given too, (lambda, mu) being functions of both
+  int pf_mask = 0;
+  double* pf_law[2] = {nullptr, nullptr};   // device copies of the E / nu fields, n doubles each
+  double* pf_stream[PF_COUNT] = {};         // device streams (lambda, mu, sig0, h1, h2), n doubles each; null = uniform
 };
 
 static int sync_last(dxm_material* m);
+static int pf_refresh_elastic(dxm_material* m, hipStream_t st);
 
 static void free_state(dxm_material* m) {
   if (!m->state_base) return;
@@ -517,6 +524,8 @@ int dxm_destroy(dxm_material* m) {
   if (m->d_ct) (void)hipFree(m->d_ct);
   if (m->d_field) (void)hipFree(m->d_field);
   if (m->h_grad_ring) (void)hipHostFree(m->h_grad_ring);
+  for (double* q : m->pf_law) if (q) (void)hipFree(q);
+  for (double* q : m->pf_stream) if (q) (void)hipFree(q);
   for (hipEvent_t e : m->ring_done) if (e) (void)hipEventDestroy(e);
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
   if (m->pipe_stream) (void)hipStreamDestroy(m->pipe_stream);
@@ -532,6 +541,13 @@ int dxm_set_params(dxm_material* m, const double* params, int n_params) {
   if (!m || !params) return fail(-1, "null argument");
   if (int rc = build_params(m, params, n_params)) return rc;   // nothing changed: captured graphs stay valid
   ++m->epoch;
+  // bound parameter fields stay bound; (lambda, mu) streams made of one field and one uniform value follow the new value
+  if (m->pf_mask & 3) {
+    DEVICE_GUARD(m);
+    if (int rc = sync_last(m)) return rc;
+    if (int rc = pf_refresh_elastic(m, m->own_stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(m->own_stream));
+  }
   return 0;
 }
 
@@ -833,6 +849,16 @@ static void launch_small_strain(dxm_material* m, int grid, hipStream_t st, int64
   // a fifth wave per SIMD would fit and costs 0.65 % (0.8169 vs 0.8116 / 0.8123 ms per 1e7 points in one process,
   // profiles/archive/r03_j2_ab_pack4.jsonl); the elastic kernel keeps its five.
   constexpr int dyn_lds = LAW == LAW_ELASTIC ? 0 : 2304;
+#ifndef DXM_CUSTOM_HARDENING
+  if constexpr (LAW != LAW_ELASTIC) {
+    if (m->pf_mask) {   // param_fields.hip: the streams advance with the range like the state slots
+      ParamStreams pf{};
+      for (int k = 0; k < PF_COUNT; ++k) pf.p[k] = m->pf_stream[k] ? m->pf_stream[k] + off : nullptr;
+      param_fields_launch(LAW, tl, g, grid, dyn_lds, st, m->prm, pf, cnt, grad, s0, s1, m->ld, flux, ct, bs, src);
+      return;
+    }
+  }
+#endif
 #define DXM_LAUNCH_SS(TL, G)                                                                              \
   hipLaunchKernelGGL((small_strain_kernel<LAW, TL, G>), dim3(grid), dim3(BLOCK), dyn_lds, st, m->prm, cnt, grad, s0, s1, \
                      m->ld, flux, ct, bs, src)
@@ -1673,7 +1699,11 @@ const double* dxm_state_ptr(const dxm_material* m, int which, int field, int com
   return state_of(m, which) + (size_t)(d.isv_slot[field] + comp) * m->ld;
 }
 
-const char* dxm_kernel_name(const dxm_material* m) { return m ? kLaws[m->law].kernel : ""; }
+const char* dxm_kernel_name(const dxm_material* m) {
+  if (!m) return "";
+  if (m->pf_mask) return m->law == DXM_LAW_J2_LINEAR ? "small_strain_field_kernel<1" : "small_strain_field_kernel<2";
+  return kLaws[m->law].kernel;
+}
 
 int dxm_expand_tangent_device(const double* coef_dev, int64_t npoints, double* ct_dev, int device, void* hip_stream) {
   if (npoints < 0) return fail(-1, "negative point count");
@@ -1704,6 +1734,133 @@ int dxm_expand_tangent_pack4_device(const double* flux_dev, const double* pack_d
   hipLaunchKernelGGL(expand_pack4_kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)hip_stream, npoints, flux_dev, pack_dev, ct_dev);
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+// ---- per-point parameter fields -----------------------------------------------------------------------
+}  // extern "C"
+
+// (lambda, mu) streams from the E / nu fields and uniform values as they stand; both streams exist while either is a field
+static int pf_refresh_elastic(dxm_material* m, hipStream_t st) {
+#ifndef DXM_CUSTOM_HARDENING
+  if (!(m->pf_mask & 3) || m->n == 0) return 0;
+  param_fields_elastic_streams(m->n, m->pf_law[0], m->raw_params[0], m->pf_law[1], m->raw_params[1], m->pf_stream[PF_LAMBDA],
+                               m->pf_stream[PF_MU], st);
+  HIP_TRY(hipGetLastError());
+#endif
+  return 0;
+}
+
+static int pf_check(const dxm_material* m, int idx) {
+  if (!m) return fail(-1, "null handle");
+#ifdef DXM_CUSTOM_HARDENING
+  if (m) return fail(-1, "per-point parameter fields are served by the stock libdxmat, not by a custom-hardening build");
+#endif
+  if (m->law != DXM_LAW_J2_LINEAR && m->law != DXM_LAW_J2_VOCE)
+    return fail(-1, "per-point parameter fields exist for DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE only (law %d: %s)", m->law,
+                m->law == DXM_LAW_ELASTIC_ISO ? "the elastic tangent is a constant the host path never downloads"
+                : m->law == DXM_LAW_RAMBERG_OSGOOD ? "Ramberg-Osgood precomputes per-handle Newton constants on the host"
+                                                   : "the FeFp kernels have no registers to spare");
+  if (idx < 0 || idx >= kLaws[m->law].n_params) return fail(-1, "law %d has no parameter %d", m->law, idx);
+  return 0;
+}
+
+// where parameter idx (>= 2) of the J2 laws goes: [E, nu, sig0, H] / [E, nu, sig0, sigu, b]
+static int pf_stream_of(int idx) { return idx == 2 ? PF_SIG0 : idx == 3 ? PF_H1 : PF_H2; }
+
+// device storage a bind of parameter idx needs and does not have yet: allocated before anything is changed
+static int pf_reserve(dxm_material* m, int idx) {
+  const size_t bytes = sizeof(double) * (size_t)(m->n > 0 ? m->n : 1);
+  double** want[3] = {nullptr, nullptr, nullptr};
+  if (idx < 2) { want[0] = &m->pf_law[idx]; want[1] = &m->pf_stream[PF_LAMBDA]; want[2] = &m->pf_stream[PF_MU]; }
+  else want[0] = &m->pf_stream[pf_stream_of(idx)];
+  double* fresh[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < 3; ++k) {
+    if (!want[k] || *want[k]) continue;
+    if (hipMalloc(&fresh[k], bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      for (double* q : fresh) if (q) (void)hipFree(q);
+      return fail(-3, "hipMalloc of a %zu-byte parameter stream failed", bytes);
+    }
+  }
+  for (int k = 0; k < 3; ++k) if (fresh[k]) *want[k] = fresh[k];
+  return 0;
+}
+
+// back to the uniform value of dxm_set_params (the launch before must be complete: the streams are freed)
+static int pf_unbind(dxm_material* m, int idx, hipStream_t st) {
+  if (!(m->pf_mask & (1 << idx))) return 0;
+  m->pf_mask &= ~(1 << idx);
+  ++m->epoch;
+  if (idx >= 2) {
+    double*& q = m->pf_stream[pf_stream_of(idx)];
+    HIP_TRY(hipFree(q));
+    q = nullptr;
+    return 0;
+  }
+  HIP_TRY(hipFree(m->pf_law[idx]));
+  m->pf_law[idx] = nullptr;
+  if (m->pf_mask & 3) {
+    if (int rc = pf_refresh_elastic(m, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+  }
+  for (int k : {PF_LAMBDA, PF_MU}) { HIP_TRY(hipFree(m->pf_stream[k])); m->pf_stream[k] = nullptr; }
+  return 0;
+}
+
+extern "C" {
+
+int dxm_set_param_field(dxm_material* m, int param_index, const double* host_values) {
+  if (int rc = pf_check(m, param_index)) return rc;
+  DEVICE_GUARD(m);
+  if (int rc = sync_last(m)) return rc;
+  if (!host_values) return pf_unbind(m, param_index, m->own_stream);
+  // the rules build_params applies to the scalar, per point; E and nu are constrained one by one, so a partner field needs no look
+  for (int64_t i = 0; i < m->n; ++i) {
+    const double v = host_values[i];
+    if (!std::isfinite(v)) return fail(-1, "parameter %d is not finite at point %lld (%g)", param_index, (long long)i, v);
+    if (param_index == 0 && !(v > 0.0)) return fail(-1, "invalid elastic constant E=%g at point %lld", v, (long long)i);
+    if (param_index == 1 && !(v > -1.0 && v < 0.5)) return fail(-1, "invalid elastic constant nu=%g at point %lld", v, (long long)i);
+  }
+  if (int rc = pf_reserve(m, param_index)) return rc;
+  double* dst = param_index < 2 ? m->pf_law[param_index] : m->pf_stream[pf_stream_of(param_index)];
+  if (int rc = upload_from_host(dst, host_values, sizeof(double) * (size_t)m->n, m->own_stream)) return rc;
+  m->pf_mask |= 1 << param_index;
+  ++m->epoch;
+  if (param_index < 2) {
+    if (int rc = pf_refresh_elastic(m, m->own_stream)) return rc;
+    HIP_TRY(hipStreamSynchronize(m->own_stream));
+  }
+  return 0;
+}
+
+int dxm_set_param_field_device(dxm_material* m, int param_index, const double* dev_values, void* hip_stream) {
+  if (int rc = pf_check(m, param_index)) return rc;
+  DEVICE_GUARD(m);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (!dev_values) {
+    if (int rc = sync_last(m)) return rc;
+    return pf_unbind(m, param_index, st);
+  }
+  // the last launch may still read the streams from another stream: this one waits for it, the host does not
+  if (m->launched && m->last_event_recorded) HIP_TRY(hipStreamWaitEvent(st, m->last_event, 0));
+  else if (int rc = sync_last(m)) return rc;
+  if (int rc = pf_reserve(m, param_index)) return rc;
+  double* dst = param_index < 2 ? m->pf_law[param_index] : m->pf_stream[pf_stream_of(param_index)];
+  if (m->n > 0) HIP_TRY(hipMemcpyAsync(dst, dev_values, sizeof(double) * (size_t)m->n, hipMemcpyDeviceToDevice, st));
+  m->pf_mask |= 1 << param_index;
+  ++m->epoch;
+  if (param_index < 2) return pf_refresh_elastic(m, st);
+  return 0;
+}
+
+int dxm_param_field_mask(const dxm_material* m) { return m ? m->pf_mask : -1; }
+
+int dxm_algorithmic_bytes(const dxm_material* m) {
+  if (!m) return -1;
+  int bytes = kLaws[m->law].alg_bytes;
+  for (const double* q : m->pf_stream) if (q) bytes += 8;
+  return bytes;
 }
 
 int dxm_notify_replay(dxm_material* m) {

@@ -76,7 +76,7 @@ class HIPMaterial:
     """A constitutive behaviour integrated on an MI355X through ``libdxmat.so``."""
 
     def __init__(self, behavior, jit=True, device: int = 0, gradient_name=None, flux_name=None, tangent_layout="full",
-                 lazy_isv=True, devices=None):
+                 lazy_isv=True, devices=None, property_fields=False):
         """``JAXMaterial(behavior, jit=True)`` (``jaxmat.py:144``): ``jit`` is accepted for signature
         compatibility and has no effect -- the kernels are compiled ahead of time (or, for a traced /
         custom hardening law, by hipcc on construction).
@@ -98,13 +98,21 @@ class HIPMaterial:
         and a host-buffer ``integrate`` runs the G chunk pipelines side by side, every GPU's DMA delivering straight
         into its rows of the one host array -- G PCIe links for the PCIe-bound form, no collective, no gather
         (north_star: "reassemble ... into the dolfinx quadrature Function", i.e. into host memory of one process,
-        ``quadrature_map.py:66-70``).  The device-pointer forms belong to one GPU and raise for such a material."""
+        ``quadrature_map.py:66-70``).  The device-pointer forms belong to one GPU and raise for such a material.
+
+        ``property_fields=True`` (small-strain J2 laws of the stock library): :meth:`update_material_property` accepts one value
+        per Gauss point, as ``QuadratureMap.update_material_properties`` hands it for a property that is a ``fem.Function`` or a
+        UFL expression (``quadrature_map.py:160-172``).  The update then runs the kernel that reads the bound parameters as
+        streams, 8 B/point each (a varying ``E`` or ``nu`` binds ``lambda`` and ``mu``: 16).  With ``False`` such a value is
+        refused, as before."""
         if tangent_layout not in ("full", "sym", "coef", "pack4"):
             raise ValueError("tangent_layout must be 'full', 'sym', 'coef' or 'pack4'")
         if not isinstance(jit, (bool, type(None))):
             raise TypeError("the second argument of JAXMaterial / HIPMaterial is `jit` (jaxmat.py:144); pass the GPU index as device=")
         self.jit = bool(jit)
         self.lazy_isv = bool(lazy_isv)
+        self.property_fields = bool(property_fields)
+        self._fields = {}     # property name -> (npoints,) array, for the properties that vary from point to point
         self._serial = 0
         self._serial0 = 0     # counts the changes of s0 (advance, set_initial_state_dict)
         self._bound = {}
@@ -191,6 +199,8 @@ class HIPMaterial:
 
     @property
     def algorithmic_bytes_per_point(self):
+        if self._fields and self._parts:   # + 8 per bound kernel-parameter stream
+            return int(self._lib.dxm_algorithmic_bytes(self._parts[0][0]))
         return int(self._info.algorithmic_bytes_per_point)
 
     @property
@@ -212,10 +222,13 @@ class HIPMaterial:
         # QuadratureMap.update_material_properties hands 0-d arrays for numbers and one value per Gauss point
         # for UFL-valued properties (quadrature_map.py:160-172); a uniform field is a number
         if not np.all(arr == arr[0]):
-            raise NotImplementedError(
-                f"material property {key!r} varies from point to point: the fused kernels take uniform parameters. "
-                "Split the domain into one QuadratureMap per material (QuadratureMap(mesh, deg, material, cells=...), as the "
-                "reference's multi-material demo does) -- the reference's own JAX back-end ignores per-point values altogether")
+            if not self.property_fields:
+                raise NotImplementedError(
+                    f"material property {key!r} varies from point to point: the fused kernels take uniform parameters. "
+                    "Split the domain into one QuadratureMap per material (QuadratureMap(mesh, deg, material, cells=...), as the "
+                    "reference's multi-material demo does) -- the reference's own JAX back-end ignores per-point values altogether -- "
+                    "or, for the small-strain J2 laws, construct the material with property_fields=True")
+            return self._set_property_field(key, arr)
         value = float(arr[0])
         old, old_prop = getattr(obj, parts[-1]), self.material_properties.get(key)
         setattr(obj, parts[-1], value)
@@ -231,6 +244,45 @@ class HIPMaterial:
                 setattr(obj, parts[-1], old)
                 self.material_properties[key] = old_prop
                 raise
+        if key in self._fields:   # accepted: the property is uniform again
+            self._upload_field(key, None, restore=self._fields[key])
+            del self._fields[key]
+
+    def _field_index(self, key):
+        """Position of property ``key`` in the law's parameter vector, for the laws whose kernels read parameter fields."""
+        if self.behavior.law not in (_lib.LAW_J2_LINEAR, _lib.LAW_J2_VOCE) or getattr(self.behavior, "custom_hardening", None) is not None:
+            raise NotImplementedError(
+                f"material property {key!r} varies from point to point: per-point property fields exist for the small-strain J2 laws "
+                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp or custom hardening laws)")
+        return list(self.behavior.flat_properties()).index(key)
+
+    def _upload_field(self, key, arr, restore=None):
+        """Hand every block's handle its slice of ``arr`` (``None``: back to the uniform value).  If a handle refuses, the ones
+        before it get ``restore`` back and the error goes up: nothing has changed."""
+        if not self._parts:
+            return
+        idx = self._field_index(key)
+        done = []
+        try:
+            for h, lo, hi, _ in self._parts:
+                a = None if arr is None else np.ascontiguousarray(arr[lo:hi])
+                self._chk(self._lib.dxm_set_param_field(h, idx, None if a is None else a.ctypes.data))
+                done.append((h, lo, hi))
+        except DxmError:
+            for h, lo, hi in done:
+                a = None if restore is None else np.ascontiguousarray(restore[lo:hi])
+                self._lib.dxm_set_param_field(h, idx, None if a is None else a.ctypes.data)
+            raise
+
+    def _set_property_field(self, key, arr):
+        """One value per Gauss point for property ``key`` (``property_fields=True``)."""
+        self._field_index(key)
+        if self._parts and arr.size != self._n:
+            raise ValueError(f"material property {key!r}: {arr.size} values for {self._n} Gauss points")
+        arr = arr.copy()
+        self._upload_field(key, arr, restore=self._fields.get(key))
+        self._fields[key] = arr
+        self.material_properties[key] = arr
 
     def default_properties(self):
         """``generic.py:122-123``: the base class's (empty) defaults -- the properties of a behaviour live in ``material_properties``
@@ -262,6 +314,16 @@ class HIPMaterial:
                 if self.tangent_layout != "full":
                     self._chk(self._lib.dxm_set_tangent_layout(h, {"sym": 1, "coef": 2, "pack4": 3}[self.tangent_layout]))
                 lo = hi
+        except Exception:
+            self.close()
+            raise
+        # property fields set before the handles existed, or kept from a data manager of the same size
+        try:
+            for key, arr in self._fields.items():
+                if arr.size != self._n:
+                    raise ValueError(f"material property {key!r} holds {arr.size} values, the data manager has {self._n} Gauss points: "
+                                     "set the property again (an array of the new size, or a number)")
+                self._upload_field(key, arr)
         except Exception:
             self.close()
             raise
@@ -602,13 +664,24 @@ class HIPMaterial:
         """A second material of the same behaviour for ``n`` points (same device, same library, full tangent blocks, same Newton
         controls): the explicit-state callables integrate on it, so the state of THIS material (s0 / s1, its mirrors, its bound
         arrays) is never touched.  Kept for the next call of the same size."""
+        if self._fields and n != self._n:
+            raise DxmError(f"explicit-state update of {n} points: the properties {sorted(self._fields)} are fields over the {self._n} Gauss "
+                           "points of this material, so the call must pass one gradient row per Gauss point")
         sc = self.__dict__.get("_scratch_material")
         if sc is None or sc._n != n or not sc._parts:
             if sc is not None:
                 sc.close()
-            sc = HIPMaterial(self.behavior, device=self.device, gradient_name=self._gname, flux_name=self._fname, lazy_isv=False)
+            sc = HIPMaterial(self.behavior, device=self.device, gradient_name=self._gname, flux_name=self._fname, lazy_isv=False,
+                             property_fields=self.property_fields)
             sc.set_data_manager(n)
             self._scratch_material = sc
+        for key in set(sc._fields) - set(self._fields):   # (the scratch material follows this one's fields, array by array)
+            sc._upload_field(key, None)
+            del sc._fields[key]
+        for key, arr in self._fields.items():
+            if sc._fields.get(key) is not arr:
+                sc._upload_field(key, arr)
+                sc._fields[key] = arr
         prm = np.asarray(self.behavior.params(), dtype=np.float64)   # (update_material_property may have changed them since)
         for h in sc._handles():
             sc._chk(sc._lib.dxm_set_params(h, prm.ctypes.data_as(C.POINTER(C.c_double)), prm.size))

@@ -135,6 +135,26 @@ int64_t dxm_npoints(const dxm_material* m);
 int dxm_law(const dxm_material* m);
 /* Material.update_material_property (generic.py:119-120): replace the parameter vector. */
 int dxm_set_params(dxm_material* m, const double* params, int n_params);
+/* Per-point parameter fields, DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE of the stock library (what the reference's
+ * QuadratureMap.update_material_properties hands to update_material_property when a property is a Function or an expression:
+ * one value per Gauss point, quadrature_map.py:160-172).  param_index indexes the law's parameter vector ([E, nu, sig0, H] /
+ * [E, nu, sig0, sigu, b]); host_values holds npoints doubles, of which the library keeps its own device copy; NULL returns the
+ * parameter to the uniform value of dxm_set_params.  Every value is checked with the rules dxm_set_params applies to the
+ * scalar (finite; E > 0; -1 < nu < 0.5); a refusal returns < 0, names the first offending point and leaves the handle as it
+ * was.  The kernels read streams of lambda, mu, sig0, h1, h2 (8 B/point each): a varying E or nu binds both lambda and mu.
+ * dxm_set_params keeps working for the parameters that stay uniform and does not unbind a field.  The other laws refuse
+ * (< 0, message); so does a custom-hardening build. */
+int dxm_set_param_field(dxm_material* m, int param_index, const double* host_values);
+/* The same from npoints doubles in device memory on the handle's device; asynchronous on hip_stream (the copy, and for E / nu
+ * the kernel that forms lambda and mu); dev_values is not referenced once the call is complete on that stream.  Launches that
+ * are to see the field go to the same stream or are ordered after it by the caller.  The values are NOT checked: a value that
+ * makes an update non-finite shows in dxm_stats.n_nan.  NULL unbinds, as above (that form waits for the last launch). */
+int dxm_set_param_field_device(dxm_material* m, int param_index, const double* dev_values, void* hip_stream);
+/* bit i = parameter i is a field */
+int dxm_param_field_mask(const dxm_material* m);
+/* Bytes per point the handle's update kernel moves as it is configured now: dxm_law_info.algorithmic_bytes_per_point plus 8
+ * per bound kernel-parameter stream. */
+int dxm_algorithmic_bytes(const dxm_material* m);
 /* Tangent layout integrate writes, doubles per point:
  *   DXM_TANGENT_FULL   n_flux*n_grad (36 / 81), row-major: what `jacobian_flatten` holds (quadrature_map.py:83-105);
  *   DXM_TANGENT_SYM    21 upper-triangle entries (i <= j), small-strain laws (symmetric tangent);
@@ -227,7 +247,7 @@ const char* dxm_kernel_name(const dxm_material* m);
 /* Identity of the launch configuration: changes whenever a launch captured into a HIP graph before would
  * no longer do what a fresh call does -- dxm_advance (the two state buffers swap: the low bit flips and
  * flips back at the next advance), dxm_set_params / dxm_set_newton / dxm_set_tangent_layout /
- * dxm_set_option and anything else that moves the resident state (the upper bits increase).  Replay a captured graph only while the
+ * dxm_set_param_field(_device) / dxm_set_option and anything else that moves the resident state (the upper bits increase).  Replay a captured graph only while the
  * value equals the one read at capture time.  dxm_revert does not change it. */
 uint64_t dxm_launch_generation(const dxm_material* m);
 /* Tell the handle that the caller has replayed a HIP graph containing a launch of this handle: the replay

@@ -9,6 +9,11 @@ alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is u
 plateau of the curve).  Its line also carries the time of the arithmetic-free probe with the same three streams
 (stream_mix_elastic_shape_launch in tools/libstreammix.so, same arrays, same grid) and the ratios to it and to the elastic
 kernel when that ran in the same process.
+
+--param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
+(dxm_set_param_field; 1 = sig0, 2 = lambda and mu from an E field, 3 = both, 4 / 5 = H | sigu, b as well), in the same process and on
+the same arrays.  The fields hold the uniform values, so every point does the same work as in the uniform run.  Each line carries
+the yardstick (496 + 8 K) / 496 times the uniform time and the spread of the uniform kernel's repeated timings in this run.
 """
 import argparse
 import json
@@ -107,6 +112,8 @@ def main():
     ap.add_argument("--sym", action="store_true", help="symmetric-packed tangent (small-strain laws)")
     ap.add_argument("--blocks-per-cu", type=int, nargs="+", default=None,
                     help="ramberg_osgood: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
+    ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
+                    help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and "ramberg_osgood" in a.laws:
         ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood law")
@@ -191,6 +198,32 @@ def main():
             r["cpu_port"] = cpu_port(law, a.cpu_sample)
         print(json.dumps(r), flush=True)
         res.append(r)
+        if a.param_fields and law in ("j2_linear", "j2_voce") and not sym:
+            import ctypes
+
+            prm = beh.params()
+            order = [2, 0, 3, 4]                       # sig0 (1 stream), E (2: lambda and mu), H | sigu, b
+            uniform = [ms, timed(), timed()]           # the uniform kernel again: the spread the field timings are read against
+            h = m._require()
+            for k in a.param_fields:
+                idx = {1: [2], 2: [0], 3: [2, 0]}.get(k, order[: k - 1])
+                idx = [i for i in idx if i < len(prm)]
+                for i in idx:
+                    v = np.full(n, prm[i])
+                    m._chk(m._lib.dxm_set_param_field(h, i, v.ctypes.data))
+                streams = (m._lib.dxm_algorithmic_bytes(h) - 496) // 8
+                t = [timed(), timed()]
+                for i in idx:
+                    m._chk(m._lib.dxm_set_param_field(h, i, ctypes.c_void_p(None)))
+                uniform.append(timed())
+                base = float(np.median(uniform))
+                yard = base * (496 + 8 * streams) / 496
+                f = {"law": law + f"+fields{streams}", "points": n, "kernel": "small_strain_field_kernel", "streams": streams,
+                     "kernel_ms": [round(x, 4) for x in t], "uniform_ms": [round(x, 4) for x in uniform],
+                     "uniform_spread_ms": round(max(uniform) - min(uniform), 4), "yardstick_ms": round(yard, 4),
+                     "excess_over_yardstick_ms": round(min(t) - yard, 4), "algorithmic_bytes_per_point": 496 + 8 * streams,
+                     "GBs": round((496 + 8 * streams) * n / min(t) / 1e6, 1)}
+                print(json.dumps(f), flush=True)
         del m, g, flux, ct
         torch.cuda.empty_cache()
 
