@@ -30,6 +30,7 @@
 #include "small_strain.hpp"
 #include "ramberg_osgood.hpp"
 #include "param_fields.hpp"
+#include "hyperelastic.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -110,7 +111,14 @@ static const LawDesc kLaws[DXM_LAW_COUNT] = {
     // stateless: the elastic law's stream (48 B in, 48 + 288 B out), with per-point tangent coefficients like J2
     {6, 6, 5, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 384,
      "small_strain_kernel<3"},
+    // id 6 is not assigned (law_known)
+    {0, 0, 0, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 0, nullptr},
+    // Ogden: F in (72 B), PK1 (72) + dP/dF (648) + the isochoric PK2 stress (48) out; the state is written, never read
+    {9, 9, 3, 1, 1, {6, 0, 0, 0}, {"PK2Stress", nullptr, nullptr, nullptr}, {0, 0, 0, 0}, OGDEN_NSLOTS, 840,
+     "ogden_kernel"},
 };
+
+static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
 static int tangent_size(const dxm_material* m);
 
@@ -241,6 +249,26 @@ static int n_params_of(int law) {
 static int build_params(dxm_material* m, const double* p, int np) {
   const int expect = n_params_of(m->law);
   if (np != expect) return fail(-1, "law %d expects %d parameters, got %d", m->law, expect, np);
+  if (m->law == DXM_LAW_OGDEN) {
+    // [alpha, mu, K] (Ogden.mfront); the exponents the kernel needs are formed here once
+    const double alpha = p[0], mu = p[1], K = p[2];
+    if (!(alpha != 0.0) || !std::isfinite(alpha)) return fail(-1, "Ogden: alpha must be finite and non-zero, got %g", alpha);
+    if (!(mu > 0.0) || !std::isfinite(mu)) return fail(-1, "Ogden: mu must be finite and > 0, got %g", mu);
+    if (!(K > 0.0) || !std::isfinite(K)) return fail(-1, "Ogden: K must be finite and > 0, got %g", K);
+    LawParams q{};
+    const double a = 0.5 * alpha;
+    q.mu = mu;
+    q.kappa = K;
+    q.c[OG_A] = a;
+    q.c[OG_AM2] = a - 2.0;
+    q.c[OG_MA3] = -a / 3.0;
+    q.c[OG_M] = a - 1.0;
+    q.maxit = m->maxit;
+    q.rtol = m->rtol;
+    m->prm = q;
+    m->raw_params.assign(p, p + np);
+    return 0;
+  }
   const double E = p[0], nu = p[1];
   if (!(E > 0.0) || !(nu > -1.0 && nu < 0.5)) return fail(-1, "invalid elastic constants E=%g nu=%g", E, nu);
   LawParams q{};
@@ -362,7 +390,7 @@ int dxm_device_count(void) {
 }
 
 int dxm_law_info_get(int law, dxm_law_info* out) {
-  if (law < 0 || law >= DXM_LAW_COUNT || !out) return fail(-1, "unknown law id %d", law);
+  if (!law_known(law) || !out) return fail(-1, "unknown law id %d", law);
   const LawDesc& d = kLaws[law];
   memset(out, 0, sizeof(*out));
   out->n_grad = d.n_grad;
@@ -384,7 +412,7 @@ static int init_state(dxm_material* m) {
   const size_t bytes = (size_t)d.n_slots * m->ld * sizeof(double);
   for (int w = 0; w < 2; ++w) {
     HIP_TRY(hipMemsetAsync(m->state[w], 0, bytes, m->own_stream));
-    if (kLaws[m->law].n_grad == 9) {
+    if (m->law == DXM_LAW_FEFP_J2_VOCE || m->law == DXM_LAW_FEFP_J2_LINEAR) {
       // be_bar = Cp^-1 = identity: unstressed natural configuration
       // (demos/jax/finite_strain_elastoplasticity/finite_strain_elastoplasticity.py:181)
       const int ones[6] = {FEFP_SLOT_BE + 0, FEFP_SLOT_BE + 1, FEFP_SLOT_BE + 2,
@@ -401,7 +429,7 @@ static int init_state(dxm_material* m) {
 }
 
 dxm_material* dxm_create(int law, const double* params, int n_params, int64_t npoints, int device) {
-  if (law < 0 || law >= DXM_LAW_COUNT) { fail(-1, "unknown law id %d", law); return nullptr; }
+  if (!law_known(law)) { fail(-1, "unknown law id %d", law); return nullptr; }
   if (npoints < 0) { fail(-1, "negative point count"); return nullptr; }
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
@@ -415,6 +443,10 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
   // a library built for a user-supplied hardening law carries the hardening kernels only
   if (law == DXM_LAW_RAMBERG_OSGOOD) {
     fail(-1, "Ramberg-Osgood has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build");
+    return nullptr;
+  }
+  if (law == DXM_LAW_OGDEN) {
+    fail(-1, "Ogden hyperelasticity has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build");
     return nullptr;
   }
 #endif
@@ -463,6 +495,7 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
       case DXM_LAW_FEFP_J2_LINEAR: fn = (const void*)fefp_kernel<0, 0>; break;
 #ifndef DXM_CUSTOM_HARDENING
       case DXM_LAW_RAMBERG_OSGOOD: fn = ramberg_osgood_kernel(); break;
+      case DXM_LAW_OGDEN: fn = ogden_kernel_fn(); break;
 #endif
       default: fn = (const void*)fefp_kernel<1, 0>; break;
     }
@@ -487,6 +520,7 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
     if (law == DXM_LAW_J2_VOCE || law == DXM_LAW_FEFP_J2_VOCE || law == DXM_LAW_FEFP_J2_LINEAR) m->blocks_per_cu = 256;
     // Ramberg-Osgood: RO_BLOCKS_PER_CU (DESIGN.md section "Ramberg-Osgood")
     if (law == DXM_LAW_RAMBERG_OSGOOD) m->blocks_per_cu = RO_BLOCKS_PER_CU;
+    if (law == DXM_LAW_OGDEN) m->blocks_per_cu = OGDEN_BLOCKS_PER_CU;   // hyperelastic.hpp
   }
   // one record per workgroup and launch.  A single launch has at most num_cu * 256 workgroups (the largest grid
   // dxm_set_option("blocks_per_cu") allows); the chunked host path appends the records of up to DXM_MAX_CHUNKS
@@ -555,6 +589,8 @@ int dxm_set_tangent_layout(dxm_material* m, int layout) {
   if (!m) return fail(-1, "null handle");
   if (layout != DXM_TANGENT_FULL && layout != DXM_TANGENT_SYM && layout != DXM_TANGENT_COEF && layout != DXM_TANGENT_PACK4)
     return fail(-1, "unknown tangent layout %d", layout);
+  if (layout != DXM_TANGENT_FULL && m->law == DXM_LAW_OGDEN)
+    return fail(-1, "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record (sym / coef / pack4) exists for this law");
   if (layout != DXM_TANGENT_FULL && kLaws[m->law].n_grad == 9)
     return fail(-1, "the FeFp tangent dP/dF is not symmetric: only DXM_TANGENT_FULL is available");
   if ((layout == DXM_TANGENT_COEF || layout == DXM_TANGENT_PACK4) && m->law == DXM_LAW_ELASTIC_ISO)
@@ -893,6 +929,13 @@ static int launch_range(dxm_material* m, int64_t off, int64_t cnt, const double*
       ramberg_osgood_launch(tl, fused ? fused->kind : 0, grid, st, m->prm, cnt, grad, flux, ct, m->d_stats + stats_off, fused ? *fused : none);
       break;
     }
+    case DXM_LAW_OGDEN:   // hyperelastic.hip: F from the (N, 9) array, the full tangent
+      if (fused)
+        return fail(-1, "the Ogden kernel has no fused displacement-gradient form: set option fused_gradient to 0 (F is then evaluated "
+                        "by the gradient kernel) or pass F as an array");
+      if (tl != TL_FULL) return fail(-1, "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record exists for this law");
+      ogden_launch(grid, st, m->prm, cnt, grad, m->state[1] + off, m->ld, flux, ct, m->d_stats + stats_off);
+      break;
 #endif
     case DXM_LAW_FEFP_J2_VOCE:
     case DXM_LAW_FEFP_J2_LINEAR: {
@@ -1759,6 +1802,7 @@ static int pf_check(const dxm_material* m, int idx) {
     return fail(-1, "per-point parameter fields exist for DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE only (law %d: %s)", m->law,
                 m->law == DXM_LAW_ELASTIC_ISO ? "the elastic tangent is a constant the host path never downloads"
                 : m->law == DXM_LAW_RAMBERG_OSGOOD ? "Ramberg-Osgood precomputes per-handle Newton constants on the host"
+                : m->law == DXM_LAW_OGDEN          ? "the Ogden kernel takes its exponents as per-handle constants"
                                                    : "the FeFp kernels have no registers to spare");
   if (idx < 0 || idx >= kLaws[m->law].n_params) return fail(-1, "law %d has no parameter %d", m->law, idx);
   return 0;

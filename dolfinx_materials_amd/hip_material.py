@@ -107,6 +107,9 @@ class HIPMaterial:
         refused, as before."""
         if tangent_layout not in ("full", "sym", "coef", "pack4"):
             raise ValueError("tangent_layout must be 'full', 'sym', 'coef' or 'pack4'")
+        if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_OGDEN:
+            raise ValueError("the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record "
+                             f"(tangent_layout={tangent_layout!r}) exists for this law")
         if not isinstance(jit, (bool, type(None))):
             raise TypeError("the second argument of JAXMaterial / HIPMaterial is `jit` (jaxmat.py:144); pass the GPU index as device=")
         self.jit = bool(jit)
@@ -173,6 +176,12 @@ class HIPMaterial:
             self._info.isv_name[f].decode(): int(self._info.isv_dim[f])
             for f in range(self._info.n_isv_fields)
         }
+
+    @property
+    def _has_be_bar(self):
+        """The FeFp laws: their kernel state (isochoric Cp^-1) is rebuilt from (F, be_bar) when either is set.  (Ogden shares the
+        F / PK1 boundary and has no such state.)"""
+        return "be_bar" in self.internal_state_variables
 
     @property
     def variables(self):
@@ -253,7 +262,7 @@ class HIPMaterial:
         if self.behavior.law not in (_lib.LAW_J2_LINEAR, _lib.LAW_J2_VOCE) or getattr(self.behavior, "custom_hardening", None) is not None:
             raise NotImplementedError(
                 f"material property {key!r} varies from point to point: per-point property fields exist for the small-strain J2 laws "
-                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp or custom hardening laws)")
+                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp, Ogden or custom hardening laws)")
         return list(self.behavior.flat_properties()).index(key)
 
     def _upload_field(self, key, arr, restore=None):
@@ -485,12 +494,12 @@ class HIPMaterial:
                 self._retire_initial_views((1,))
                 self._flux[0] = a.copy()
                 self._serial0 += 1
-            elif key == "be_bar" and self._info.n_grad == 9:
+            elif key == "be_bar" and self._has_be_bar:
                 continue  # handled below together with F
             else:
                 self._retire_final_views(materializing=True)   # dxm_set_state gives s1 its own storage back: its device copies go
                 self._set_state(isv_names.index(key), a)
-        if self._info.n_grad == 9 and ("be_bar" in state or self._gname in state):
+        if self._has_be_bar and ("be_bar" in state or self._gname in state):
             # the kernel's state is the isochoric Cp^-1 (hidden field 2), rebuilt from (F_n, be_bar_n)
             from .conventions import cp_bar_inv_from_be_bar
 

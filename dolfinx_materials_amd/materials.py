@@ -262,3 +262,47 @@ class RambergOsgoodNonLinearElasticity(SmallStrainBehavior):
     def flat_properties(self):
         return {"elasticity.E": self.elasticity.E, "elasticity.nu": self.elasticity.nu, "sig0": self.sig0, "alpha": self.alpha,
                 "n": self.n}
+
+
+class OgdenHyperelasticity(FiniteStrainBehavior):
+    """Finite-strain Ogden hyperelasticity (``demos/mfront/hyperelasticity/Ogden.mfront``): stored energy
+    ``W(F) = (mu / alpha) (J^(-alpha/3) sum_i c_i^(alpha/2) - 3) + K/2 (J - 1)^2`` with ``c_i`` the eigenvalues of ``C = F^T F``
+    and ``J = det F``; ``alpha != 0``, ``mu > 0``, ``K > 0`` (the file's defaults: 28.8, 27778, 69444444).  One internal state
+    variable, ``PK2Stress`` (6): the isochoric part of the second Piola-Kirchhoff stress.
+
+    ``JAXMaterial(OgdenHyperelasticity(...))`` stands where the reference's hyperelasticity demo uses
+    ``MFrontMaterial(lib, "Ogden")``: gradient ``DeformationGradient`` (9), flux ``FirstPiolaKirchhoffStress`` (9), tangent block
+    ``(9, 9)``; :meth:`from_mfront_properties` takes the ``material_properties`` dictionary of that call.  Full tangent only; the
+    displacement forms need option ``fused_gradient`` off (no fused kernel for this law)."""
+
+    law = _lib.LAW_OGDEN
+    gradient_name = "DeformationGradient"
+    flux_name = "FirstPiolaKirchhoffStress"
+    MFRONT_DEFAULTS = {"alpha": 28.8, "mu": 27778.0, "K": 69444444.0}
+
+    def __init__(self, mu: float = MFRONT_DEFAULTS["mu"], alpha: float = MFRONT_DEFAULTS["alpha"], K: float = MFRONT_DEFAULTS["K"]):
+        self.mu = float(mu)
+        self.alpha = float(alpha)
+        self.K = float(K)
+        if not (self.alpha != 0.0 and self.mu > 0.0 and self.K > 0.0 and all(map(_isfinite, (self.alpha, self.mu, self.K)))):
+            raise ValueError(f"Ogden: alpha must be non-zero, mu and K > 0 (all finite); got alpha={alpha}, mu={mu}, K={K}")
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict | None = None):
+        """``material_properties`` of ``MFrontMaterial(..., "Ogden", material_properties=...)``: any of ``alpha``, ``mu``, ``K``;
+        what is absent keeps the behaviour file's default, as MFront parameters do."""
+        props = dict(props or {})
+        extra = set(props) - set(cls.MFRONT_DEFAULTS)
+        if extra:
+            raise ValueError(f"Ogden material properties: unknown {sorted(extra)} (the behaviour has alpha, mu, K)")
+        return cls(**{**cls.MFRONT_DEFAULTS, **{k: float(v) for k, v in props.items()}})
+
+    def params(self):
+        return [self.alpha, self.mu, self.K]
+
+    def flat_properties(self):
+        return {"alpha": self.alpha, "mu": self.mu, "K": self.K}
+
+
+def _isfinite(x):
+    return x == x and abs(x) != float("inf")

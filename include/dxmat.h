@@ -81,7 +81,18 @@ enum {
    * Tangent layouts "sym", "coef" and "pack4" as for J2.  Not served by a custom-hardening build.
    * params = [E, nu, sig0, alpha, n] with sig0 > 0, alpha > 0, n >= 1 */
   DXM_LAW_RAMBERG_OSGOOD = 5,
-  DXM_LAW_COUNT = 6
+  /* finite-strain Ogden hyperelasticity, gradient F (9), flux PK1 (9), full 81-entry dP/dF
+   * (demos/mfront/hyperelasticity/Ogden.mfront): stored energy
+   * W(F) = (mu / alpha) (J^(-alpha/3) sum_i c_i^(alpha/2) - 3) + K/2 (J - 1)^2, c_i the eigenvalues of C = F^T F, J = det F.
+   * One internal state variable, PK2Stress (6, MFront vector convention): the isochoric part of the second Piola-Kirchhoff
+   * stress, written by every update, never read, zero initially.  Points with det F <= 0 give NaN outputs and count in
+   * dxm_stats.n_nan; n_plastic, n_not_converged and max_local_iters are 0 (closed form, no local iteration).
+   * Only DXM_TANGENT_FULL; the displacement forms evaluate the gradient in a kernel of its own (no fused kernel for this
+   * law: with option fused_gradient on they are refused).  The host-buffer forms download the 81 entries as they are.
+   * Not served by a custom-hardening build.
+   * params = [alpha, mu, K] with alpha != 0, mu > 0, K > 0 */
+  DXM_LAW_OGDEN = 7,   /* id 6 is not assigned: the library answers it with "unknown law id", as ABI 6 always has */
+  DXM_LAW_COUNT = 8
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

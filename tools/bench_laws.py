@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -115,8 +115,8 @@ def main():
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
-    if a.cpu_sample and "ramberg_osgood" in a.laws:
-        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood law")
+    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws):
+        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood or Ogden law")
     import torch
 
     import dolfinx_materials_amd.materials as jm
@@ -128,11 +128,17 @@ def main():
     el = jm.LinearElasticIsotropic(E=E, nu=NU)
     res = []
     elastic_ms = None
+    fefp_ms = None
     for law in a.laws:
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
             beh, hist = jm.RambergOsgoodNonLinearElasticity(jm.LinearElasticIsotropic(E=RO_E, nu=RO_NU), RO_SIG0, RO_ALPHA, RO_N), [ro_eps, ro_eps]
             del ro_eps
+        elif law == "ogden":
+            # the behaviour file's parameters; F = I + 0.2 U(-1/2, 1/2), the family of the law's parity tests
+            rng = np.random.default_rng(2025)
+            eye = np.array([1.0, 1, 1, 0, 0, 0, 0, 0, 0])
+            beh, hist = jm.OgdenHyperelasticity(), [eye + 0.2 * (rng.random((n, 9)) - 0.5) for _ in range(2)]
         elif law == "elastic":
             beh, hist = jm.ElasticBehavior(el), j2_history(n)[1:3]
         elif law == "j2_linear":
@@ -142,7 +148,7 @@ def main():
         else:
             path = fefp_path(n)
             beh, hist = jm.FeFpJ2Plasticity(el, jm.VoceHardening(SIG0_F, SIGU_F, B_F)), [path[9], path[18]]
-        sym = a.sym and law != "fefp"
+        sym = a.sym and law not in ("fefp", "ogden")
         m = JAXMaterial(beh, tangent_layout="sym" if sym else "full")
         m.set_data_manager(n)
         ng, nf = m._info.n_grad, m._info.n_flux
@@ -184,6 +190,14 @@ def main():
         }
         if law == "elastic" and not sym:
             elastic_ms = ms
+        if law in ("fefp", "ogden"):   # same-process comparison of the two finite-strain kernels: two more timings each, for the spread
+            r["kernel"] = m.kernel_name
+            r["kernel_ms_repeats"] = [round(ms, 4), round(timed(), 4), round(timed(), 4)]
+            if law == "fefp":
+                fefp_ms = float(np.median(r["kernel_ms_repeats"]))
+            elif fefp_ms:
+                r["ratio_to_fefp"] = round(float(np.median(r["kernel_ms_repeats"])) / fefp_ms, 3)
+                r["byte_ratio_to_fefp"] = round(840 / 976, 3)
         if law == "ramberg_osgood":
             r["kernel"] = m.kernel_name
             if sweep:
