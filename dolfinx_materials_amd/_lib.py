@@ -17,6 +17,7 @@ DXM_MAX_STATE_FIELDS = 4
 LAW_ELASTIC_ISO, LAW_J2_LINEAR, LAW_J2_VOCE, LAW_FEFP_J2_VOCE, LAW_FEFP_J2_LINEAR = 0, 1, 2, 3, 4
 LAW_RAMBERG_OSGOOD = 5
 LAW_OGDEN = 7   # (6 is not assigned)
+LAW_HOSFORD_LINEAR = 10   # (8 and 9 are not assigned)
 S0, S1 = 0, 1
 
 

@@ -31,6 +31,7 @@
 #include "ramberg_osgood.hpp"
 #include "param_fields.hpp"
 #include "hyperelastic.hpp"
+#include "hosford.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -116,6 +117,13 @@ static const LawDesc kLaws[DXM_LAW_COUNT] = {
     // Ogden: F in (72 B), PK1 (72) + dP/dF (648) + the isochoric PK2 stress (48) out; the state is written, never read
     {9, 9, 3, 1, 1, {6, 0, 0, 0}, {"PK2Stress", nullptr, nullptr, nullptr}, {0, 0, 0, 0}, OGDEN_NSLOTS, 840,
      "ogden_kernel"},
+    // ids 8 and 9 are not assigned
+    {0, 0, 0, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 0, nullptr},
+    {0, 0, 0, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 0, nullptr},
+    // Hosford: strain in (48 B), stress (48) + tangent (288) out; reads p and the hidden plastic strain (56), writes them and the
+    // elastic strain (104).  Field 2 is hidden state: what the update is driven by (hosford.hpp)
+    {6, 6, 5, 2, 3, {6, 1, 6, 0}, {"ElasticStrain", "EquivalentPlasticStrain", "PlasticStrain", nullptr}, {HF_SLOT_EEL, HF_SLOT_P, HF_SLOT_EP, 0},
+     HF_NSLOTS, 544, "hosford_kernel"},
 };
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
@@ -278,6 +286,20 @@ static int build_params(dxm_material* m, const double* p, int np) {
   q.sig0 = 1.0;
   switch (m->law) {
     case DXM_LAW_ELASTIC_ISO: break;
+    case DXM_LAW_HOSFORD_LINEAR: {
+      // [E, nu, R0, H, a]: the exponent's derived constants are formed here once
+      const double R0 = p[2], H = p[3], a = p[4];
+      if (!(R0 > 0.0) || !std::isfinite(R0)) return fail(-1, "Hosford: R0 must be finite and > 0, got %g", R0);
+      if (!(H >= 0.0) || !std::isfinite(H)) return fail(-1, "Hosford: the hardening slope H must be finite and >= 0, got %g", H);
+      if (!(a >= 2.0) || !std::isfinite(a)) return fail(-1, "Hosford: the exponent a must be a finite number >= 2, got %g", a);
+      q.sig0 = R0;
+      q.h1 = H;
+      q.c[HF_A] = a;
+      q.c[HF_AM2] = a - 2.0;
+      q.c[HF_INVA] = 1.0 / a;
+      q.c[HF_AM1] = a - 1.0;
+      break;
+    }
     case DXM_LAW_J2_LINEAR:
     case DXM_LAW_FEFP_J2_LINEAR: q.sig0 = p[2]; q.h1 = p[3]; break;
     case DXM_LAW_J2_VOCE:
@@ -449,6 +471,10 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
     fail(-1, "Ogden hyperelasticity has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build");
     return nullptr;
   }
+  if (law == DXM_LAW_HOSFORD_LINEAR) {
+    fail(-1, "Hosford plasticity takes linear hardening only: it is served by the stock libdxmat, not by a custom-hardening build");
+    return nullptr;
+  }
 #endif
   dxm_material* m = new dxm_material();
   m->law = law;
@@ -496,6 +522,7 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
 #ifndef DXM_CUSTOM_HARDENING
       case DXM_LAW_RAMBERG_OSGOOD: fn = ramberg_osgood_kernel(); break;
       case DXM_LAW_OGDEN: fn = ogden_kernel_fn(); break;
+      case DXM_LAW_HOSFORD_LINEAR: fn = hosford_kernel_fn(); break;
 #endif
       default: fn = (const void*)fefp_kernel<1, 0>; break;
     }
@@ -521,6 +548,7 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
     // Ramberg-Osgood: RO_BLOCKS_PER_CU (DESIGN.md section "Ramberg-Osgood")
     if (law == DXM_LAW_RAMBERG_OSGOOD) m->blocks_per_cu = RO_BLOCKS_PER_CU;
     if (law == DXM_LAW_OGDEN) m->blocks_per_cu = OGDEN_BLOCKS_PER_CU;   // hyperelastic.hpp
+    if (law == DXM_LAW_HOSFORD_LINEAR) m->blocks_per_cu = HF_BLOCKS_PER_CU;   // hosford.hpp
   }
   // one record per workgroup and launch.  A single launch has at most num_cu * 256 workgroups (the largest grid
   // dxm_set_option("blocks_per_cu") allows); the chunked host path appends the records of up to DXM_MAX_CHUNKS
@@ -591,6 +619,9 @@ int dxm_set_tangent_layout(dxm_material* m, int layout) {
     return fail(-1, "unknown tangent layout %d", layout);
   if (layout != DXM_TANGENT_FULL && m->law == DXM_LAW_OGDEN)
     return fail(-1, "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record (sym / coef / pack4) exists for this law");
+  if ((layout == DXM_TANGENT_COEF || layout == DXM_TANGENT_PACK4) && m->law == DXM_LAW_HOSFORD_LINEAR)
+    return fail(-1, "the Hosford tangent is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no coefficients "
+                    "(coef / pack4); DXM_TANGENT_FULL and DXM_TANGENT_SYM are available");
   if (layout != DXM_TANGENT_FULL && kLaws[m->law].n_grad == 9)
     return fail(-1, "the FeFp tangent dP/dF is not symmetric: only DXM_TANGENT_FULL is available");
   if ((layout == DXM_TANGENT_COEF || layout == DXM_TANGENT_PACK4) && m->law == DXM_LAW_ELASTIC_ISO)
@@ -935,6 +966,14 @@ static int launch_range(dxm_material* m, int64_t off, int64_t cnt, const double*
                         "by the gradient kernel) or pass F as an array");
       if (tl != TL_FULL) return fail(-1, "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record exists for this law");
       ogden_launch(grid, st, m->prm, cnt, grad, m->state[1] + off, m->ld, flux, ct, m->d_stats + stats_off);
+      break;
+    case DXM_LAW_HOSFORD_LINEAR:   // hosford.hip: strain from the (N, 6) array, the full block or its upper triangle
+      if (fused)
+        return fail(-1, "the Hosford kernel has no fused displacement-gradient form: set option fused_gradient to 0 (the strain is then "
+                        "evaluated by the gradient kernel) or pass the strain as an array");
+      if (tl != TL_FULL && tl != TL_SYM)
+        return fail(-1, "the Hosford tangent is a general symmetric 6x6: no coefficient record (coef / pack4) exists for this law");
+      hosford_launch(tl, grid, st, m->prm, cnt, grad, m->state[0] + off, m->state[1] + off, m->ld, flux, ct, m->d_stats + stats_off);
       break;
 #endif
     case DXM_LAW_FEFP_J2_VOCE:
@@ -1803,6 +1842,7 @@ static int pf_check(const dxm_material* m, int idx) {
                 m->law == DXM_LAW_ELASTIC_ISO ? "the elastic tangent is a constant the host path never downloads"
                 : m->law == DXM_LAW_RAMBERG_OSGOOD ? "Ramberg-Osgood precomputes per-handle Newton constants on the host"
                 : m->law == DXM_LAW_OGDEN          ? "the Ogden kernel takes its exponents as per-handle constants"
+                : m->law == DXM_LAW_HOSFORD_LINEAR ? "the Hosford kernel takes its exponent's constants per handle"
                                                    : "the FeFp kernels have no registers to spare");
   if (idx < 0 || idx >= kLaws[m->law].n_params) return fail(-1, "law %d has no parameter %d", m->law, idx);
   return 0;

@@ -156,6 +156,21 @@ inline void expand_fefp_tangent(const double* __restrict__ s, double* __restrict
   }
 }
 
+// A general symmetric 6x6 from its 21 upper-triangle entries (row by row: the kernels' TL_SYM order), Hosford: entry (i, j) and
+// (j, i) of the kernel's full block are the same number, so mirroring is the block bit for bit.  rows / fdst / sg as in
+// expand_pack4_tangent.
+inline void expand_sym_tangent(const double* __restrict__ s, double* __restrict__ dbase, int64_t n, const int64_t* __restrict__ rows = nullptr,
+                               double* __restrict__ fdst = nullptr, const double* __restrict__ sg = nullptr) {
+  for (int64_t p = 0; p < n; ++p, s += 21) {
+    double* d = dbase + (rows ? rows[p] : p) * 36;
+    int t = 0;
+    for (int i = 0; i < 6; ++i)
+      for (int j = i; j < 6; ++j, ++t) d[i * 6 + j] = d[j * 6 + i] = s[t];
+    if (rows)
+      for (int k = 0; k < 6; ++k) fdst[rows[p] * 6 + k] = sg[p * 6 + k];
+  }
+}
+
 // elastic law: the same constant block for every point (python_materials/elasticity.py:15-19)
 inline void fill_const_tangent(const double* __restrict__ s /* lambda, mu */, double* __restrict__ dbase, int64_t n, const int64_t* __restrict__ rows = nullptr,
                                double* __restrict__ fdst = nullptr, const double* __restrict__ sg = nullptr) {
@@ -175,7 +190,7 @@ inline void fill_const_tangent(const double* __restrict__ s /* lambda, mu */, do
 // ------------------------------------------------------------------------------------------
 struct HostPool {
   // stride 9: J2 coefficients -> 6x6, 4: (c1, c2, c3, w) + the stress rows `aux` -> 6x6, -4: the same source -> the 21
-  // upper-triangle entries, 54: FeFp building blocks -> 9x9, 0: constant block, -1: plain copy of n BYTES, -8: rows of `tag`
+  // upper-triangle entries, 21: the upper triangle of a general symmetric 6x6 -> 6x6, 54: FeFp building blocks -> 9x9, 0: constant block, -1: plain copy of n BYTES, -8: rows of `tag`
   // doubles from a contiguous block to rows `rows` of `dst` (a state field into the Function of a map over a subset of the cells)
   struct Job { const double* src; double* dst; int64_t n; int stride; int tag; const double* aux; const int64_t* rows; double* dst2; };
   std::vector<std::thread> threads;
@@ -208,6 +223,7 @@ struct HostPool {
       if (j.stride == 9) expand_coef_tangent(j.src, j.dst, j.n);
       else if (j.stride == 4) expand_pack4_tangent(j.aux, j.src, j.dst, j.n, j.rows, j.dst2);
       else if (j.stride == -4) expand_pack4_tangent_sym(j.aux, j.src, j.dst, j.n);
+      else if (j.stride == 21) expand_sym_tangent(j.src, j.dst, j.n, j.rows, j.dst2, j.aux);
       else if (j.stride == FEFP_RECORD) expand_fefp_tangent(j.src, j.dst, j.n, j.rows, j.dst2, j.aux);
       else if (j.stride == -1) memcpy(j.dst, j.src, (size_t)j.n);
       else if (j.stride == -8) {
@@ -384,6 +400,9 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   // Ogden: the kernel writes the 81 entries only (no record to rebuild from): they are downloaded as they are, and the rows forms
   // move them like a handle's own packed layout
   const bool plain81 = r.law == DXM_LAW_OGDEN;
+  // Hosford: a general symmetric 6x6 with no coefficient form.  A full-layout handle's packed transfer is the kernel's 21
+  // upper-triangle entries (168 instead of 288 B/point), mirrored into the block by the workers; a "sym" handle downloads its 21
+  const bool gsym = r.law == DXM_LAW_HOSFORD_LINEAR;
   const bool fefp = r.n_grad == 9 && !plain81, elastic = r.law == DXM_LAW_ELASTIC_ISO;
   int total = 0;
   for (int f = 0; f < r.n_isv_fields; ++f) total += r.isv_dim[f];
@@ -397,7 +416,7 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   // a J2 handle with the "sym" layout: (c1, c2, c3, w) cross PCIe like for the full layout (32 instead of 168 B/point) and the
   // workers rebuild the 21 upper-triangle entries from them and the stress (expand_pack4_tangent_sym); needs the stress in
   // page-locked memory like the pack4 form below, else the kernel's own 21 entries are downloaded
-  const bool sym_packed = !r.rows && r.packed_transfer >= 2 && r.layout == DXM_TANGENT_SYM && !elastic && !fefp && r.ct && r.flux &&
+  const bool sym_packed = !r.rows && r.packed_transfer >= 2 && r.layout == DXM_TANGENT_SYM && !elastic && !fefp && !gsym && r.ct && r.flux &&
                           r.n >= r.packed_min_points && flux_locked;
   p.packed = r.rows || sym_packed || (r.packed_transfer && r.layout == DXM_TANGENT_FULL && r.ct && r.n >= r.packed_min_points && !plain81);
   // the rows forms of a handle whose OWN layout is packed (sym / coef / pack4): the kernel writes that layout, it lands in the
@@ -406,9 +425,9 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   const bool constant = p.packed && !rows_plain && elastic;   // the elastic block is a constant and is only filled in
   // small strain: (c1, c2, c3, w) only -- the direction n is rebuilt from the stress, which the caller receives in
   // page-locked memory as part of the same chunk -- else the nine coefficients
-  const bool pack4 = p.packed && !constant && !fefp && !rows_plain && (r.rows || (r.packed_transfer >= 2 && r.flux && flux_locked));
-  p.tl = rows_plain ? r.layout : (p.packed && !constant ? (pack4 ? DXM_TANGENT_PACK4 : DXM_TANGENT_COEF) : r.layout);
-  p.np = rows_plain ? r.tangent_size : (fefp ? FEFP_RECORD : (pack4 ? 4 : 9));
+  const bool pack4 = p.packed && !constant && !fefp && !gsym && !rows_plain && (r.rows || (r.packed_transfer >= 2 && r.flux && flux_locked));
+  p.tl = rows_plain ? r.layout : (p.packed && !constant ? (gsym ? DXM_TANGENT_SYM : (pack4 ? DXM_TANGENT_PACK4 : DXM_TANGENT_COEF)) : r.layout);
+  p.np = rows_plain ? r.tangent_size : (fefp ? FEFP_RECORD : (gsym ? 21 : (pack4 ? 4 : 9)));
   p.land = fefp ? FEFP_RECORD : std::max(p.np, 9);   // (9 covers both packed forms of the J2 laws; a "sym" handle in the rows forms lands 21)
   p.nfull = sym_packed ? 21 : r.n_flux * r.n_grad;
   p.job = constant ? 0 : (sym_packed ? -4 : p.np);

@@ -110,6 +110,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_OGDEN:
             raise ValueError("the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for this law")
+        if tangent_layout in ("coef", "pack4") and getattr(behavior, "law", None) == _lib.LAW_HOSFORD_LINEAR:
+            raise ValueError("the Hosford tangent is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no "
+                             f"coefficients (tangent_layout={tangent_layout!r}); use 'full' or 'sym'")
         if not isinstance(jit, (bool, type(None))):
             raise TypeError("the second argument of JAXMaterial / HIPMaterial is `jit` (jaxmat.py:144); pass the GPU index as device=")
         self.jit = bool(jit)
@@ -182,6 +185,12 @@ class HIPMaterial:
         """The FeFp laws: their kernel state (isochoric Cp^-1) is rebuilt from (F, be_bar) when either is set.  (Ogden shares the
         F / PK1 boundary and has no such state.)"""
         return "be_bar" in self.internal_state_variables
+
+    @property
+    def _has_hidden_plastic_strain(self):
+        """Hosford: the kernel is handed the total strain, so its state is the plastic strain (hidden field 2), rebuilt from
+        (Strain_n, ElasticStrain_n) when either is set."""
+        return self.behavior.law == _lib.LAW_HOSFORD_LINEAR
 
     @property
     def variables(self):
@@ -262,7 +271,7 @@ class HIPMaterial:
         if self.behavior.law not in (_lib.LAW_J2_LINEAR, _lib.LAW_J2_VOCE) or getattr(self.behavior, "custom_hardening", None) is not None:
             raise NotImplementedError(
                 f"material property {key!r} varies from point to point: per-point property fields exist for the small-strain J2 laws "
-                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp, Ogden or custom hardening laws)")
+                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp, Ogden, Hosford or custom hardening laws)")
         return list(self.behavior.flat_properties()).index(key)
 
     def _upload_field(self, key, arr, restore=None):
@@ -508,6 +517,11 @@ class HIPMaterial:
             self._retire_final_views(materializing=True)
             self._set_state(1, _as_c(be))
             self._set_state(2, _as_c(cpi))
+        if self._has_hidden_plastic_strain and ("ElasticStrain" in state or self._gname in state):
+            # eps_p,n = eps_n - eps_el,n: what the next update forms its trial elastic strain from
+            eel = _as_c(state["ElasticStrain"], (self._n, 6)) if "ElasticStrain" in state else self._isv_dict(S0)["ElasticStrain"]
+            self._retire_final_views(materializing=True)
+            self._set_state(2, _as_c(np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 6) - eel))
 
     def _set_state(self, field, a):
         for h, lo, hi, ptrs in self._blocks(a):

@@ -304,5 +304,52 @@ class OgdenHyperelasticity(FiniteStrainBehavior):
         return {"alpha": self.alpha, "mu": self.mu, "K": self.K}
 
 
+class HosfordIsotropicHardening(SmallStrainBehavior):
+    """Small-strain Hosford plasticity with linear isotropic hardening (the reference's ``IsotropicPlasticHosfordFlowLinear``
+    MFront behaviour, the matrix material of ``demos/multimaterials/multimaterials.py``): Hooke's law, associated flow on
+    ``seq = (1/2 (|s1-s2|^a + |s1-s3|^a + |s2-s3|^a))^(1/a)`` of the principal stresses, ``R(p) = R0 + H p``; ``R0 > 0``,
+    ``H >= 0``, ``a >= 2`` (the behaviour file fixes ``a = 10``; ``a = 2`` and ``a = 4`` are von Mises).  Internal state variables
+    ``ElasticStrain`` (6) and ``EquivalentPlasticStrain`` (1), MFront's names.
+
+    ``JAXMaterial(HosfordIsotropicHardening(...))`` stands where the demo uses ``MFrontMaterial(lib, "IsotropicPlasticHosfordFlowLinear",
+    material_properties=...)``: gradient ``Strain``, flux ``Stress``; :meth:`from_mfront_properties` takes that dictionary.  Tangent
+    layouts ``"full"`` and ``"sym"`` (a general symmetric 6x6: no ``"coef"`` / ``"pack4"``); uniform properties only; the displacement
+    forms need option ``fused_gradient`` off."""
+
+    law = _lib.LAW_HOSFORD_LINEAR
+    gradient_name = "Strain"
+    flux_name = "Stress"
+    MFRONT_NAMES = ("young_modulus", "poisson_ratio", "R0", "hardening_slope")
+
+    def __init__(self, elasticity: LinearElasticIsotropic, yield_stress, a: float = 10.0):
+        if not isinstance(yield_stress, LinearHardening):
+            raise TypeError("Hosford plasticity is served with linear hardening only: yield_stress must be a materials.LinearHardening(R0, H), "
+                            f"got {type(yield_stress).__name__}")
+        self.elasticity = elasticity
+        self.yield_stress = yield_stress
+        self.a = float(a)
+        R0, H = float(yield_stress.sig0), float(yield_stress.H)
+        if not (R0 > 0.0 and H >= 0.0 and self.a >= 2.0 and all(map(_isfinite, (R0, H, self.a)))):
+            raise ValueError(f"Hosford: R0 must be > 0, H >= 0 and the exponent a >= 2 (all finite); got R0={R0}, H={H}, a={a}")
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict):
+        """The ``material_properties`` of the multi-material demo: ``young_modulus``, ``poisson_ratio``, ``R0``, ``hardening_slope``,
+        and optionally the exponent ``a`` (10, the behaviour file's value, when absent)."""
+        need, known = set(cls.MFRONT_NAMES), set(cls.MFRONT_NAMES) | {"a"}
+        missing, extra = need - set(props), set(props) - known
+        if missing or extra:
+            raise ValueError(f"Hosford material properties: missing {sorted(missing)}, unknown {sorted(extra)}")
+        el = LinearElasticIsotropic(E=float(props["young_modulus"]), nu=float(props["poisson_ratio"]))
+        return cls(el, LinearHardening(float(props["R0"]), float(props["hardening_slope"])), a=float(props.get("a", 10.0)))
+
+    def params(self):
+        return [self.elasticity.E, self.elasticity.nu, self.yield_stress.sig0, self.yield_stress.H, self.a]
+
+    def flat_properties(self):
+        return {"elasticity.E": self.elasticity.E, "elasticity.nu": self.elasticity.nu, "yield_stress.sig0": self.yield_stress.sig0,
+                "yield_stress.H": self.yield_stress.H, "a": self.a}
+
+
 def _isfinite(x):
     return x == x and abs(x) != float("inf")

@@ -92,7 +92,20 @@ enum {
    * Not served by a custom-hardening build.
    * params = [alpha, mu, K] with alpha != 0, mu > 0, K > 0 */
   DXM_LAW_OGDEN = 7,   /* id 6 is not assigned: the library answers it with "unknown law id", as ABI 6 always has */
-  DXM_LAW_COUNT = 8
+  /* small-strain Hosford plasticity with linear isotropic hardening R(p) = R0 + H p (the reference's
+   * IsotropicPlasticHosfordFlowLinear behaviour): equivalent stress (1/2 (|s1-s2|^a + |s1-s3|^a + |s2-s3|^a))^(1/a) of the
+   * principal stresses, associated flow, implicit update with a local Newton per plastic point (dxm_set_newton: stops when every
+   * residual, as a stress, is <= max(tol, rtol seq_trial)); a = 2 and a = 4 are von Mises.  Plain Newton from the trial state:
+   * converges for seq_trial / R <= 3 with a <= 10 and <= 1.5 with a = 20; points beyond that may stop at maxit and
+   * are counted in dxm_stats.n_not_converged (and n_nan if their outputs are not finite), never silently.
+   * Internal state variables ElasticStrain (6; written by every update) and EquivalentPlasticStrain (1); the strain handed in is
+   * the TOTAL strain, so the update is driven by a hidden state field 2, the plastic strain (6): dxm_set_state / dxm_get_state
+   * address it, a state set through field 0 alone does not change the next update.
+   * The tangent is a general symmetric 6x6: DXM_TANGENT_FULL and DXM_TANGENT_SYM; _COEF and _PACK4 are refused.  No per-point
+   * parameter fields, no fused displacement gradient (option fused_gradient 0), not served by a custom-hardening build.
+   * params = [E, nu, R0, H, a] with R0 > 0, H >= 0, a >= 2 */
+  DXM_LAW_HOSFORD_LINEAR = 10,   /* ids 8 and 9 are not assigned */
+  DXM_LAW_COUNT = 11
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */
@@ -169,6 +182,7 @@ int dxm_algorithmic_bytes(const dxm_material* m);
 /* Tangent layout integrate writes, doubles per point:
  *   DXM_TANGENT_FULL   n_flux*n_grad (36 / 81), row-major: what `jacobian_flatten` holds (quadrature_map.py:83-105);
  *   DXM_TANGENT_SYM    21 upper-triangle entries (i <= j), small-strain laws (symmetric tangent);
+ *                      Hosford: the host-buffer forms of a DXM_TANGENT_FULL handle move these 21 and mirror them on the host;
  *   DXM_TANGENT_COEF   9 = (c1, c2, c3, n[0..5]) of Ct = c1 1x1 + c2 I + c3 n x n, J2 laws and Ramberg-Osgood
  *                      (tests/mfront/IsotropicLinearHardeningPlasticity.mfront:66-69 with M expanded);
  *   DXM_TANGENT_PACK4  4 = (c1, c2, c3, w), J2 laws and Ramberg-Osgood: the kernels form n = dev(stress) w, so the stress of the same update

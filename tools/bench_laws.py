@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -115,8 +115,8 @@ def main():
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
-    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws):
-        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood or Ogden law")
+    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws):
+        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden or Hosford law")
     import torch
 
     import dolfinx_materials_amd.materials as jm
@@ -129,6 +129,7 @@ def main():
     res = []
     elastic_ms = None
     fefp_ms = None
+    j2_linear_ms = None
     for law in a.laws:
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
@@ -139,6 +140,9 @@ def main():
             rng = np.random.default_rng(2025)
             eye = np.array([1.0, 1, 1, 0, 0, 0, 0, 0, 0])
             beh, hist = jm.OgdenHyperelasticity(), [eye + 0.2 * (rng.random((n, 9)) - 0.5) for _ in range(2)]
+        elif law == "hosford":
+            # the J2-linear parameters with the behaviour file's exponent a = 10, uniform (zero) state, the headline increments
+            beh, hist = jm.HosfordIsotropicHardening(el, jm.LinearHardening(SIG0_LIN, H_LIN), a=10.0), j2_history(n)[1:3]
         elif law == "elastic":
             beh, hist = jm.ElasticBehavior(el), j2_history(n)[1:3]
         elif law == "j2_linear":
@@ -190,6 +194,14 @@ def main():
         }
         if law == "elastic" and not sym:
             elastic_ms = ms
+        if law in ("j2_linear", "hosford") and not sym:   # same-process comparison with the J2-linear kernel: two more timings each
+            r["kernel"] = m.kernel_name
+            r["kernel_ms_repeats"] = [round(ms, 4), round(timed(), 4), round(timed(), 4)]
+            if law == "j2_linear":
+                j2_linear_ms = float(np.median(r["kernel_ms_repeats"]))
+            elif j2_linear_ms:
+                r["ratio_to_j2_linear"] = round(float(np.median(r["kernel_ms_repeats"])) / j2_linear_ms, 3)
+                r["byte_ratio_to_j2_linear"] = round(544 / 496, 3)
         if law in ("fefp", "ogden"):   # same-process comparison of the two finite-strain kernels: two more timings each, for the spread
             r["kernel"] = m.kernel_name
             r["kernel_ms_repeats"] = [round(ms, 4), round(timed(), 4), round(timed(), 4)]
