@@ -83,50 +83,360 @@ struct DeviceGuard {
   if (!_guard.ok) return fail(-2, "hipSetDevice(%d) failed", (m)->device)
 
 // ------------------------------------------------------------------------------------------
-// law descriptors
+// law descriptors: one row of kLaws per law carries everything that law decides; the host code below reads the row of the
+// handle's law and tests no law id ("Adding a law")
 // ------------------------------------------------------------------------------------------
+#ifdef DXM_CUSTOM_HARDENING
+// A JIT build with a user-supplied hardening law is dxmat.hip alone: the other translation units' entry points do not exist
+constexpr bool kCustomBuild = true;
+#define DXM_STOCK_ONLY(entry) nullptr
+#else
+constexpr bool kCustomBuild = false;
+#define DXM_STOCK_ONLY(entry) entry
+#endif
+
+struct dxm_material;
+
+// One launch over the point range [off, off + cnt) (off a multiple of 256): the chunk-pipelined host
+// path issues several of these on alternating streams; everything else launches the whole batch.
+// The block records of the launch go to m->d_stats[stats_off ...).
+struct LaunchArgs {
+  dxm_material* m;
+  int grid;
+  hipStream_t st;
+  int64_t off, cnt;
+  const double* grad;
+  double* flux;
+  double* ct;
+  int stats_off;
+  const MeshSource* fused;   // gradient evaluated inside the kernel from this mesh; null: read from `grad`
+  int tl;                    // tangent layout of THIS launch (the host path may ask for the coefficient form although the
+                             // handle's layout is the full block: it rebuilds the block on the host)
+};
+
+constexpr unsigned L_FULL = 1u << TL_FULL, L_SYM = 1u << TL_SYM, L_COEF = 1u << TL_COEF, L_PACK4 = 1u << TL_PACK4;
+constexpr unsigned L_ALL = L_FULL | L_SYM | L_COEF | L_PACK4;
+
 struct LawDesc {
-  int n_grad, n_flux, n_params;
+  int id;                                 // DXM_LAW_*: the row's own index in kLaws
+  int n_grad, n_flux;
+  int n_params, n_params_custom;          // parameters in the stock build / in a custom-hardening build
   int n_isv_fields;                       // user-visible
   int n_fields;                           // incl. hidden state fields (addressable by set/get_state)
   int isv_dim[DXM_MAX_STATE_FIELDS];
   const char* isv_name[DXM_MAX_STATE_FIELDS];
   int isv_slot[DXM_MAX_STATE_FIELDS];     // first SoA slot of the field
   int n_slots;                            // SoA slots incl. hidden ones
+  unsigned unit_fields;                   // bit f: field f is a symmetric tensor that starts as the identity (else: zeros)
   int alg_bytes;
-  const char* kernel;
+  const char* kernel;                     // null: the id is not assigned (law_known)
+  const char* field_kernel;               // the kernel while per-point parameter fields are bound; null: the law serves none ...
+  const char* no_fields;                  // ... for this reason
+  int (*build)(const double* p, LawParams& q);   // validates the n_params parameters and forms the kernel's record from them
+  const char* stock_only;                 // what a custom-hardening build answers dxm_create with; null: it serves the law too
+  const void* (*residency_kernel)();      // the kernel whose registers and LDS give the residency estimate of dxm_create
+  int blocks_per_cu;                      // grid size in workgroups per CU; 0: the residency estimate
+  unsigned set_layouts;                   // tangent layouts a handle may be set to (L_* bits) ...
+  const char* set_refusal;                // ... and what dxm_set_tangent_layout says to the others
+  unsigned launch_layouts;                // layouts a launch may be asked for: the host path also asks for records it expands itself
+  const char* launch_refusal;
+  const char* no_fused;                   // null: the kernel can evaluate the displacement gradient itself; else the refusal
+  void (*launch)(const LaunchArgs& a);    // null: not launchable in this build
 };
 
-static const LawDesc kLaws[DXM_LAW_COUNT] = {
-    {6, 6, 2, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 384,
-     "small_strain_kernel<0"},
-    {6, 6, 4, 2, 2, {1, 6, 0, 0}, {"p", "epsp", nullptr, nullptr}, {0, 1, 0, 0}, SS_NSLOTS, 496,
-     "small_strain_kernel<1"},
-    {6, 6, 5, 2, 2, {1, 6, 0, 0}, {"p", "epsp", nullptr, nullptr}, {0, 1, 0, 0}, SS_NSLOTS, 496,
-     "small_strain_kernel<2"},
-    // field 2 is hidden state: the isochoric inverse plastic right Cauchy-Green tensor
-    {9, 9, 5, 2, 3, {1, 6, 6, 0}, {"p", "be_bar", "cp_bar_inv", nullptr}, {FEFP_SLOT_P, FEFP_SLOT_BE, FEFP_SLOT_CPI, 0}, FEFP_NSLOTS, 976,
-     "fefp_kernel<1"},
-    {9, 9, 4, 2, 3, {1, 6, 6, 0}, {"p", "be_bar", "cp_bar_inv", nullptr}, {FEFP_SLOT_P, FEFP_SLOT_BE, FEFP_SLOT_CPI, 0}, FEFP_NSLOTS, 976,
-     "fefp_kernel<0"},
-    // stateless: the elastic law's stream (48 B in, 48 + 288 B out), with per-point tangent coefficients like J2
-    {6, 6, 5, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 384,
-     "small_strain_kernel<3"},
-    // id 6 is not assigned (law_known)
-    {0, 0, 0, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 0, nullptr},
-    // Ogden: F in (72 B), PK1 (72) + dP/dF (648) + the isochoric PK2 stress (48) out; the state is written, never read
-    {9, 9, 3, 1, 1, {6, 0, 0, 0}, {"PK2Stress", nullptr, nullptr, nullptr}, {0, 0, 0, 0}, OGDEN_NSLOTS, 840,
-     "ogden_kernel"},
-    // ids 8 and 9 are not assigned
-    {0, 0, 0, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 0, nullptr},
-    {0, 0, 0, 0, 0, {0, 0, 0, 0}, {nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, 0, 0, nullptr},
-    // Hosford: strain in (48 B), stress (48) + tangent (288) out; reads p and the hidden plastic strain (56), writes them and the
-    // elastic strain (104).  Field 2 is hidden state: what the update is driven by (hosford.hpp)
-    {6, 6, 5, 2, 3, {6, 1, 6, 0}, {"ElasticStrain", "EquivalentPlasticStrain", "PlasticStrain", nullptr}, {HF_SLOT_EEL, HF_SLOT_P, HF_SLOT_EP, 0},
-     HF_NSLOTS, 544, "hosford_kernel"},
+// ---- parameters: [E, nu, ...] for all laws but Ogden ----
+static int elastic_constants(const double* p, LawParams& q) {
+  const double E = p[0], nu = p[1];
+  if (!(E > 0.0) || !(nu > -1.0 && nu < 0.5)) return fail(-1, "invalid elastic constants E=%g nu=%g", E, nu);
+  q.lambda = E * nu / (1 + nu) / (1 - 2 * nu);  // python_materials/elasticity.py:12-13
+  q.mu = E / 2 / (1 + nu);
+  q.kappa = q.lambda + 2.0 * q.mu / 3.0;
+  q.sig0 = 1.0;
+  return 0;
+}
+
+// residual tolerance of the local Newton: relative to the initial yield stress, floored so that a law with R(0) = 0 keeps a
+// reachable tolerance
+static void yield_tolerance(LawParams& q) { q.tol = q.rtol * fmax(fabs(q.sig0), 2e-8 * q.mu); }
+
+static int build_elastic(const double* p, LawParams& q) {
+  if (int rc = elastic_constants(p, q)) return rc;
+  yield_tolerance(q);
+  return 0;
+}
+
+// [E, nu, sig0, H]
+static int build_linear_hardening(const double* p, LawParams& q) {
+  if (int rc = elastic_constants(p, q)) return rc;
+  q.sig0 = p[2]; q.h1 = p[3];
+  yield_tolerance(q);
+  return 0;
+}
+
+// [E, nu, sig0, sigu, b]; a custom-hardening build: [E, nu, sig0, c0..c5]
+static int build_voce_hardening(const double* p, LawParams& q) {
+  if (int rc = elastic_constants(p, q)) return rc;
+  q.sig0 = p[2];
+  if (kCustomBuild) { for (int k = 0; k < 6; ++k) q.c[k] = p[3 + k]; }
+  else { q.h1 = p[3]; q.h2 = p[4]; }
+  yield_tolerance(q);
+  return 0;
+}
+
+// [E, nu, sig0, alpha, n]; the local Newton's monotone convergence needs a convex f, i.e. n >= 1
+static int build_ramberg_osgood(const double* p, LawParams& q) {
+  if (int rc = elastic_constants(p, q)) return rc;
+  const double E = p[0], nu = p[1], sig0 = p[2], alpha = p[3], n = p[4];
+  if (!(sig0 > 0.0)) return fail(-1, "Ramberg-Osgood: sig0 must be > 0, got %g", sig0);
+  if (!(alpha > 0.0)) return fail(-1, "Ramberg-Osgood: alpha must be > 0, got %g", alpha);
+  if (!(n >= 1.0) || !std::isfinite(n)) return fail(-1, "Ramberg-Osgood: n must be a finite number >= 1, got %g", n);
+  q.sig0 = sig0;
+  q.kappa = E / (3.0 * (1.0 - 2.0 * nu));   // the .mfront file's K
+  q.c[RO_I3MU] = 1.0 / (3.0 * q.mu);
+  q.c[RO_BETA] = alpha * sig0 / E;
+  q.c[RO_ISIG0] = 1.0 / sig0;
+  q.c[RO_N] = n;
+  q.c[RO_INVN] = 1.0 / n;
+  q.c[RO_ESIG] = E * RO_EPS;
+  q.h1 = 3.0 * q.mu;
+  q.h2 = n * q.c[RO_BETA];
+  q.tol = q.c[RO_I3MU] * RO_EPS;   // no residual tolerance: the floor of f' (small_strain.hpp)
+  return 0;
+}
+
+// [alpha, mu, K] (Ogden.mfront); the exponents the kernel needs are formed here once
+static int build_ogden(const double* p, LawParams& q) {
+  const double alpha = p[0], mu = p[1], K = p[2];
+  if (!(alpha != 0.0) || !std::isfinite(alpha)) return fail(-1, "Ogden: alpha must be finite and non-zero, got %g", alpha);
+  if (!(mu > 0.0) || !std::isfinite(mu)) return fail(-1, "Ogden: mu must be finite and > 0, got %g", mu);
+  if (!(K > 0.0) || !std::isfinite(K)) return fail(-1, "Ogden: K must be finite and > 0, got %g", K);
+  const double a = 0.5 * alpha;
+  q.mu = mu;
+  q.kappa = K;
+  q.c[OG_A] = a;
+  q.c[OG_AM2] = a - 2.0;
+  q.c[OG_MA3] = -a / 3.0;
+  q.c[OG_M] = a - 1.0;
+  return 0;
+}
+
+// [E, nu, R0, H, a]: the exponent's derived constants are formed here once
+static int build_hosford(const double* p, LawParams& q) {
+  if (int rc = elastic_constants(p, q)) return rc;
+  const double R0 = p[2], H = p[3], a = p[4];
+  if (!(R0 > 0.0) || !std::isfinite(R0)) return fail(-1, "Hosford: R0 must be finite and > 0, got %g", R0);
+  if (!(H >= 0.0) || !std::isfinite(H)) return fail(-1, "Hosford: the hardening slope H must be finite and >= 0, got %g", H);
+  if (!(a >= 2.0) || !std::isfinite(a)) return fail(-1, "Hosford: the exponent a must be a finite number >= 2, got %g", a);
+  q.sig0 = R0;
+  q.h1 = H;
+  q.c[HF_A] = a;
+  q.c[HF_AM2] = a - 2.0;
+  q.c[HF_INVA] = 1.0 / a;
+  q.c[HF_AM1] = a - 1.0;
+  yield_tolerance(q);
+  return 0;
+}
+
+// ---- launchers (defined in the launch section, where the handle is complete) ----
+template <int LAW> static void launch_small_strain(const LaunchArgs& a);
+static void launch_fefp_voce(const LaunchArgs& a);
+static void launch_fefp_linear(const LaunchArgs& a);
+static void launch_ramberg_osgood(const LaunchArgs& a);
+static void launch_ogden(const LaunchArgs& a);
+static void launch_hosford(const LaunchArgs& a);
+
+// The device assembly of this file lists its kernels in the order in which host code first names them, and
+// tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
+// not the order of the rows below (the Voce FeFp law has the lower id): naming them here, ahead of the table, keeps the order.
+[[maybe_unused]] static const void* const kKernelOrder[5] = {
+    (const void*)small_strain_kernel<LAW_ELASTIC, TL_FULL>, (const void*)small_strain_kernel<LAW_J2_LINEAR, TL_FULL>,
+    (const void*)small_strain_kernel<LAW_J2_VOCE, TL_FULL>, (const void*)fefp_kernel<0, 0>, (const void*)fefp_kernel<1, 0>};
+
+// ---- the rows ----
+// Grid size, in workgroups per CU (blocks_per_cu).  FeFp: the workgroups that are resident at once (persistent
+// grid).  Small strain: 32 = 8 x the resident 4: a grid of exactly-resident workgroups starts all
+// waves together and keeps them in lockstep (everybody loads, then everybody stores); workgroups
+// that are dispatched as others retire spread those phases, 3-6 % faster at 1e7 points in the fast
+// placement mode and 10 % in the slow one (tools/grid_sweep.py, profiles/archive/r01_grid_sweep.jsonl).
+// The laws with a local Newton iteration (Voce or traced hardening, FeFp) do a point-dependent amount of work per tile: a
+// grid of one workgroup per 256 points (up to 256 per CU, the cap; a grid-stride loop beyond) lets the dispatcher balance
+// it -- Voce +3 %, FeFp +2.5 % over the persistent grids above at 1e7 points (profiles/archive/r03_grid_size_by_law.txt); the
+// linear-hardening kernel, whose tiles all cost the same, loses 2.5 % with it and keeps 32.
+
+constexpr void state_field(LawDesc& d, int f, const char* name, int dim, int slot) {
+  d.isv_name[f] = name; d.isv_dim[f] = dim; d.isv_slot[f] = slot;
+}
+
+// what the small-strain laws of small_strain.hpp share; `coef`: the tangent is c1 1x1 + c2 I + c3 n x n with per-point coefficients
+constexpr LawDesc small_strain_law(int id, int n_params, int alg_bytes, const char* kernel, bool coef, void (*launch)(const LaunchArgs&)) {
+  LawDesc d{};
+  d.id = id;
+  d.n_grad = d.n_flux = 6;
+  d.n_params = d.n_params_custom = n_params;
+  d.alg_bytes = alg_bytes;
+  d.kernel = kernel;
+  d.set_layouts = d.launch_layouts = coef ? L_ALL : L_FULL | L_SYM;
+  d.launch = launch;
+  return d;
+}
+
+constexpr void j2_state(LawDesc& d) {
+  d.n_isv_fields = d.n_fields = 2;
+  state_field(d, 0, "p", 1, 0);
+  state_field(d, 1, "epsp", 6, 1);
+  d.n_slots = SS_NSLOTS;
+}
+
+constexpr LawDesc law_elastic() {
+  LawDesc d = small_strain_law(DXM_LAW_ELASTIC_ISO, 2, 384, "small_strain_kernel<0", false, launch_small_strain<LAW_ELASTIC>);
+  d.build = build_elastic;
+  d.residency_kernel = []() -> const void* { return (const void*)small_strain_kernel<LAW_ELASTIC, TL_FULL>; };
+  d.blocks_per_cu = 32;
+  d.set_refusal = d.launch_refusal = "the elastic tangent is the constant lambda 1x1 + 2 mu I: there are no per-point coefficients";
+  d.no_fields = "the elastic tangent is a constant the host path never downloads";
+  return d;
+}
+
+constexpr LawDesc law_j2_linear() {
+  LawDesc d = small_strain_law(DXM_LAW_J2_LINEAR, 4, 496, "small_strain_kernel<1", true, launch_small_strain<LAW_J2_LINEAR>);
+  j2_state(d);
+  d.build = build_linear_hardening;
+  d.residency_kernel = []() -> const void* { return (const void*)small_strain_kernel<LAW_J2_LINEAR, TL_FULL>; };
+  d.blocks_per_cu = 32;
+  d.field_kernel = "small_strain_field_kernel<1";
+  return d;
+}
+
+constexpr LawDesc law_j2_voce() {
+  LawDesc d = small_strain_law(DXM_LAW_J2_VOCE, 5, 496, "small_strain_kernel<2", true, launch_small_strain<LAW_J2_VOCE>);
+  j2_state(d);
+  d.n_params_custom = 9;
+  d.build = build_voce_hardening;
+  d.residency_kernel = []() -> const void* { return (const void*)small_strain_kernel<LAW_J2_VOCE, TL_FULL>; };
+  d.blocks_per_cu = 256;
+  d.field_kernel = "small_strain_field_kernel<2";
+  return d;
+}
+
+// stateless: the elastic law's stream (48 B in, 48 + 288 B out), with per-point tangent coefficients like J2
+constexpr LawDesc law_ramberg_osgood() {
+  // ramberg_osgood.hip holds the kernels
+  LawDesc d = small_strain_law(DXM_LAW_RAMBERG_OSGOOD, 5, 384, "small_strain_kernel<3", true, DXM_STOCK_ONLY(launch_ramberg_osgood));
+  d.build = build_ramberg_osgood;
+  d.stock_only = "Ramberg-Osgood has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(ramberg_osgood_kernel);
+  d.blocks_per_cu = RO_BLOCKS_PER_CU;   // DESIGN.md section "Ramberg-Osgood"
+  d.no_fields = "Ramberg-Osgood precomputes per-handle Newton constants on the host";
+  return d;
+}
+
+// F -> PK1.  A launch may also ask for TL_COEF: the 54 building blocks of the tangent per point instead of its 81 entries, which
+// the host-buffer form expands; no handle can be set to it
+constexpr LawDesc law_fefp(int id, bool voce) {
+  LawDesc d{};
+  d.id = id;
+  d.n_grad = d.n_flux = 9;
+  d.n_params = voce ? 5 : 4;
+  d.n_params_custom = voce ? 9 : 4;
+  d.n_isv_fields = 2;
+  d.n_fields = 3;   // field 2 is hidden state: the isochoric inverse plastic right Cauchy-Green tensor
+  state_field(d, 0, "p", 1, FEFP_SLOT_P);
+  state_field(d, 1, "be_bar", 6, FEFP_SLOT_BE);
+  state_field(d, 2, "cp_bar_inv", 6, FEFP_SLOT_CPI);
+  d.n_slots = FEFP_NSLOTS;
+  // be_bar = Cp^-1 = identity: unstressed natural configuration
+  // (demos/jax/finite_strain_elastoplasticity/finite_strain_elastoplasticity.py:181)
+  d.unit_fields = 1u << 1 | 1u << 2;
+  d.alg_bytes = 976;
+  d.kernel = voce ? "fefp_kernel<1" : "fefp_kernel<0";
+  d.no_fields = "the FeFp kernels have no registers to spare";
+  d.build = voce ? build_voce_hardening : build_linear_hardening;
+  if (voce) d.residency_kernel = []() -> const void* { return (const void*)fefp_kernel<1, 0>; };
+  else d.residency_kernel = []() -> const void* { return (const void*)fefp_kernel<0, 0>; };
+  d.blocks_per_cu = 256;
+  d.set_layouts = L_FULL;
+  d.launch_layouts = L_FULL | L_COEF;
+  d.set_refusal = d.launch_refusal = "the FeFp tangent dP/dF is not symmetric: only DXM_TANGENT_FULL is available";
+  d.launch = voce ? launch_fefp_voce : launch_fefp_linear;
+  return d;
+}
+
+// Ogden: F in (72 B), PK1 (72) + dP/dF (648) + the isochoric PK2 stress (48) out; the state is written, never read
+constexpr LawDesc law_ogden() {
+  LawDesc d{};
+  d.id = DXM_LAW_OGDEN;
+  d.n_grad = d.n_flux = 9;
+  d.n_params = d.n_params_custom = 3;
+  d.n_isv_fields = d.n_fields = 1;
+  state_field(d, 0, "PK2Stress", 6, 0);
+  d.n_slots = OGDEN_NSLOTS;
+  d.alg_bytes = 840;
+  d.kernel = "ogden_kernel";
+  d.no_fields = "the Ogden kernel takes its exponents as per-handle constants";
+  d.build = build_ogden;
+  d.stock_only = "Ogden hyperelasticity has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(ogden_kernel_fn);
+  d.blocks_per_cu = OGDEN_BLOCKS_PER_CU;   // hyperelastic.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.set_refusal = "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record (sym / coef / pack4) exists for this law";
+  d.launch_refusal = "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record exists for this law";
+  d.no_fused = "the Ogden kernel has no fused displacement-gradient form: set option fused_gradient to 0 (F is then evaluated "
+               "by the gradient kernel) or pass F as an array";
+  d.launch = DXM_STOCK_ONLY(launch_ogden);   // hyperelastic.hip: F from the (N, 9) array, the full tangent
+  return d;
+}
+
+// Hosford: strain in (48 B), stress (48) + tangent (288) out; reads p and the hidden plastic strain (56), writes them and the
+// elastic strain (104)
+constexpr LawDesc law_hosford() {
+  LawDesc d{};
+  d.id = DXM_LAW_HOSFORD_LINEAR;
+  d.n_grad = d.n_flux = 6;
+  d.n_params = d.n_params_custom = 5;
+  d.n_isv_fields = 2;
+  d.n_fields = 3;   // field 2 is hidden state: what the update is driven by (hosford.hpp)
+  state_field(d, 0, "ElasticStrain", 6, HF_SLOT_EEL);
+  state_field(d, 1, "EquivalentPlasticStrain", 1, HF_SLOT_P);
+  state_field(d, 2, "PlasticStrain", 6, HF_SLOT_EP);
+  d.n_slots = HF_NSLOTS;
+  d.alg_bytes = 544;
+  d.kernel = "hosford_kernel";
+  d.no_fields = "the Hosford kernel takes its exponent's constants per handle";
+  d.build = build_hosford;
+  d.stock_only = "Hosford plasticity takes linear hardening only: it is served by the stock libdxmat, not by a custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(hosford_kernel_fn);
+  d.blocks_per_cu = HF_BLOCKS_PER_CU;   // hosford.hpp
+  d.set_layouts = d.launch_layouts = L_FULL | L_SYM;
+  d.set_refusal = "the Hosford tangent is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no coefficients "
+                  "(coef / pack4); DXM_TANGENT_FULL and DXM_TANGENT_SYM are available";
+  d.launch_refusal = "the Hosford tangent is a general symmetric 6x6: no coefficient record (coef / pack4) exists for this law";
+  d.no_fused = "the Hosford kernel has no fused displacement-gradient form: set option fused_gradient to 0 (the strain is then "
+               "evaluated by the gradient kernel) or pass the strain as an array";
+  d.launch = DXM_STOCK_ONLY(launch_hosford);   // hosford.hip: strain from the (N, 6) array, the full block or its upper triangle
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8 and 9 are not assigned and stay empty rows (law_known)
+static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
+    law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
+    law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(),
 };
+
+constexpr bool rows_in_place() {
+  for (int i = 0; i < DXM_LAW_COUNT; ++i)
+    if (kLaws[i].kernel && kLaws[i].id != i) return false;
+  return true;
+}
+static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
+static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel, "ids 6, 8 and 9 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
+
+// parameters a law takes in THIS build: a custom-hardening build takes [E, nu, sig0, c0..c5] for the two "voce" slots
+static int n_params_of(const LawDesc& d) { return kCustomBuild ? d.n_params_custom : d.n_params; }
+
+// what the mesh gradient kernel evaluates for the law: 1 the deformation gradient F (9 components), 0 the small strain (6)
+static int gradient_kind(const LawDesc& d) { return d.n_grad == 9 ? 1 : 0; }
 
 static int tangent_size(const dxm_material* m);
 
@@ -245,96 +555,14 @@ static void free_state(dxm_material* m) {
   m->state_base = nullptr;
 }
 
-// number of parameters a law takes in THIS build: a JIT build with a user-supplied hardening law
-// (DXM_CUSTOM_HARDENING) takes [E, nu, sig0, c0..c5] for the two "voce" slots
-static int n_params_of(int law) {
-#ifdef DXM_CUSTOM_HARDENING
-  if (law == DXM_LAW_J2_VOCE || law == DXM_LAW_FEFP_J2_VOCE) return 9;
-#endif
-  return kLaws[law].n_params;
-}
-
 static int build_params(dxm_material* m, const double* p, int np) {
-  const int expect = n_params_of(m->law);
+  const LawDesc& d = kLaws[m->law];
+  const int expect = n_params_of(d);
   if (np != expect) return fail(-1, "law %d expects %d parameters, got %d", m->law, expect, np);
-  if (m->law == DXM_LAW_OGDEN) {
-    // [alpha, mu, K] (Ogden.mfront); the exponents the kernel needs are formed here once
-    const double alpha = p[0], mu = p[1], K = p[2];
-    if (!(alpha != 0.0) || !std::isfinite(alpha)) return fail(-1, "Ogden: alpha must be finite and non-zero, got %g", alpha);
-    if (!(mu > 0.0) || !std::isfinite(mu)) return fail(-1, "Ogden: mu must be finite and > 0, got %g", mu);
-    if (!(K > 0.0) || !std::isfinite(K)) return fail(-1, "Ogden: K must be finite and > 0, got %g", K);
-    LawParams q{};
-    const double a = 0.5 * alpha;
-    q.mu = mu;
-    q.kappa = K;
-    q.c[OG_A] = a;
-    q.c[OG_AM2] = a - 2.0;
-    q.c[OG_MA3] = -a / 3.0;
-    q.c[OG_M] = a - 1.0;
-    q.maxit = m->maxit;
-    q.rtol = m->rtol;
-    m->prm = q;
-    m->raw_params.assign(p, p + np);
-    return 0;
-  }
-  const double E = p[0], nu = p[1];
-  if (!(E > 0.0) || !(nu > -1.0 && nu < 0.5)) return fail(-1, "invalid elastic constants E=%g nu=%g", E, nu);
   LawParams q{};
-  q.lambda = E * nu / (1 + nu) / (1 - 2 * nu);  // python_materials/elasticity.py:12-13
-  q.mu = E / 2 / (1 + nu);
-  q.kappa = q.lambda + 2.0 * q.mu / 3.0;
-  q.sig0 = 1.0;
-  switch (m->law) {
-    case DXM_LAW_ELASTIC_ISO: break;
-    case DXM_LAW_HOSFORD_LINEAR: {
-      // [E, nu, R0, H, a]: the exponent's derived constants are formed here once
-      const double R0 = p[2], H = p[3], a = p[4];
-      if (!(R0 > 0.0) || !std::isfinite(R0)) return fail(-1, "Hosford: R0 must be finite and > 0, got %g", R0);
-      if (!(H >= 0.0) || !std::isfinite(H)) return fail(-1, "Hosford: the hardening slope H must be finite and >= 0, got %g", H);
-      if (!(a >= 2.0) || !std::isfinite(a)) return fail(-1, "Hosford: the exponent a must be a finite number >= 2, got %g", a);
-      q.sig0 = R0;
-      q.h1 = H;
-      q.c[HF_A] = a;
-      q.c[HF_AM2] = a - 2.0;
-      q.c[HF_INVA] = 1.0 / a;
-      q.c[HF_AM1] = a - 1.0;
-      break;
-    }
-    case DXM_LAW_J2_LINEAR:
-    case DXM_LAW_FEFP_J2_LINEAR: q.sig0 = p[2]; q.h1 = p[3]; break;
-    case DXM_LAW_J2_VOCE:
-    case DXM_LAW_FEFP_J2_VOCE:
-#ifdef DXM_CUSTOM_HARDENING
-      q.sig0 = p[2];
-      for (int k = 0; k < 6; ++k) q.c[k] = p[3 + k];
-#else
-      q.sig0 = p[2]; q.h1 = p[3]; q.h2 = p[4];
-#endif
-      break;
-    case DXM_LAW_RAMBERG_OSGOOD: {
-      // [E, nu, sig0, alpha, n]; the local Newton's monotone convergence needs a convex f, i.e. n >= 1
-      const double sig0 = p[2], alpha = p[3], n = p[4];
-      if (!(sig0 > 0.0)) return fail(-1, "Ramberg-Osgood: sig0 must be > 0, got %g", sig0);
-      if (!(alpha > 0.0)) return fail(-1, "Ramberg-Osgood: alpha must be > 0, got %g", alpha);
-      if (!(n >= 1.0) || !std::isfinite(n)) return fail(-1, "Ramberg-Osgood: n must be a finite number >= 1, got %g", n);
-      q.sig0 = sig0;
-      q.kappa = E / (3.0 * (1.0 - 2.0 * nu));   // the .mfront file's K
-      q.c[RO_I3MU] = 1.0 / (3.0 * q.mu);
-      q.c[RO_BETA] = alpha * sig0 / E;
-      q.c[RO_ISIG0] = 1.0 / sig0;
-      q.c[RO_N] = n;
-      q.c[RO_INVN] = 1.0 / n;
-      q.c[RO_ESIG] = E * RO_EPS;
-      q.h1 = 3.0 * q.mu;
-      q.h2 = n * q.c[RO_BETA];
-      break;
-    }
-  }
   q.maxit = m->maxit;
-  // relative to the initial yield stress, floored so that a law with R(0) = 0 keeps a reachable tolerance
   q.rtol = m->rtol;
-  q.tol = m->rtol * fmax(fabs(q.sig0), 2e-8 * q.mu);
-  if (m->law == DXM_LAW_RAMBERG_OSGOOD) q.tol = q.c[RO_I3MU] * RO_EPS;   // no residual tolerance: the floor of f' (small_strain.hpp)
+  if (int rc = d.build(p, q)) return rc;
   m->prm = q;
   m->raw_params.assign(p, p + np);
   return 0;
@@ -394,13 +622,7 @@ extern "C" {
 
 int dxm_abi_version(void) { return DXM_ABI_VERSION; }
 
-int dxm_has_custom_hardening(void) {
-#ifdef DXM_CUSTOM_HARDENING
-  return 1;
-#else
-  return 0;
-#endif
-}
+int dxm_has_custom_hardening(void) { return kCustomBuild ? 1 : 0; }
 
 const char* dxm_last_error(void) { return g_last_error.c_str(); }
 
@@ -417,7 +639,7 @@ int dxm_law_info_get(int law, dxm_law_info* out) {
   memset(out, 0, sizeof(*out));
   out->n_grad = d.n_grad;
   out->n_flux = d.n_flux;
-  out->n_params = n_params_of(law);
+  out->n_params = n_params_of(d);
   out->n_isv_fields = d.n_isv_fields;
   for (int f = 0; f < DXM_MAX_STATE_FIELDS; ++f) {
     out->isv_dim[f] = d.isv_dim[f];
@@ -434,12 +656,9 @@ static int init_state(dxm_material* m) {
   const size_t bytes = (size_t)d.n_slots * m->ld * sizeof(double);
   for (int w = 0; w < 2; ++w) {
     HIP_TRY(hipMemsetAsync(m->state[w], 0, bytes, m->own_stream));
-    if (m->law == DXM_LAW_FEFP_J2_VOCE || m->law == DXM_LAW_FEFP_J2_LINEAR) {
-      // be_bar = Cp^-1 = identity: unstressed natural configuration
-      // (demos/jax/finite_strain_elastoplasticity/finite_strain_elastoplasticity.py:181)
-      const int ones[6] = {FEFP_SLOT_BE + 0, FEFP_SLOT_BE + 1, FEFP_SLOT_BE + 2,
-                           FEFP_SLOT_CPI + 0, FEFP_SLOT_CPI + 1, FEFP_SLOT_CPI + 2};
-      for (int s : ones) {
+    for (int f = 0; f < d.n_fields; ++f) {
+      if (!(d.unit_fields & (1u << f))) continue;
+      for (int s = d.isv_slot[f]; s < d.isv_slot[f] + 3; ++s) {   // the diagonal of the identity
         const int blocks = (int)((m->ld + 255) / 256);
         hipLaunchKernelGGL(fill_slot_kernel, dim3(blocks), dim3(256), 0, m->own_stream,
                            m->state[w] + (size_t)s * m->ld, m->ld, 1.0);
@@ -461,21 +680,9 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
     return nullptr;
   }
   if (device < 0 || device >= ndev) { fail(-1, "device %d out of range [0,%d)", device, ndev); return nullptr; }
-#ifdef DXM_CUSTOM_HARDENING
+  const LawDesc& d = kLaws[law];
   // a library built for a user-supplied hardening law carries the hardening kernels only
-  if (law == DXM_LAW_RAMBERG_OSGOOD) {
-    fail(-1, "Ramberg-Osgood has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build");
-    return nullptr;
-  }
-  if (law == DXM_LAW_OGDEN) {
-    fail(-1, "Ogden hyperelasticity has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build");
-    return nullptr;
-  }
-  if (law == DXM_LAW_HOSFORD_LINEAR) {
-    fail(-1, "Hosford plasticity takes linear hardening only: it is served by the stock libdxmat, not by a custom-hardening build");
-    return nullptr;
-  }
-#endif
+  if (kCustomBuild && d.stock_only) { fail(-1, "%s", d.stock_only); return nullptr; }
   dxm_material* m = new dxm_material();
   m->law = law;
   m->device = device;
@@ -495,7 +702,6 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
       hipEventCreateWithFlags(&m->last_event, hipEventDisableTiming) != hipSuccess) {
     fail(-2, "hipStreamCreate / hipEventCreate failed"); return bail();
   }
-  const LawDesc& d = kLaws[law];
   if (d.n_slots > 0) {
     const size_t bytes = (size_t)d.n_slots * m->ld * sizeof(double);
     {
@@ -506,49 +712,22 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
       m->state[1] = reinterpret_cast<double*>(reinterpret_cast<char*>(m->state_base) + bytes + m->s1_skew);
     }
   }
-  // grid size, in workgroups per CU.  FeFp: the workgroups that are resident at once (persistent
-  // grid).  Small strain: 32 = 8 x the resident 4: a grid of exactly-resident workgroups starts all
-  // waves together and keeps them in lockstep (everybody loads, then everybody stores); workgroups
-  // that are dispatched as others retire spread those phases, 3-6 % faster at 1e7 points in the fast
-  // placement mode and 10 % in the slow one (tools/grid_sweep.py, profiles/archive/r01_grid_sweep.jsonl).
+  // grid size, in workgroups per CU: the row's figure (the paragraphs at kLaws), else the residency of its kernel
   {
-    int occ = 0;
-    const void* fn = nullptr;
-    switch (law) {
-      case DXM_LAW_ELASTIC_ISO: fn = (const void*)small_strain_kernel<LAW_ELASTIC, TL_FULL>; break;
-      case DXM_LAW_J2_LINEAR: fn = (const void*)small_strain_kernel<LAW_J2_LINEAR, TL_FULL>; break;
-      case DXM_LAW_J2_VOCE: fn = (const void*)small_strain_kernel<LAW_J2_VOCE, TL_FULL>; break;
-      case DXM_LAW_FEFP_J2_LINEAR: fn = (const void*)fefp_kernel<0, 0>; break;
-#ifndef DXM_CUSTOM_HARDENING
-      case DXM_LAW_RAMBERG_OSGOOD: fn = ramberg_osgood_kernel(); break;
-      case DXM_LAW_OGDEN: fn = ogden_kernel_fn(); break;
-      case DXM_LAW_HOSFORD_LINEAR: fn = hosford_kernel_fn(); break;
-#endif
-      default: fn = (const void*)fefp_kernel<1, 0>; break;
-    }
     // residency from the kernel's own resources (the occupancy API over-reports on ROCm 7.2):
     // waves/SIMD by allocated VGPRs (512-entry file, granule 8), workgroups by LDS (160 KiB/CU)
     hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, fn) == hipSuccess && fa.numRegs > 0) {
+    if (d.residency_kernel && hipFuncGetAttributes(&fa, d.residency_kernel()) == hipSuccess && fa.numRegs > 0) {
       const int alloc = ((fa.numRegs + 7) / 8) * 8;
       int waves_simd = 512 / alloc;
       if (waves_simd > 8) waves_simd = 8;
       int by_vgpr = waves_simd * 4 / WAVES_PER_BLOCK;
       int by_lds = fa.sharedSizeBytes > 0 ? (int)(160 * 1024 / fa.sharedSizeBytes) : 8;
-      occ = by_vgpr < by_lds ? by_vgpr : by_lds;
+      int occ = by_vgpr < by_lds ? by_vgpr : by_lds;
       if (occ < 1) occ = 1;
       m->blocks_per_cu = occ;
     }
-    if (law == DXM_LAW_ELASTIC_ISO || law == DXM_LAW_J2_LINEAR) m->blocks_per_cu = 32;
-    // The laws with a local Newton iteration (Voce or traced hardening, FeFp) do a point-dependent amount of work per tile: a
-    // grid of one workgroup per 256 points (up to 256 per CU, the cap; a grid-stride loop beyond) lets the dispatcher balance
-    // it -- Voce +3 %, FeFp +2.5 % over the persistent grids above at 1e7 points (profiles/archive/r03_grid_size_by_law.txt); the
-    // linear-hardening kernel, whose tiles all cost the same, loses 2.5 % with it and keeps 32.
-    if (law == DXM_LAW_J2_VOCE || law == DXM_LAW_FEFP_J2_VOCE || law == DXM_LAW_FEFP_J2_LINEAR) m->blocks_per_cu = 256;
-    // Ramberg-Osgood: RO_BLOCKS_PER_CU (DESIGN.md section "Ramberg-Osgood")
-    if (law == DXM_LAW_RAMBERG_OSGOOD) m->blocks_per_cu = RO_BLOCKS_PER_CU;
-    if (law == DXM_LAW_OGDEN) m->blocks_per_cu = OGDEN_BLOCKS_PER_CU;   // hyperelastic.hpp
-    if (law == DXM_LAW_HOSFORD_LINEAR) m->blocks_per_cu = HF_BLOCKS_PER_CU;   // hosford.hpp
+    if (d.blocks_per_cu) m->blocks_per_cu = d.blocks_per_cu;
   }
   // one record per workgroup and launch.  A single launch has at most num_cu * 256 workgroups (the largest grid
   // dxm_set_option("blocks_per_cu") allows); the chunked host path appends the records of up to DXM_MAX_CHUNKS
@@ -617,15 +796,8 @@ int dxm_set_tangent_layout(dxm_material* m, int layout) {
   if (!m) return fail(-1, "null handle");
   if (layout != DXM_TANGENT_FULL && layout != DXM_TANGENT_SYM && layout != DXM_TANGENT_COEF && layout != DXM_TANGENT_PACK4)
     return fail(-1, "unknown tangent layout %d", layout);
-  if (layout != DXM_TANGENT_FULL && m->law == DXM_LAW_OGDEN)
-    return fail(-1, "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record (sym / coef / pack4) exists for this law");
-  if ((layout == DXM_TANGENT_COEF || layout == DXM_TANGENT_PACK4) && m->law == DXM_LAW_HOSFORD_LINEAR)
-    return fail(-1, "the Hosford tangent is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no coefficients "
-                    "(coef / pack4); DXM_TANGENT_FULL and DXM_TANGENT_SYM are available");
-  if (layout != DXM_TANGENT_FULL && kLaws[m->law].n_grad == 9)
-    return fail(-1, "the FeFp tangent dP/dF is not symmetric: only DXM_TANGENT_FULL is available");
-  if ((layout == DXM_TANGENT_COEF || layout == DXM_TANGENT_PACK4) && m->law == DXM_LAW_ELASTIC_ISO)
-    return fail(-1, "the elastic tangent is the constant lambda 1x1 + 2 mu I: there are no per-point coefficients");
+  const LawDesc& d = kLaws[m->law];
+  if (!(d.set_layouts & (1u << layout))) return fail(-1, "%s", d.set_refusal);
   m->tangent_layout = layout;
   ++m->epoch;
   return 0;
@@ -898,19 +1070,21 @@ int dxm_revert(dxm_material* m) {
 }  // extern "C"
 
 // ---- launch -------------------------------------------------------------------------------
-// One launch over the point range [off, off + cnt) (off a multiple of 256): the chunk-pipelined host
-// path issues several of these on alternating streams; everything else launches the whole batch.
-// The block records of the launch go to m->d_stats[stats_off ...).
+// The launchers of the rows of kLaws: one launch each over the point range of a LaunchArgs record.
 template <int LAW>
-static void launch_small_strain(dxm_material* m, int grid, hipStream_t st, int64_t off, int64_t cnt,
-                                const double* grad, double* flux, double* ct, int stats_off,
-                                const MeshSource* fused, int tl) {
-  const double* s0 = m->state[0] + off;
-  double* s1 = m->state[1] + off;
-  BlockStats* bs = m->d_stats + stats_off;
+static void launch_small_strain(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  const int grid = a.grid, tl = a.tl;
+  const hipStream_t st = a.st;
+  const int64_t cnt = a.cnt;
+  const double* grad = a.grad;
+  double *flux = a.flux, *ct = a.ct;
+  const double* s0 = m->state[0] + a.off;
+  double* s1 = m->state[1] + a.off;
+  BlockStats* bs = m->d_stats + a.stats_off;
   const MeshSource none{};
-  const MeshSource& src = fused ? *fused : none;
-  const int g = fused ? fused->kind : 0;   // where the strain comes from: array / hex8 x 8 / tet4 / Lagrange simplex
+  const MeshSource& src = a.fused ? *a.fused : none;
+  const int g = a.fused ? a.fused->kind : 0;   // where the strain comes from: array / hex8 x 8 / tet4 / Lagrange simplex
   // J2 kernels: 2.25 KiB of unused dynamic LDS on top of the static 30.1 KiB keep FOUR workgroups (16 waves) per CU.  The
   // linear-hardening kernel needs 95 VGPRs since the flow direction of the tangent comes from the stress (it was 103):
   // a fifth wave per SIMD would fit and costs 0.65 % (0.8169 vs 0.8116 / 0.8123 ms per 1e7 points in one process,
@@ -920,7 +1094,7 @@ static void launch_small_strain(dxm_material* m, int grid, hipStream_t st, int64
   if constexpr (LAW != LAW_ELASTIC) {
     if (m->pf_mask) {   // param_fields.hip: the streams advance with the range like the state slots
       ParamStreams pf{};
-      for (int k = 0; k < PF_COUNT; ++k) pf.p[k] = m->pf_stream[k] ? m->pf_stream[k] + off : nullptr;
+      for (int k = 0; k < PF_COUNT; ++k) pf.p[k] = m->pf_stream[k] ? m->pf_stream[k] + a.off : nullptr;
       param_fields_launch(LAW, tl, g, grid, dyn_lds, st, m->prm, pf, cnt, grad, s0, s1, m->ld, flux, ct, bs, src);
       return;
     }
@@ -938,8 +1112,53 @@ static void launch_small_strain(dxm_material* m, int grid, hipStream_t st, int64
 #undef DXM_LAUNCH_SS
 }
 
-// tl: tangent layout of THIS launch (the host path may ask for the coefficient form although the handle's
-// layout is the full block: it rebuilds the block on the host)
+// voce: Voce hardening (or the traced law of a custom-hardening build); else linear hardening
+static void launch_fefp(const LaunchArgs& a, bool voce) {
+  dxm_material* m = a.m;
+  const int grid = a.grid;
+  const hipStream_t st = a.st;
+  const int64_t cnt = a.cnt;
+  const double* grad = a.grad;
+  double *flux = a.flux, *ct = a.ct;
+  const double* s0 = m->state[0] + a.off;
+  double* s1 = m->state[1] + a.off;
+  BlockStats* bs = m->d_stats + a.stats_off;
+  const MeshSource none{};
+  const MeshSource& fsrc = a.fused ? *a.fused : none;
+  const int g = a.fused ? a.fused->kind : 0;
+#define DXM_LAUNCH_FEFP(HARD, G, T) \
+  hipLaunchKernelGGL((fefp_kernel<HARD, G, T>), dim3(grid), dim3(BLOCK), 0, st, m->prm, cnt, grad, s0, s1, m->ld, flux, ct, bs, fsrc)
+#define DXM_LAUNCH_FEFP_G(HARD, T) do { if (g == 0) DXM_LAUNCH_FEFP(HARD, 0, T); else if (g == 1) DXM_LAUNCH_FEFP(HARD, 1, T); \
+                                       else if (g == 2) DXM_LAUNCH_FEFP(HARD, 2, T); else DXM_LAUNCH_FEFP(HARD, 3, T); } while (0)
+  // tl == TL_COEF: the 54 building blocks of the tangent per point instead of its 81 entries (host-buffer form)
+  if (a.tl == TL_COEF) { if (voce) DXM_LAUNCH_FEFP_G(1, 1); else DXM_LAUNCH_FEFP_G(0, 1); }
+  else                 { if (voce) DXM_LAUNCH_FEFP_G(1, 0); else DXM_LAUNCH_FEFP_G(0, 0); }
+#undef DXM_LAUNCH_FEFP_G
+#undef DXM_LAUNCH_FEFP
+}
+static void launch_fefp_voce(const LaunchArgs& a) { launch_fefp(a, true); }
+static void launch_fefp_linear(const LaunchArgs& a) { launch_fefp(a, false); }
+
+#ifndef DXM_CUSTOM_HARDENING
+static void launch_ramberg_osgood(const LaunchArgs& a) {
+  const MeshSource none{};
+  ramberg_osgood_launch(a.tl, a.fused ? a.fused->kind : 0, a.grid, a.st, a.m->prm, a.cnt, a.grad, a.flux, a.ct,
+                        a.m->d_stats + a.stats_off, a.fused ? *a.fused : none);
+}
+
+static void launch_ogden(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  ogden_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[1] + a.off, m->ld, a.flux, a.ct, m->d_stats + a.stats_off);
+}
+
+static void launch_hosford(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  hosford_launch(a.tl, a.grid, a.st, m->prm, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
+                 m->d_stats + a.stats_off);
+}
+#endif
+
+// tl: tangent layout of THIS launch (LaunchArgs)
 static int launch_range(dxm_material* m, int64_t off, int64_t cnt, const double* grad, double* flux,
                         double* ct, hipStream_t st, int stats_off, int* grid_out,
                         const MeshSource* fused, int tl) {
@@ -950,54 +1169,11 @@ static int launch_range(dxm_material* m, int64_t off, int64_t cnt, const double*
   const int64_t blocks = dxm_host::launch_grid(cnt, m->num_cu, m->blocks_per_cu);
   if (stats_off + blocks > m->stats_capacity) return fail(-1, "internal: stats buffer too small");
   const int grid = (int)blocks;
-  switch (m->law) {
-    case DXM_LAW_ELASTIC_ISO: launch_small_strain<LAW_ELASTIC>(m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl); break;
-    case DXM_LAW_J2_LINEAR: launch_small_strain<LAW_J2_LINEAR>(m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl); break;
-    case DXM_LAW_J2_VOCE: launch_small_strain<LAW_J2_VOCE>(m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl); break;
-#ifndef DXM_CUSTOM_HARDENING
-    case DXM_LAW_RAMBERG_OSGOOD: {   // ramberg_osgood.hip
-      const MeshSource none{};
-      ramberg_osgood_launch(tl, fused ? fused->kind : 0, grid, st, m->prm, cnt, grad, flux, ct, m->d_stats + stats_off, fused ? *fused : none);
-      break;
-    }
-    case DXM_LAW_OGDEN:   // hyperelastic.hip: F from the (N, 9) array, the full tangent
-      if (fused)
-        return fail(-1, "the Ogden kernel has no fused displacement-gradient form: set option fused_gradient to 0 (F is then evaluated "
-                        "by the gradient kernel) or pass F as an array");
-      if (tl != TL_FULL) return fail(-1, "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record exists for this law");
-      ogden_launch(grid, st, m->prm, cnt, grad, m->state[1] + off, m->ld, flux, ct, m->d_stats + stats_off);
-      break;
-    case DXM_LAW_HOSFORD_LINEAR:   // hosford.hip: strain from the (N, 6) array, the full block or its upper triangle
-      if (fused)
-        return fail(-1, "the Hosford kernel has no fused displacement-gradient form: set option fused_gradient to 0 (the strain is then "
-                        "evaluated by the gradient kernel) or pass the strain as an array");
-      if (tl != TL_FULL && tl != TL_SYM)
-        return fail(-1, "the Hosford tangent is a general symmetric 6x6: no coefficient record (coef / pack4) exists for this law");
-      hosford_launch(tl, grid, st, m->prm, cnt, grad, m->state[0] + off, m->state[1] + off, m->ld, flux, ct, m->d_stats + stats_off);
-      break;
-#endif
-    case DXM_LAW_FEFP_J2_VOCE:
-    case DXM_LAW_FEFP_J2_LINEAR: {
-      const double* s0 = m->state[0] + off;
-      double* s1 = m->state[1] + off;
-      BlockStats* bs = m->d_stats + stats_off;
-      const MeshSource none{};
-      const bool voce = m->law == DXM_LAW_FEFP_J2_VOCE;
-      const MeshSource& fsrc = fused ? *fused : none;
-      const int g = fused ? fused->kind : 0;
-#define DXM_LAUNCH_FEFP(HARD, G, T) \
-  hipLaunchKernelGGL((fefp_kernel<HARD, G, T>), dim3(grid), dim3(BLOCK), 0, st, m->prm, cnt, grad, s0, s1, m->ld, flux, ct, bs, fsrc)
-#define DXM_LAUNCH_FEFP_G(HARD, T) do { if (g == 0) DXM_LAUNCH_FEFP(HARD, 0, T); else if (g == 1) DXM_LAUNCH_FEFP(HARD, 1, T); \
-                                       else if (g == 2) DXM_LAUNCH_FEFP(HARD, 2, T); else DXM_LAUNCH_FEFP(HARD, 3, T); } while (0)
-      // tl == TL_COEF: the 54 building blocks of the tangent per point instead of its 81 entries (host-buffer form)
-      if (tl == TL_COEF) { if (voce) DXM_LAUNCH_FEFP_G(1, 1); else DXM_LAUNCH_FEFP_G(0, 1); }
-      else               { if (voce) DXM_LAUNCH_FEFP_G(1, 0); else DXM_LAUNCH_FEFP_G(0, 0); }
-#undef DXM_LAUNCH_FEFP_G
-#undef DXM_LAUNCH_FEFP
-      break;
-    }
-    default: return fail(-1, "law %d not launchable", m->law);
-  }
+  const LawDesc& d = kLaws[m->law];
+  if (!d.launch) return fail(-1, "law %d not launchable", m->law);
+  if (fused && d.no_fused) return fail(-1, "%s", d.no_fused);
+  if (!(d.launch_layouts & (1u << tl))) return fail(-1, "%s", d.launch_refusal);
+  d.launch(LaunchArgs{m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl});
   HIP_TRY(hipGetLastError());
   *grid_out = grid;
   return 0;
@@ -1126,7 +1302,7 @@ static dxm_host::TransferRequest transfer_request(const dxm_material* m, const d
   const LawDesc& d = kLaws[m->law];
   const int64_t n = m->n;
   dxm_host::TransferRequest r{};
-  r.law = m->law; r.n_grad = d.n_grad; r.n_flux = d.n_flux; r.n_isv_fields = d.n_isv_fields;
+  r.law = d.id; r.n_grad = d.n_grad; r.n_flux = d.n_flux; r.n_isv_fields = d.n_isv_fields;
   for (int f = 0; f < d.n_isv_fields; ++f) {
     r.isv_dim[f] = d.isv_dim[f];
     if (m->isv_out[f]) r.bound_fields |= 1u << f;
@@ -1726,8 +1902,7 @@ static int integrate_displacement_host(dxm_material* m, dxm_mesh* mesh, const do
   if (fuse) {
     src = mesh_source(mesh, mesh->d_u);
   } else {
-    const int kind = kLaws[m->law].n_grad == 9 ? 1 : 0;
-    if (int rc = dxm_mesh_gradient_device(mesh, mesh->d_u, kind, m->d_grad, st)) return rc;
+    if (int rc = dxm_mesh_gradient_device(mesh, mesh->d_u, gradient_kind(kLaws[m->law]), m->d_grad, st)) return rc;
   }
   // the displacement upload (and the gradient array) are produced on own_stream; chunks on the second stream wait for it
   if (!mesh->grad_done) HIP_TRY(hipEventCreateWithFlags(&mesh->grad_done, hipEventDisableTiming));
@@ -1770,7 +1945,7 @@ int dxm_integrate_displacement_device(dxm_material* m, dxm_mesh* mesh, const dou
   }
   // two kernels on the caller's stream through the handle's gradient scratch
   if (!m->d_grad) HIP_TRY(hipMalloc(&m->d_grad, sizeof(double) * m->n * d.n_grad));
-  if (int rc = dxm_mesh_gradient_device(mesh, u_dev, d.n_grad == 9 ? 1 : 0, m->d_grad, hip_stream)) return rc;
+  if (int rc = dxm_mesh_gradient_device(mesh, u_dev, gradient_kind(d), m->d_grad, hip_stream)) return rc;
   return launch(m, m->d_grad, flux_dev, ct_dev, st);
 }
 
@@ -1783,8 +1958,7 @@ const double* dxm_state_ptr(const dxm_material* m, int which, int field, int com
 
 const char* dxm_kernel_name(const dxm_material* m) {
   if (!m) return "";
-  if (m->pf_mask) return m->law == DXM_LAW_J2_LINEAR ? "small_strain_field_kernel<1" : "small_strain_field_kernel<2";
-  return kLaws[m->law].kernel;
+  return m->pf_mask ? kLaws[m->law].field_kernel : kLaws[m->law].kernel;
 }
 
 int dxm_expand_tangent_device(const double* coef_dev, int64_t npoints, double* ct_dev, int device, void* hip_stream) {
@@ -1834,17 +2008,11 @@ static int pf_refresh_elastic(dxm_material* m, hipStream_t st) {
 
 static int pf_check(const dxm_material* m, int idx) {
   if (!m) return fail(-1, "null handle");
-#ifdef DXM_CUSTOM_HARDENING
-  if (m) return fail(-1, "per-point parameter fields are served by the stock libdxmat, not by a custom-hardening build");
-#endif
-  if (m->law != DXM_LAW_J2_LINEAR && m->law != DXM_LAW_J2_VOCE)
-    return fail(-1, "per-point parameter fields exist for DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE only (law %d: %s)", m->law,
-                m->law == DXM_LAW_ELASTIC_ISO ? "the elastic tangent is a constant the host path never downloads"
-                : m->law == DXM_LAW_RAMBERG_OSGOOD ? "Ramberg-Osgood precomputes per-handle Newton constants on the host"
-                : m->law == DXM_LAW_OGDEN          ? "the Ogden kernel takes its exponents as per-handle constants"
-                : m->law == DXM_LAW_HOSFORD_LINEAR ? "the Hosford kernel takes its exponent's constants per handle"
-                                                   : "the FeFp kernels have no registers to spare");
-  if (idx < 0 || idx >= kLaws[m->law].n_params) return fail(-1, "law %d has no parameter %d", m->law, idx);
+  if (kCustomBuild) return fail(-1, "per-point parameter fields are served by the stock libdxmat, not by a custom-hardening build");
+  const LawDesc& d = kLaws[m->law];
+  if (!d.field_kernel)
+    return fail(-1, "per-point parameter fields exist for DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE only (law %d: %s)", m->law, d.no_fields);
+  if (idx < 0 || idx >= d.n_params) return fail(-1, "law %d has no parameter %d", m->law, idx);
   return 0;
 }
 
