@@ -2,7 +2,7 @@
 #include "param_fields.hpp"
 
 #define DXM_UPDATE_KERNELS_ONLY
-#include "small_strain_fields.hpp"
+#include "small_strain.hpp"
 
 namespace dxm {
 

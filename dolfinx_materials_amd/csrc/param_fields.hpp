@@ -1,7 +1,8 @@
-// Host entry points of the J2 kernels with per-point parameter fields (param_fields.hip).  Like the Ramberg-Osgood kernels
-// (ramberg_osgood.hpp) they are instantiated in a translation unit of their own: the device modules of dxmat.hip and
+// Host entry points of the J2 kernels with per-point parameter fields (param_fields.hip), and the record of streams the kernels take.
+// small_strain_field_kernel is defined beside small_strain_kernel (small_strain.hpp: one tile body for both) and, like the
+// Ramberg-Osgood kernels (ramberg_osgood.hpp), instantiated in a translation unit of its own: the device modules of dxmat.hip and
 // ramberg_osgood.hip compile to exactly the instruction streams they had before this form existed
-// (tools/check_param_fields_build.py compares them).  A custom-hardening build compiles dxmat.hip alone and refuses fields.
+// (tools/check_device_asm.py compares them).  A custom-hardening build compiles dxmat.hip alone and refuses fields.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,22 +1,11 @@
-// The J2 small-strain kernels with per-point parameter fields (instantiated in param_fields.hip only).
-#pragma once
-#include "param_fields.hpp"
-#include "small_strain.hpp"
-
-namespace dxm {
-
-// small_strain_kernel (small_strain.hpp) for the two J2 laws with the bound streams of `pf` read per point.  The steps, the LDS
-// staging, the store loops and every arithmetic expression are those of that kernel: a field that is constant gives the bits
-// of the uniform kernel (tests/test_gpu_param_fields.py).  What differs is marked "fields:".
-template <int LAW, int TL, int GRAD = 0>
-__global__ void __launch_bounds__(BLOCK, 4)
-small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int64_t n, const double* __restrict__ eps,
-                          const double* __restrict__ s0, double* __restrict__ s1, const int64_t ld,
-                          double* __restrict__ sig, double* __restrict__ ct,
-                          BlockStats* __restrict__ stats, const MeshSource src) {
-  static_assert(LAW == LAW_J2_LINEAR || LAW == LAW_J2_VOCE, "parameter fields: the J2 laws");
+// The tile body of the small-strain update kernels: NOT a header of its own.  small_strain.hpp includes this text inside the braces
+// of small_strain_kernel (FIELDS = false) and of small_strain_field_kernel (FIELDS = true); each defines, just before the include,
+//   constexpr bool FIELDS    and    pf (ParamStreams: the kernel's argument, or an all-null constant that only discarded code names)
+// beside the common arguments (prm, n, eps, s0, s1, ld, sig, ct, stats, src) and template parameters (LAW, TL, GRAD).  Shared as
+// text and not through a function: see the comment at the top of small_strain.hpp.
   __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * SS_LDS_PER_WAVE];
   __shared__ unsigned long long red[4 * WAVES_PER_BLOCK];
+
   int lane = threadIdx.x & (WAVE - 1);
   // (not made scalar with readfirstlane as in fefp.hpp: measured in one process, three handles each, that build is
   // 0.45 % slower -- 96 instead of 103 VGPRs makes a fifth wave per SIMD resident, which this kernel does not like)
@@ -36,9 +25,13 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
        tile += tile_stride) {
     const int64_t base = tile * WAVE;
     const int npts = (n - base) < WAVE ? (int)(n - base) : WAVE;
-    // the lane index is re-read through an opaque copy once per tile, as in the uniform Voce kernel
-    asm volatile("" : "+v"(lane));
-    lane &= WAVE - 1;
+    if constexpr (FIELDS || LAW == LAW_J2_VOCE || LAW == LAW_RAMBERG_OSGOOD) {
+      // the lane index is re-read through an opaque copy once per tile: per-lane invariants hoisted out of the
+      // tile loop otherwise push the Voce kernels over their 128-register budget (2-8 spilled VGPRs; the fused
+      // Ramberg-Osgood kernels, whose inlined exp / log are live at the same time, 2-16).  FIELDS: for both laws
+      asm volatile("" : "+v"(lane));
+      lane &= WAVE - 1;
+    }
     const bool valid = lane < npts;
     const int64_t gi = base + lane;
 
@@ -58,10 +51,12 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
         for (int k = 0; k < 3; ++k) stage2[k * WAVE + lane] = v[k];
       }
       // ---- old state, SoA (issued before the LDS round trip completes) -------------------------
-      if (valid) {
-        p_n = stream_load<3>(s0 + gi);
+      if constexpr (ss_has_state<LAW>) {
+        if (valid) {
+          p_n = stream_load<3>(s0 + gi);
 #pragma unroll
-        for (int c = 0; c < 6; ++c) ep[c] = stream_load<3>(s0 + (int64_t)(1 + c) * ld + gi);
+          for (int c = 0; c < 6; ++c) ep[c] = stream_load<3>(s0 + (int64_t)(1 + c) * ld + gi);
+        }
       }
       wave_lds_sync();
       // ---- 2. my point's strain ----------------------------------------------------------------
@@ -120,33 +115,38 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
         e[3] = r * (Hd[1] + Hd[3]); e[4] = r * (Hd[2] + Hd[6]); e[5] = r * (Hd[5] + Hd[7]);
       }
       // old state only now: 14 registers fewer live through the gradient evaluation
-      if (valid) {
-        p_n = stream_load<3>(s0 + gi);
+      if constexpr (ss_has_state<LAW>) {
+        if (valid) {
+          p_n = stream_load<3>(s0 + gi);
 #pragma unroll
-        for (int c = 0; c < 6; ++c) ep[c] = stream_load<3>(s0 + (int64_t)(1 + c) * ld + gi);
+          for (int c = 0; c < 6; ++c) ep[c] = stream_load<3>(s0 + (int64_t)(1 + c) * ld + gi);
+        }
       }
     }
 
     // ---- 3. constitutive update --------------------------------------------------------------
     double lambda = lambda_u, mu = mu_u;
-    // fields: this point's parameters.  Bound streams: 8 B per lane at gi, like the state slots (a lane past the end keeps
-    // the uniform values)
-    LawParams lp = prm;
-    {
+    // lp, this point's parameters as the update reads them: the kernel's own (an alias, not a copy: a copy changes the uniform
+    // kernels' code), or with FIELDS the copy lp_point that the bound streams overwrite (unused and without code otherwise)
+    LawParams lp_point;
+    const LawParams& lp = FIELDS ? lp_point : prm;
+    if constexpr (FIELDS) {
+      lp_point = prm;
+      // bound streams: 8 B per lane at gi, like the state slots (a lane past the end keeps the uniform values)
       if (pf.p[PF_LAMBDA] && valid) lambda = stream_load<3>(pf.p[PF_LAMBDA] + gi);
       if (pf.p[PF_MU] && valid) mu = stream_load<3>(pf.p[PF_MU] + gi);
-      if (pf.p[PF_SIG0] && valid) lp.sig0 = stream_load<3>(pf.p[PF_SIG0] + gi);
-      if (pf.p[PF_H1] && valid) lp.h1 = stream_load<3>(pf.p[PF_H1] + gi);
+      if (pf.p[PF_SIG0] && valid) lp_point.sig0 = stream_load<3>(pf.p[PF_SIG0] + gi);
+      if (pf.p[PF_H1] && valid) lp_point.h1 = stream_load<3>(pf.p[PF_H1] + gi);
       if constexpr (LAW == LAW_J2_VOCE) {
-        if (pf.p[PF_H2] && valid) lp.h2 = stream_load<3>(pf.p[PF_H2] + gi);
+        if (pf.p[PF_H2] && valid) lp_point.h2 = stream_load<3>(pf.p[PF_H2] + gi);
         // the Newton tolerance of dxmat.hip::build_params, per point
-        if (pf.p[PF_SIG0] || pf.p[PF_MU]) lp.tol = prm.rtol * fmax(fabs(lp.sig0), 2e-8 * mu);
+        if (pf.p[PF_SIG0] || pf.p[PF_MU]) lp_point.tol = prm.rtol * fmax(fabs(lp.sig0), 2e-8 * mu);
       }
     }
     double c1 = lambda, c2 = 2.0 * mu, c3 = 0.0;
     double wn = 0.0;   // n = dev(sigma) wn: the direction the tangent is built with (0 for an elastic point)
     double p_new = p_n;
-    {
+    if constexpr (ss_has_state<LAW>) {
       // trial elastic strain                                   mfront:52  eel += deto
 #pragma unroll
       for (int c = 0; c < 6; ++c) e[c] -= ep[c];
@@ -163,12 +163,12 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
 #pragma unroll
       for (int c = 0; c < 6; ++c) nrm2 += se[c] * se[c];
       const double seq = sqrt(1.5 * nrm2);                    // mfront:54
-      const double f = seq - hardening_R<LAW>(lp, p_n);      // mfront:55
+      const double f = seq - hardening_R<LAW>(lp, p_n);       // mfront:55
       if (f > 0.0) {
         double dp;
         unsigned iters = 0;
         if constexpr (LAW == LAW_J2_LINEAR) {
-          dp = f / (lp.h1 + 3.0 * mu);                       // mfront:62-63
+          dp = f / (lp.h1 + 3.0 * mu);                        // mfront:62-63
         } else {
           // r(dp) = seq - 3 mu dp - R(p_n + dp) = 0, monotone Newton from dp = 0
           // tolerance relative to the larger of the yield stress and the trial stress the residual is made of
@@ -197,10 +197,10 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
           // rho = R(p) / seq of the returned state: <= 0 only for a yield stress that is not positive there (a softening law
           // driven to zero, an overshooting iterate).  The direction is then undefined (wn = 0 drops the n x n term): reported
           // as a point that did not converge, never silently.  Linear hardening can get there with H < 0 only: one scalar
-          // compare on the kernel's parameters keeps the per-lane test out of the H >= 0 launches (the headline)
+          // compare on the kernel's parameters keeps the per-lane test out of the H >= 0 launches (the headline); FIELDS: per
+          // lane where H is a stream
           if constexpr (LAW != LAW_J2_LINEAR) { if (valid && !(rho > 0.0)) ++c_notconv; }
-          // fields: per lane where H is a stream
-          else if (pf.p[PF_H1] ? lp.h1 < 0.0 : prm.h1 < 0.0) { if (valid && !(rho > 0.0)) ++c_notconv; }
+          else if ((FIELDS && pf.p[PF_H1]) ? lp.h1 < 0.0 : prm.h1 < 0.0) { if (valid && !(rho > 0.0)) ++c_notconv; }
         }
         const double gamma = 1.0 / (hardening_dR<LAW>(lp, p_n + dp) + 3.0 * mu);
         // Dt = lambda IxI + 2mu Id - 4mu^2 [beta (M - n^n) + gamma n^n]      mfront:66-69
@@ -222,12 +222,17 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
     // sigma = lambda tr(eel) 1 + 2 mu eel                                      mfront:76
     const double ltr = lambda * (e[0] + e[1] + e[2]);
     double s[6];
+    if constexpr (LAW == LAW_RAMBERG_OSGOOD) {
+      // no state: stress and tangent coefficients of the total strain
+      ramberg_osgood_update(prm, mu, e, stage2 + lane * 3, s, c1, c2, c3, wn, valid, c_plastic, c_notconv, c_maxit);
+    } else {
     s[0] = ltr + 2.0 * mu * e[0];
     s[1] = ltr + 2.0 * mu * e[1];
     s[2] = ltr + 2.0 * mu * e[2];
     s[3] = 2.0 * mu * e[3];
     s[4] = 2.0 * mu * e[4];
     s[5] = 2.0 * mu * e[5];
+    }
     {
       // stress, p and what the tangent is made of (quadrature_map.py:322-324 asserts on flux, state and Ct): a hardening
       // slope that is not finite at the returned state leaves the stress finite and c3 not
@@ -236,27 +241,24 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
     }
 
     // ---- 4. new state, SoA -------------------------------------------------------------------
-    if (valid) {
-      stream_store<1>(s1 + gi, p_new);
+    if constexpr (ss_has_state<LAW>) {
+      if (valid) {
+        stream_store<1>(s1 + gi, p_new);
 #pragma unroll
-      for (int c = 0; c < 6; ++c) stream_store<1>(s1 + (int64_t)(1 + c) * ld + gi, ep[c]);
+        for (int c = 0; c < 6; ++c) stream_store<1>(s1 + (int64_t)(1 + c) * ld + gi, ep[c]);
+      }
     }
 
     // ---- 5. stage stress and tangent coefficients in LDS --------------------------------------
     stage2[lane * 3 + 0] = double2_t{s[0], s[1]};
     stage2[lane * 3 + 1] = double2_t{s[2], s[3]};
     stage2[lane * 3 + 2] = double2_t{s[4], s[5]};
-    if constexpr (TL == TL_PACK4) {
+    if constexpr (ss_has_coef<LAW> && TL == TL_PACK4) {
       double2_t* c4 = reinterpret_cast<double2_t*>(coef) + lane * 2;
       c4[0] = double2_t{c1, c2};
       c4[1] = double2_t{c3, wn};
-    } else {
-      double* cf = coef + lane * 9;
-      cf[0] = c1; cf[1] = c2; cf[2] = c3;
-      // n = dev(sigma) wn, every operation individually rounded (the host rebuilds it with the same three lines)
-      const double third = opaque((s[0] + s[1] + s[2]) * SS_THIRD);
-      cf[3] = (s[0] - third) * wn; cf[4] = (s[1] - third) * wn; cf[5] = (s[2] - third) * wn;
-      cf[6] = s[3] * wn; cf[7] = s[4] * wn; cf[8] = s[5] * wn;
+    } else if constexpr (ss_has_coef<LAW>) {
+#include "small_strain_stage_coef.hpp"
     }
     wave_lds_sync();
 
@@ -273,6 +275,7 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
     }
     // ---- 7. coalesced tangent store: entry pair (i, j..j+1) of point q ---------------------------
     if constexpr (TL == TL_PACK4) {
+      static_assert(ss_has_coef<LAW>, "the elastic tangent is a constant: nothing to write");
       if (npts == WAVE) {   // 64 x 4 doubles: two 1 KiB wave stores
         double2_t* gct = reinterpret_cast<double2_t*>(ct + base * 4);
         const double2_t* c4 = reinterpret_cast<const double2_t*>(coef);
@@ -286,6 +289,7 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
       }
     } else if constexpr (TL == TL_COEF) {
       // the staged coefficients as they are: 64 x 9 doubles, contiguous (4.5 KiB per tile)
+      static_assert(ss_has_coef<LAW>, "the elastic tangent is a constant: nothing to write");
       if (npts == WAVE) {
         double2_t* gct = reinterpret_cast<double2_t*>(ct + base * 9);
         const double2_t* c2 = reinterpret_cast<const double2_t*>(coef);
@@ -310,7 +314,14 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
       // together, ahead of the arithmetic (groups of 3: larger groups spill at 128 VGPRs).
       double2_t* gct = reinterpret_cast<double2_t*>(ct + base * 36);
       auto entry = [&](int q, int i, int j) -> double2_t {
-        return tangent_pair(coef + q * 9, i, j);
+        double2_t v;
+        if constexpr (LAW == LAW_ELASTIC) {
+          v.x = ((i < 3 && j < 3) ? lambda : 0.0) + ((i == j) ? 2.0 * mu : 0.0);
+          v.y = ((i < 3 && j + 1 < 3) ? lambda : 0.0) + ((i == j + 1) ? 2.0 * mu : 0.0);
+        } else {
+          v = tangent_pair(coef + q * 9, i, j);
+        }
+        return v;
       };
       if (npts == WAVE) {
 #pragma unroll 1  // a fully unrolled loop gets its (loop-invariant) index arithmetic hoisted out of the
@@ -361,8 +372,14 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
           const int q = e / 21;
           const int t = e - q * 21;
           const int i = (int)((IP >> (3 * t)) & 7ull), j = (int)((JP >> (3 * t)) & 7ull);
-          const double* cf = coef + (q < WAVE ? q : 0) * 9;
-          v[u] = (((i < 3 && j < 3) ? cf[0] : 0.0) + ((i == j) ? cf[1] : 0.0)) + cf[2] * (cf[3 + i] * cf[3 + j]);
+          double x;
+          if constexpr (LAW == LAW_ELASTIC) {
+            x = ((i < 3 && j < 3) ? lambda : 0.0) + ((i == j) ? 2.0 * mu : 0.0);
+          } else {
+            const double* cf = coef + (q < WAVE ? q : 0) * 9;
+            x = (((i < 3 && j < 3) ? cf[0] : 0.0) + ((i == j) ? cf[1] : 0.0)) + cf[2] * (cf[3 + i] * cf[3 + j]);
+          }
+          v[u] = x;
         }
         if (e0 + 1 < lim) stream_store<0>(reinterpret_cast<double2_t*>(gct + e0), double2_t{v[0], v[1]});
         else if (e0 < lim) stream_store<0>(gct + e0, v[0]);
@@ -372,6 +389,3 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
   }
 
   store_block_stats(stats, c_plastic, c_notconv, c_nan, c_maxit, red);
-}
-
-}  // namespace dxm
