@@ -102,6 +102,15 @@ def flow(sig, a):
     return seq, n, dn
 
 
+def _deviatoric_stress(e, mu):
+    """2 mu dev(e): what the flow functions are evaluated on.  seq, n and dn/dsigma depend on the deviator alone; formed from the strain,
+    it carries no rounding of the hydrostatic part, which at nu -> 0.5 is far larger (kappa tr / R0 ~ 1e3 stalls the iteration at its
+    tolerance of 1e-14 R0 otherwise)."""
+    d = e.copy()
+    d[:, :3] -= d[:, :3].mean(axis=1, keepdims=True)
+    return 2 * mu * d
+
+
 def update(eps, ep_n, p_n, E, nu, R0, H, a, maxit=25, rtol=1e-14):
     """One implicit update of N points.  Returns a dict: sig (N, 6), eel (N, 6), ep (N, 6), p (N,), Ct (N, 6, 6), plastic (N,) bool,
     iters (N,), converged (N,) bool, f_trial (N,)."""
@@ -110,8 +119,7 @@ def update(eps, ep_n, p_n, E, nu, R0, H, a, maxit=25, rtol=1e-14):
     lam, mu = lame(E, nu)
     D = elastic_matrix(E, nu)
     e = eps - ep_n
-    sig_tr = e @ D
-    seq_tr = flow(sig_tr, a)[0] if N else np.zeros(0)
+    seq_tr = flow(_deviatoric_stress(e, mu), a)[0] if N else np.zeros(0)
     f_tr = seq_tr - (R0 + H * p_n)
     plastic = f_tr > 0
     eel, dp = e.copy(), np.zeros(N)
@@ -129,8 +137,7 @@ def update(eps, ep_n, p_n, E, nu, R0, H, a, maxit=25, rtol=1e-14):
         Jinv = np.zeros((idx.size, 7, 7))
         while not done.all():
             act = np.flatnonzero(~done)
-            sig = x_e[act] @ D
-            seq, n, dn = flow(sig, a)
+            seq, n, dn = flow(_deviatoric_stress(x_e[act], mu), a)
             r_e = x_e[act] - et[act] + x_p[act, None] * n
             r_p = seq - R0 - H * (pn[act] + x_p[act])
             J = np.zeros((act.size, 7, 7))
@@ -160,8 +167,9 @@ def update(eps, ep_n, p_n, E, nu, R0, H, a, maxit=25, rtol=1e-14):
 
 
 # ---- 50-digit version ------------------------------------------------------------------------------------------------------------
-def _mp_stress(mp, e6, pn, E, nu, R0, H, a):
-    """(sig (6), dp) of one trial elastic strain e6 (list of mpf, Mandel)."""
+def _mp_stress(mp, e6, pn, E, nu, R0, H, a, principal=False):
+    """(sig (6), dp, f_trial) of one trial elastic strain e6 (list of mpf, Mandel); ``principal``: also (s, w, Q), the principal deviatoric
+    stresses, the eigenvalues of the trial strain and their eigenvectors."""
     lam = E * nu / (1 + nu) / (1 - 2 * nu)
     mu = E / 2 / (1 + nu)
     r2 = mp.sqrt(2)
@@ -197,12 +205,59 @@ def _mp_stress(mp, e6, pn, E, nu, R0, H, a):
     S = mp.zeros(3, 3)
     for i in range(3):
         S += (s[i] + kap * tr) * (Q[:, i] * Q[:, i].T)
-    return [S[0, 0], S[1, 1], S[2, 2], r2 * S[0, 1], r2 * S[0, 2], r2 * S[1, 2]], dp, f
+    sig = [S[0, 0], S[1, 1], S[2, 2], r2 * S[0, 1], r2 * S[0, 2], r2 * S[1, 2]]
+    return (sig, dp, f, s, w, Q) if principal else (sig, dp, f)
 
 
-def update_mp(eps, ep_n, p_n, E, nu, R0, H, a, tangent=True, dps=50):
-    """The update of ONE point in 50-digit arithmetic; returns float64 arrays sig (6), eel (6), p, Ct (6, 6) (central differences of the
-    50-digit stress, relative step 1e-20) and plastic."""
+def _mp_tangent_analytic(mp, e6, pn, E, nu, R0, H, a):
+    """The consistent tangent (6 x 6 mpmath matrix) from the derivative formulas, evaluated at the 50-digit solution -- no differences:
+    principal block lambda 1x1 + 2 mu A^-1 - 4 mu^2 z z^T / (2 mu n.z + H), A = I + 2 mu dp dn/ds, z = A^-1 n; shear moduli
+    (s_i - s_j) / (2 mu (w_i - w_j)) 2 mu, at exactly repeated trial eigenvalues their limit 2 mu / (1 + 2 mu dp (dn_ii - dn_ij))."""
+    lam = E * nu / (1 + nu) / (1 - 2 * nu)
+    mu = E / 2 / (1 + nu)
+    sig, dp, f, s, w, Q = _mp_stress(mp, e6, pn, E, nu, R0, H, a, principal=True)
+    one = mp.matrix([1, 1, 1])
+    if f <= 0:
+        P, th = lam * one * one.T + 2 * mu * mp.eye(3), {k: 2 * mu for k in ((0, 1), (0, 2), (1, 2))}
+    else:
+        d = [s[0] - s[1], s[1] - s[2], s[0] - s[2]]
+        dm = max(abs(x) for x in d)
+        q = dm * (sum((abs(x) / dm) ** a for x in d) / 2) ** (1 / a)
+        r = [abs(x) / q for x in d]
+        g = mp.matrix([mp.sign(x) * y ** (a - 1) / 2 for x, y in zip(d, r)])
+        h = mp.diag([(y ** (a - 2) if y > 0 else mp.mpf(1 if a == 2 else 0)) / 2 for y in r])
+        B = mp.matrix([[1, -1, 0], [0, 1, -1], [1, 0, -1]])
+        n = B.T * g
+        dn = (a - 1) / q * (B.T * h * B - n * n.T)
+        Ai = (mp.eye(3) + 2 * mu * dp * dn) ** -1
+        z = Ai * n
+        P = lam * one * one.T + 2 * mu * Ai - 4 * mu * mu * z * z.T / (2 * mu * (n.T * z)[0] + H)
+        th = {(i, j): (s[i] - s[j]) / (w[i] - w[j]) if w[i] != w[j] else 2 * mu / (1 + 2 * mu * dp * (dn[i, i] - dn[i, j])) for i, j in ((0, 1), (0, 2), (1, 2))}
+    r2 = mp.sqrt(2)
+    mandel = lambda T: mp.matrix([T[0, 0], T[1, 1], T[2, 2], r2 * T[0, 1], r2 * T[0, 2], r2 * T[1, 2]])   # noqa: E731
+    Ev = [mandel(Q[:, i] * Q[:, i].T) for i in range(3)]
+    Ct = mp.zeros(6, 6)
+    for i in range(3):
+        for j in range(3):
+            Ct += P[i, j] * Ev[i] * Ev[j].T
+    for (i, j), t in th.items():
+        M = mandel((Q[:, i] * Q[:, j].T + Q[:, j] * Q[:, i].T) / r2)
+        Ct += t * M * M.T
+    return Ct
+
+
+def update_mp(eps, ep_n, p_n, E, nu, R0, H, a, tangent=True, dps=50, rel_step=1e-20):
+    """The update of ONE point in 50-digit arithmetic; returns float64 arrays sig (6), eel (6), p, Ct (6, 6) and plastic.  ``tangent``:
+    True for central differences of the 50-digit stress with the relative step ``rel_step``, "analytic" for the derivative formulas
+    evaluated at the 50-digit solution (:func:`_mp_tangent_analytic`).
+
+    Where the differences stop being trusted: for an exponent 2 < a < 3 at a trial state with exactly repeated eigenvalues (uniaxial
+    loading).  The tangent is continuous there but only Hoelder continuous -- dn/ds carries |s_i - s_j|^(a-2) -- so a central
+    difference of step h is off by O(h^(a-2)): at a = 2.5, 3e-11 of the tangent with the default step and 3e-7 with 1e-12, while
+    ``update`` agrees with the analytic 50-digit tangent to 1e-15.  Next to such a state (a relative gap of 1e-12) it is the other way
+    round: the differences are exact, and every float64 evaluation, ``update`` included, is off by about (a - 2) gap^(a-3) x the
+    rounding of the gap, 7e-11 there (``test_law_fuzz_cpu.py::test_hosford_tangent_between_exponents_2_and_3``).  For a = 2 and a >= 3 the
+    default step is good to better than 1e-14 everywhere."""
     import mpmath
 
     mp = mpmath.mp
@@ -218,9 +273,12 @@ def update_mp(eps, ep_n, p_n, E, nu, R0, H, a, tangent=True, dps=50):
         trs = sig[0] + sig[1] + sig[2]
         eel = [(sig[i] - trs / 3) / (2 * mu) + trs / (3 * (3 * lam + 2 * mu)) if i < 3 else sig[i] / (2 * mu) for i in range(6)]
         Ct = np.zeros((6, 6))
-        if tangent:
+        if tangent == "analytic":
+            Cm = _mp_tangent_analytic(mp, e, pn, E, nu, R0, H, a)
+            Ct = np.array([[float(Cm[i, j]) for j in range(6)] for i in range(6)])
+        elif tangent:
             scale = max(abs(x) for x in e) or mp.mpf(1)
-            hstep = scale * mp.mpf(10) ** (-20)
+            hstep = scale * mp.mpf(float(rel_step))
             for j in range(6):
                 ep_, em_ = list(e), list(e)
                 ep_[j] += hstep
@@ -290,9 +348,9 @@ def make_inputs(cls, n, a, seed, E=PROPS["E"], nu=PROPS["nu"], R0=PROPS["R0"], H
     return ep_n + e, ep_n, p_n
 
 
-def mixed_inputs(n, a, seed, trivial_state=False):
-    """n points cycling through every class (what the GPU parity tests run)."""
-    per = [make_inputs(c, (n + len(CLASSES) - 1 - k) // len(CLASSES), a, seed + 17 * k, trivial_state=trivial_state) for k, c in enumerate(CLASSES)]
+def mixed_inputs(n, a, seed, trivial_state=False, **props):
+    """n points cycling through every class (what the GPU parity tests run); ``props``: E, nu, R0, H other than ``PROPS``."""
+    per = [make_inputs(c, (n + len(CLASSES) - 1 - k) // len(CLASSES), a, seed + 17 * k, trivial_state=trivial_state, **props) for k, c in enumerate(CLASSES)]
     eps, ep, p = (np.concatenate([x[i] for x in per]) for i in range(3))
     perm = np.random.default_rng(seed + 999).permutation(eps.shape[0])
     return eps[perm], ep[perm], p[perm]

@@ -31,8 +31,8 @@ def behaviour(a, **over):
     return jm.HosfordIsotropicHardening(jm.LinearElasticIsotropic(E=p["E"], nu=p["nu"]), jm.LinearHardening(p["R0"], p["H"]), a=a)
 
 
-def material(a, n, ep=None, p=None, **kw):
-    m = JAXMaterial(behaviour(a), lazy_isv=False, **kw)
+def material(a, n, ep=None, p=None, props=None, **kw):
+    m = JAXMaterial(behaviour(a, **(props or {})), lazy_isv=False, **kw)
     m.set_data_manager(n)
     if ep is not None:
         # a non-trivial initial state: eps_n = eps_p,n (no elastic strain), so that the hidden plastic strain is eps_p,n
@@ -40,18 +40,22 @@ def material(a, n, ep=None, p=None, **kw):
     return m
 
 
-def compare(tag, sig, isv, Ct, ref):
+def compare(tag, sig, isv, Ct, ref, props=None, b_state=B_STATE, b_tangent=B_TANGENT):
+    """Row-scaled deviations of (sig, isv, Ct) from ``ref`` against the bounds; ``props``: the material's E and R0 if not ``PROPS``.
+    Returns the four figures."""
+    props = props or P
     n = ref["sig"].shape[0]
     if n == 0:
-        return
-    sc = np.maximum(np.abs(ref["sig"]).max(axis=1), P["R0"])
+        return 0.0, 0.0, 0.0, 0.0
+    sc = np.maximum(np.abs(ref["sig"]).max(axis=1), props["R0"])
     es = (np.abs(np.asarray(sig) - ref["sig"]).max(axis=1) / sc).max()
-    ee = (P["E"] * np.abs(np.asarray(isv)[:, :6] - ref["eel"]).max(axis=1) / sc).max()
-    ep = (P["E"] * np.abs(np.asarray(isv)[:, 6] - ref["p"]) / sc).max()
+    ee = (props["E"] * np.abs(np.asarray(isv)[:, :6] - ref["eel"]).max(axis=1) / sc).max()
+    ep = (props["E"] * np.abs(np.asarray(isv)[:, 6] - ref["p"]) / sc).max()
     ct = np.asarray(Ct).reshape(n, 36)
     ec = (np.abs(ct - ref["Ct"].reshape(n, 36)).max(axis=1) / np.abs(ref["Ct"]).reshape(n, 36).max(axis=1)).max()
-    print(f"hosford parity {tag}: stress {es:.3e} eel {ee:.3e} p {ep:.3e} (bound {B_STATE:.2e})  tangent {ec:.3e} (bound {B_TANGENT:.2e})")
-    assert es <= B_STATE and ee <= B_STATE and ep <= B_STATE and ec <= B_TANGENT, (es, ee, ep, ec)
+    print(f"hosford parity {tag}: stress {es:.3e} eel {ee:.3e} p {ep:.3e} (bound {b_state:.2e})  tangent {ec:.3e} (bound {b_tangent:.2e})")
+    assert es <= b_state and ee <= b_state and ep <= b_state and ec <= b_tangent, (tag, es, ee, ep, ec)
+    return es, ee, ep, ec
 
 
 def check_stats(st, ref):

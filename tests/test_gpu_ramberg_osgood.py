@@ -13,6 +13,7 @@ from dolfinx_materials_amd.jaxmat import JAXMaterial
 
 import ramberg_osgood_ref as ro
 from helpers import to_device, to_host
+from law_fuzz import ramberg_osgood_strains as strains
 from test_ramberg_osgood_cpu import ALPHA, E, N_EXP, NU, PRM, SIG0, close, load_curves
 
 pytestmark = pytest.mark.gpu
@@ -24,35 +25,16 @@ def behavior(n=N_EXP, alpha=ALPHA, sig0=SIG0):
     return jm.RambergOsgoodNonLinearElasticity(jm.LinearElasticIsotropic(E=E, nu=NU), sig0=sig0, alpha=alpha, n=n)
 
 
-def strains(N, seed):
-    """eps_e log-uniform over 1e-14 ... 3e-1 with a volumetric part, plus zero rows, purely volumetric rows and rows just
-    below and above the threshold e_eps = 1e-12."""
-    rng = np.random.default_rng(seed)
-    d = rng.standard_normal((N, 6))
-    d[:, :3] -= d[:, :3].mean(axis=1, keepdims=True)
-    d /= np.linalg.norm(d, axis=1, keepdims=True) * np.sqrt(2.0 / 3.0)
-    ee = np.exp(rng.uniform(np.log(1e-14), np.log(3e-1), N))
-    eps = d * ee[:, None]
-    eps[:, :3] += (ee * rng.uniform(-1.0, 1.0, N))[:, None]
-    k = rng.integers(0, 6, N)
-    eps[k == 0] = 0.0                                         # zero rows
-    vol = k == 1
-    eps[vol] = 0.0
-    eps[vol, :3] = rng.uniform(-1e-2, 1e-2, vol.sum())[:, None]   # purely volumetric
-    near = k == 2
-    eps[near] = d[near] * rng.choice([0.5e-12, 0.9e-12, 1.1e-12, 2e-12], near.sum())[:, None]
-    return eps
-
-
-def check_against_ref(sig, ct, eps, prm, stats, **kw):
+def check_against_ref(sig, ct, eps, prm, stats, tag="", **kw):
+    """``tag``: what a failure should name next to its figure (a sweep's drawn parameters)."""
     r = ro.update(eps, *prm, **kw)
     srow = np.maximum(np.abs(r["sig"]).max(axis=1), 1e-300)
-    assert np.all(np.abs(sig - r["sig"]).max(axis=1) <= 1e-12 * srow), float((np.abs(sig - r["sig"]).max(axis=1) / srow).max())
+    assert np.all(np.abs(sig - r["sig"]).max(axis=1) <= 1e-12 * srow), (tag, float((np.abs(sig - r["sig"]).max(axis=1) / srow).max()))
     cscale = np.abs(r["Ct_mfront"]).max(axis=(1, 2))
     ct = np.asarray(ct).reshape(-1, 6, 6)
     err = np.abs(ct - r["Ct_mfront"]).max(axis=(1, 2)) / cscale
-    assert err.max() <= 1e-11, float(err.max())
-    assert stats["n_plastic"] == int(r["newton"].sum()) and stats["n_nan"] == 0
+    assert err.max() <= 1e-11, (tag, float(err.max()))
+    assert stats["n_plastic"] == int(r["newton"].sum()) and stats["n_nan"] == 0, (tag, stats)
     return r
 
 
