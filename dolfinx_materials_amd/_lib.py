@@ -18,6 +18,7 @@ LAW_ELASTIC_ISO, LAW_J2_LINEAR, LAW_J2_VOCE, LAW_FEFP_J2_VOCE, LAW_FEFP_J2_LINEA
 LAW_RAMBERG_OSGOOD = 5
 LAW_OGDEN = 7   # (6 is not assigned)
 LAW_HOSFORD_LINEAR = 10   # (8 and 9 are not assigned)
+LAW_ORTHOTROPIC_ELASTIC = 12   # (11 is not assigned)
 S0, S1 = 0, 1
 
 
@@ -77,6 +78,10 @@ SYMBOLS = {
     "dxm_set_param_field": (C.c_int, [_h, C.c_int, C.c_void_p]),
     "dxm_set_param_field_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_void_p]),
     "dxm_param_field_mask": (C.c_int, [_h]),
+    "dxm_set_frame": (C.c_int, [_h, C.c_void_p]),
+    "dxm_set_frame_field": (C.c_int, [_h, C.c_void_p]),
+    "dxm_set_frame_field_device": (C.c_int, [_h, C.c_void_p, C.c_void_p]),
+    "dxm_frame_kind": (C.c_int, [_h]),
     "dxm_algorithmic_bytes": (C.c_int, [_h]),
     "dxm_set_newton": (C.c_int, [_h, C.c_int, C.c_double]),
     "dxm_set_tangent_layout": (C.c_int, [_h, C.c_int]),

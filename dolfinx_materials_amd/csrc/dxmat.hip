@@ -32,6 +32,7 @@
 #include "param_fields.hpp"
 #include "hyperelastic.hpp"
 #include "hosford.hpp"
+#include "orthotropic.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -141,6 +142,8 @@ struct LawDesc {
   unsigned launch_layouts;                // layouts a launch may be asked for: the host path also asks for records it expands itself
   const char* launch_refusal;
   const char* no_fused;                   // null: the kernel can evaluate the displacement gradient itself; else the refusal
+  const char* no_frame;                   // null: the kernel reads a material frame (dxm_set_frame*); else the refusal
+  const char* frame_kernel[2];            // the kernel while a uniform frame / a frame field is bound
   void (*launch)(const LaunchArgs& a);    // null: not launchable in this build
 };
 
@@ -237,6 +240,36 @@ static int build_hosford(const double* p, LawParams& q) {
   return 0;
 }
 
+// [E1, E2, E3, nu12, nu23, nu13, G12, G23, G13]: the 3x3 normal block of the stiffness is the inverse of the compliance block
+// (closed-form adjugate, every operation individually rounded: tests restate it), the shear diagonal is 2 G in Mandel order
+static int build_orthotropic(const double* p, LawParams& q) {
+#pragma clang fp contract(off)
+  static const char* const names[9] = {"E1", "E2", "E3", "nu12", "nu23", "nu13", "G12", "G23", "G13"};
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "orthotropic elasticity: %s must be finite, got %g", names[k], p[k]);
+  for (int k : {0, 1, 2, 6, 7, 8})
+    if (!(p[k] > 0.0)) return fail(-1, "orthotropic elasticity: %s must be > 0, got %g", names[k], p[k]);
+  const double E1 = p[0], E2 = p[1], E3 = p[2], nu12 = p[3], nu23 = p[4], nu13 = p[5], G12 = p[6], G23 = p[7], G13 = p[8];
+  const double s11 = 1.0 / E1, s22 = 1.0 / E2, s33 = 1.0 / E3, s12 = -nu12 / E1, s13 = -nu13 / E1, s23 = -nu23 / E2;
+  // positive definite: the leading minors, scaled to 1 - nu12^2 E2 / E1 > 0 and det(S) E1 E2 E3 > 0
+  const double m2 = 1.0 - nu12 * nu12 * E2 / E1;
+  if (!(m2 > 0.0)) return fail(-1, "orthotropic elasticity: the compliance is not positive definite: 1 - nu12^2 E2/E1 = %g (nu12 = %g)", m2, nu12);
+  const double c11 = s22 * s33 - s23 * s23, c12 = s13 * s23 - s12 * s33, c13 = s12 * s23 - s13 * s22;
+  const double c22 = s11 * s33 - s13 * s13, c23 = s12 * s13 - s11 * s23, c33 = s11 * s22 - s12 * s12;
+  const double det = s11 * c11 + s12 * c12 + s13 * c13;
+  const double m3 = det * E1 * E2 * E3;
+  if (!(m3 > 0.0) || !std::isfinite(m3))
+    return fail(-1, "orthotropic elasticity: the compliance is not positive definite: det(S) E1 E2 E3 = %g (nu12 = %g, nu23 = %g, nu13 = %g)", m3, nu12, nu23, nu13);
+  OrthoStiffness s{};
+  s.c[0] = c11 / det; s.c[1] = s.c[3] = c12 / det; s.c[2] = s.c[6] = c13 / det;
+  s.c[4] = c22 / det; s.c[5] = s.c[7] = c23 / det; s.c[8] = c33 / det;
+  s.g2[0] = 2.0 * G12; s.g2[1] = 2.0 * G13; s.g2[2] = 2.0 * G23;
+  for (double v : s.c)
+    if (!std::isfinite(v)) return fail(-1, "orthotropic elasticity: the stiffness is not finite (%g): the compliance is singular to working precision", v);
+  ortho_store(q, s);
+  return 0;
+}
+
 // ---- launchers (defined in the launch section, where the handle is complete) ----
 template <int LAW> static void launch_small_strain(const LaunchArgs& a);
 static void launch_fefp_voce(const LaunchArgs& a);
@@ -244,6 +277,7 @@ static void launch_fefp_linear(const LaunchArgs& a);
 static void launch_ramberg_osgood(const LaunchArgs& a);
 static void launch_ogden(const LaunchArgs& a);
 static void launch_hosford(const LaunchArgs& a);
+static void launch_orthotropic(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -263,6 +297,10 @@ static void launch_hosford(const LaunchArgs& a);
 // it -- Voce +3 %, FeFp +2.5 % over the persistent grids above at 1e7 points (profiles/archive/r03_grid_size_by_law.txt); the
 // linear-hardening kernel, whose tiles all cost the same, loses 2.5 % with it and keeps 32.
 
+// what every isotropic law answers dxm_set_frame* with
+constexpr const char* kNoFrame = "this law is isotropic: a material frame changes nothing in its update, and accepting one would hide a "
+                                 "mistake of the caller (frames are read by DXM_LAW_ORTHOTROPIC_ELASTIC)";
+
 constexpr void state_field(LawDesc& d, int f, const char* name, int dim, int slot) {
   d.isv_name[f] = name; d.isv_dim[f] = dim; d.isv_slot[f] = slot;
 }
@@ -276,6 +314,7 @@ constexpr LawDesc small_strain_law(int id, int n_params, int alg_bytes, const ch
   d.alg_bytes = alg_bytes;
   d.kernel = kernel;
   d.set_layouts = d.launch_layouts = coef ? L_ALL : L_FULL | L_SYM;
+  d.no_frame = kNoFrame;
   d.launch = launch;
   return d;
 }
@@ -357,6 +396,7 @@ constexpr LawDesc law_fefp(int id, bool voce) {
   d.set_layouts = L_FULL;
   d.launch_layouts = L_FULL | L_COEF;
   d.set_refusal = d.launch_refusal = "the FeFp tangent dP/dF is not symmetric: only DXM_TANGENT_FULL is available";
+  d.no_frame = kNoFrame;
   d.launch = voce ? launch_fefp_voce : launch_fefp_linear;
   return d;
 }
@@ -382,6 +422,7 @@ constexpr LawDesc law_ogden() {
   d.launch_refusal = "the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record exists for this law";
   d.no_fused = "the Ogden kernel has no fused displacement-gradient form: set option fused_gradient to 0 (F is then evaluated "
                "by the gradient kernel) or pass F as an array";
+  d.no_frame = kNoFrame;
   d.launch = DXM_STOCK_ONLY(launch_ogden);   // hyperelastic.hip: F from the (N, 9) array, the full tangent
   return d;
 }
@@ -412,14 +453,41 @@ constexpr LawDesc law_hosford() {
   d.launch_refusal = "the Hosford tangent is a general symmetric 6x6: no coefficient record (coef / pack4) exists for this law";
   d.no_fused = "the Hosford kernel has no fused displacement-gradient form: set option fused_gradient to 0 (the strain is then "
                "evaluated by the gradient kernel) or pass the strain as an array";
+  d.no_frame = kNoFrame;
   d.launch = DXM_STOCK_ONLY(launch_hosford);   // hosford.hip: strain from the (N, 6) array, the full block or its upper triangle
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8 and 9 are not assigned and stay empty rows (law_known)
+// Orthotropic elasticity: strain in (48 B), stress (48) + tangent (288) out, no state; a frame field adds nine 8 B streams
+// (dxm_algorithmic_bytes)
+constexpr LawDesc law_orthotropic() {
+  LawDesc d{};
+  d.id = DXM_LAW_ORTHOTROPIC_ELASTIC;
+  d.n_grad = d.n_flux = 6;
+  d.n_params = d.n_params_custom = 9;
+  d.alg_bytes = 384;
+  d.kernel = "orthotropic_kernel<0";
+  d.frame_kernel[0] = "orthotropic_kernel<1";
+  d.frame_kernel[1] = "orthotropic_kernel<2";
+  d.no_fields = "per-point stiffness fields are not served for orthotropic elasticity: the host inverts the compliance once per handle";
+  d.build = build_orthotropic;
+  d.stock_only = "orthotropic elasticity has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(orthotropic_kernel_fn);
+  d.blocks_per_cu = OR_BLOCKS_PER_CU;   // orthotropic.hpp
+  d.set_layouts = d.launch_layouts = L_FULL | L_SYM;
+  d.set_refusal = "the orthotropic tangent Q^T C Q is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no "
+                  "coefficients (coef / pack4); DXM_TANGENT_FULL and DXM_TANGENT_SYM are available";
+  d.launch_refusal = "the orthotropic tangent is a general symmetric 6x6: no coefficient record (coef / pack4) exists for this law";
+  d.no_fused = "the orthotropic kernel has no fused displacement-gradient form: set option fused_gradient to 0 (the strain is then "
+               "evaluated by the gradient kernel) or pass the strain as an array";
+  d.launch = DXM_STOCK_ONLY(launch_orthotropic);   // orthotropic.hip: strain from the (N, 6) array, the handle's frame
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9 and 11 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
-    law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(),
+    law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(),
 };
 
 constexpr bool rows_in_place() {
@@ -428,7 +496,7 @@ constexpr bool rows_in_place() {
   return true;
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
-static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel, "ids 6, 8 and 9 are not assigned");
+static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel, "ids 6, 8, 9 and 11 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -544,6 +612,10 @@ struct dxm_material {
   int pf_mask = 0;
   double* pf_law[2] = {nullptr, nullptr};   // device copies of the E / nu fields, n doubles each
   double* pf_stream[PF_COUNT] = {};         // device streams (lambda, mu, sig0, h1, h2), n doubles each; null = uniform
+  // material frame (dxm_set_frame*; the laws whose row has no `no_frame`): 0 none (identity), 1 uniform, 2 one per Gauss point
+  int frame_kind = 0;
+  Frame9 frame_uniform{};
+  double* frame_streams = nullptr;          // the field as nine SoA streams of ld doubles each (the kernel reads 8 B per lane)
 };
 
 static int sync_last(dxm_material* m);
@@ -767,6 +839,7 @@ int dxm_destroy(dxm_material* m) {
   if (m->h_grad_ring) (void)hipHostFree(m->h_grad_ring);
   for (double* q : m->pf_law) if (q) (void)hipFree(q);
   for (double* q : m->pf_stream) if (q) (void)hipFree(q);
+  if (m->frame_streams) (void)hipFree(m->frame_streams);
   for (hipEvent_t e : m->ring_done) if (e) (void)hipEventDestroy(e);
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
   if (m->pipe_stream) (void)hipStreamDestroy(m->pipe_stream);
@@ -1155,6 +1228,13 @@ static void launch_hosford(const LaunchArgs& a) {
   dxm_material* m = a.m;
   hosford_launch(a.tl, a.grid, a.st, m->prm, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
                  m->d_stats + a.stats_off);
+}
+
+static void launch_orthotropic(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  // the frame streams advance with the range like the state slots
+  orthotropic_launch(m->frame_kind, a.tl, a.grid, a.st, m->prm, a.cnt, a.grad, m->frame_uniform,
+                     m->frame_streams ? m->frame_streams + a.off : nullptr, m->ld, a.flux, a.ct, m->d_stats + a.stats_off);
 }
 #endif
 
@@ -1958,6 +2038,7 @@ const double* dxm_state_ptr(const dxm_material* m, int which, int field, int com
 
 const char* dxm_kernel_name(const dxm_material* m) {
   if (!m) return "";
+  if (m->frame_kind) return kLaws[m->law].frame_kernel[m->frame_kind - 1];
   return m->pf_mask ? kLaws[m->law].field_kernel : kLaws[m->law].kernel;
 }
 
@@ -2108,10 +2189,125 @@ int dxm_set_param_field_device(dxm_material* m, int param_index, const double* d
 
 int dxm_param_field_mask(const dxm_material* m) { return m ? m->pf_mask : -1; }
 
+// ---- material frames -----------------------------------------------------------------------------------
+static int frame_check(const dxm_material* m) {
+  if (!m) return fail(-1, "null handle");
+  const LawDesc& d = kLaws[m->law];
+  if (d.no_frame) return fail(-1, "law %d takes no material frame: %s", m->law, d.no_frame);
+  return 0;
+}
+
+// finite and orthonormal: max |R R^T - I| <= 1e-8
+static int frame_valid(const double* r, long long point) {
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(r[k])) {
+      if (point < 0) return fail(-1, "the frame is not finite (entry %d is %g)", k, r[k]);
+      return fail(-1, "the frame of point %lld is not finite (entry %d is %g)", point, k, r[k]);
+    }
+  double worst = 0.0;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double v = r[3 * i] * r[3 * j] + r[3 * i + 1] * r[3 * j + 1] + r[3 * i + 2] * r[3 * j + 2] - (i == j ? 1.0 : 0.0);
+      worst = std::max(worst, std::fabs(v));
+    }
+  if (worst <= 1e-8) return 0;
+  if (point < 0) return fail(-1, "the frame is not orthonormal: max |R R^T - I| = %g (allowed 1e-8)", worst);
+  return fail(-1, "the frame of point %lld is not orthonormal: max |R R^T - I| = %g (allowed 1e-8)", point, worst);
+}
+
+static int frame_reserve(dxm_material* m) {
+  if (m->frame_streams) return 0;
+  if (hipMalloc(&m->frame_streams, sizeof(double) * 9 * (size_t)m->ld) != hipSuccess) {
+    (void)hipGetLastError();
+    m->frame_streams = nullptr;
+    return fail(-3, "hipMalloc of the %zu-byte frame streams failed", sizeof(double) * 9 * (size_t)m->ld);
+  }
+  return 0;
+}
+
+// the field is dropped (the launch before must be complete: the streams are freed)
+static int frame_release(dxm_material* m) {
+  if (!m->frame_streams) return 0;
+  double* q = m->frame_streams;
+  m->frame_streams = nullptr;
+  HIP_TRY(hipFree(q));
+  return 0;
+}
+
+int dxm_set_frame(dxm_material* m, const double* r9) {
+  if (int rc = frame_check(m)) return rc;
+  if (r9)
+    if (int rc = frame_valid(r9, -1)) return rc;
+  DEVICE_GUARD(m);
+  if (int rc = sync_last(m)) return rc;
+  if (int rc = frame_release(m)) return rc;
+  m->frame_kind = r9 ? 1 : 0;
+  if (r9) memcpy(m->frame_uniform.r, r9, sizeof(m->frame_uniform.r));
+  ++m->epoch;
+  return 0;
+}
+
+int dxm_set_frame_field(dxm_material* m, const double* host_aos) {
+  if (int rc = frame_check(m)) return rc;
+  DEVICE_GUARD(m);
+  if (int rc = sync_last(m)) return rc;
+  if (!host_aos) {
+    if (m->frame_kind != 2) return 0;
+    if (int rc = frame_release(m)) return rc;
+    m->frame_kind = 0;
+    ++m->epoch;
+    return 0;
+  }
+  for (int64_t i = 0; i < m->n; ++i)
+    if (int rc = frame_valid(host_aos + 9 * i, (long long)i)) return rc;
+#ifndef DXM_CUSTOM_HARDENING
+  if (int rc = frame_reserve(m)) return rc;
+  if (m->n > 0) {
+    // the (n, 9) rows go up as they are and are transposed into the streams on the device, once
+    double* aos = nullptr;
+    HIP_TRY(hipMalloc(&aos, sizeof(double) * 9 * (size_t)m->n));
+    int rc = upload_from_host(aos, host_aos, sizeof(double) * 9 * (size_t)m->n, m->own_stream);
+    if (rc == 0) {
+      orthotropic_frames_to_streams(m->n, aos, m->frame_streams, m->ld, m->own_stream);
+      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(m->own_stream) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = fail(-2, "transposing the frame field on the device failed");
+      }
+    }
+    (void)hipFree(aos);
+    if (rc) return rc;
+  }
+#endif
+  m->frame_kind = 2;
+  ++m->epoch;
+  return 0;
+}
+
+int dxm_set_frame_field_device(dxm_material* m, const double* dev_aos, void* hip_stream) {
+  if (int rc = frame_check(m)) return rc;
+  if (!dev_aos) return dxm_set_frame_field(m, nullptr);
+  DEVICE_GUARD(m);
+  hipStream_t st = (hipStream_t)hip_stream;
+  // the last launch may still read the streams from another stream: this one waits for it, the host does not
+  if (m->launched && m->last_event_recorded) HIP_TRY(hipStreamWaitEvent(st, m->last_event, 0));
+  else if (int rc = sync_last(m)) return rc;
+#ifndef DXM_CUSTOM_HARDENING
+  if (int rc = frame_reserve(m)) return rc;
+  orthotropic_frames_to_streams(m->n, dev_aos, m->frame_streams, m->ld, st);
+  HIP_TRY(hipGetLastError());
+#endif
+  m->frame_kind = 2;
+  ++m->epoch;
+  return 0;
+}
+
+int dxm_frame_kind(const dxm_material* m) { return m ? m->frame_kind : -1; }
+
 int dxm_algorithmic_bytes(const dxm_material* m) {
   if (!m) return -1;
   int bytes = kLaws[m->law].alg_bytes;
   for (const double* q : m->pf_stream) if (q) bytes += 8;
+  if (m->frame_kind == 2) bytes += 9 * 8;   // the nine frame streams
   return bytes;
 }
 

@@ -402,7 +402,8 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   const bool plain81 = r.law == DXM_LAW_OGDEN;
   // Hosford: a general symmetric 6x6 with no coefficient form.  A full-layout handle's packed transfer is the kernel's 21
   // upper-triangle entries (168 instead of 288 B/point), mirrored into the block by the workers; a "sym" handle downloads its 21
-  const bool gsym = r.law == DXM_LAW_HOSFORD_LINEAR;
+  // orthotropic elasticity: the same (Q^T C Q is a general symmetric 6x6 per point)
+  const bool gsym = r.law == DXM_LAW_HOSFORD_LINEAR || r.law == DXM_LAW_ORTHOTROPIC_ELASTIC;
   const bool fefp = r.n_grad == 9 && !plain81, elastic = r.law == DXM_LAW_ELASTIC_ISO;
   int total = 0;
   for (int f = 0; f < r.n_isv_fields; ++f) total += r.isv_dim[f];

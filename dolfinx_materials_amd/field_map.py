@@ -162,9 +162,12 @@ class FieldMapBase:
         self._accel_jacobian_layout = layout
         self.internal_state_variables = {name: Field(name, dim, total) for name, dim in material.internal_state_variables.items()}
         self.gradients, self.external_state_variables = {}, {}
-        self.rotation_func = None
+        self.rotation_func = Field("rotation", 9, total)   # quadrature_map.py:123-124: a (3, 3) quadrature Function, row-major
+        self.rotation_func.values[:] = np.eye(3).reshape(9)
         self.set_data_manager(self.cells)
         self._initialized = False
+        if getattr(material, "rotation_matrix", None) is not None:   # quadrature_map.py:125-126
+            self.update_material_rotation_matrix()
 
     def set_data_manager(self, cells):
         # rows of the fields this map owns, in the order the material sees them (quadrature_map.py:231-233, :259-260)
@@ -174,6 +177,19 @@ class FieldMapBase:
     @property
     def variables(self):
         return {**self.gradients, **self.fluxes, **self.internal_state_variables}
+
+    def update_material_rotation_matrix(self, value=None):
+        """``quadrature_map.py:227-229``: ``material.rotation_matrix`` (or ``value``) into ``rotation_func`` -- a constant 3x3, one
+        matrix per point of all cells ``(points, 3, 3)`` / ``(points, 9)``, or a callable of the cells that returns those rows
+        (what stands for a UFL expression here)."""
+        value = self.material.rotation_matrix if value is None else value
+        if value is None:
+            return
+        if callable(value):
+            value = value(np.arange(self.num_cells_total))
+        a = np.asarray(value, dtype=np.float64)
+        rows = self.rotation_func.values
+        rows[:] = a.reshape(9) if a.shape == (3, 3) else a.reshape(len(rows), 9)
 
     def register_gradient(self, name, evaluator):
         """``evaluator(cells) -> (len(cells) * nqp, dim)`` stands for the compiled UFL expression."""

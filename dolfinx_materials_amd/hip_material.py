@@ -113,6 +113,9 @@ class HIPMaterial:
         if tangent_layout in ("coef", "pack4") and getattr(behavior, "law", None) == _lib.LAW_HOSFORD_LINEAR:
             raise ValueError("the Hosford tangent is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no "
                              f"coefficients (tangent_layout={tangent_layout!r}); use 'full' or 'sym'")
+        if tangent_layout in ("coef", "pack4") and getattr(behavior, "law", None) == _lib.LAW_ORTHOTROPIC_ELASTIC:
+            raise ValueError("the orthotropic tangent Q^T C Q is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there "
+                             f"are no coefficients (tangent_layout={tangent_layout!r}); use 'full' or 'sym'")
         if not isinstance(jit, (bool, type(None))):
             raise TypeError("the second argument of JAXMaterial / HIPMaterial is `jit` (jaxmat.py:144); pass the GPU index as device=")
         self.jit = bool(jit)
@@ -144,6 +147,8 @@ class HIPMaterial:
         self.last_upload = None
         self.dt = 0.0
         self._warm = False
+        self._rotation = None     # what rotation_matrix was set to (frame_fused materials only)
+        self._frame = None        # the frames last handed to the handles: (3, 3) or (N, 9)
 
     def _chk(self, rc):
         return _lib.check(rc, self._lib)
@@ -154,8 +159,98 @@ class HIPMaterial:
         return self.behavior.__class__.__name__
 
     @property
+    def frame_fused(self):
+        """Whether the law rotates into a material frame inside its kernel (orthotropic elasticity): ``rotation_matrix`` can then
+        be set, and ``rotate_gradients / rotate_fluxes / rotate_tangent_operator`` leave the arrays alone."""
+        return self.behavior.law == _lib.LAW_ORTHOTROPIC_ELASTIC
+
+    @property
     def rotation_matrix(self):
-        return None  # generic.py:129-131
+        """``None`` (``generic.py:129-131``) for every isotropic law.  Orthotropic elasticity: ``None`` by default; a 3x3 array-like
+        is a uniform frame and reaches the handle at once; anything else is kept for the quadrature map to evaluate per point
+        (``mfront.py:83``, ``quadrature_map.py:227-229``).  The rows of the matrix are the material axes in global coordinates."""
+        return self._rotation
+
+    @rotation_matrix.setter
+    def rotation_matrix(self, value):
+        if not self.frame_fused:
+            raise AttributeError(f"{self.name} is isotropic: rotation_matrix stays None (a material frame changes nothing in its update; "
+                                 "frames are read by OrthotropicElasticity)")
+        if value is None:
+            self._rotation = None
+            self.set_frame(None)
+            return
+        try:
+            a = np.asarray(value, dtype=np.float64)
+        except (TypeError, ValueError):
+            a = None
+        if a is not None and a.shape == (3, 3):
+            self.set_frame(a)
+            self._rotation = a.copy()
+        else:
+            self._rotation = value   # a UFL matrix, a Function, a callable: the map evaluates it and hands the values over
+
+    def set_frame(self, values):
+        """Material frames of the kernel: ``(3, 3)`` one for every point, ``(N, 3, 3)`` / ``(N, 9)`` one per Gauss point, ``None``
+        none (identity).  Checked by the library (finite, ``max |R R^T - I| <= 1e-8``); a refusal leaves everything as it was.
+        Before ``set_data_manager`` the frames are kept and handed over when the handles exist."""
+        if not self.frame_fused:
+            raise DxmError(f"{self.name} is isotropic and takes no material frame")
+        if values is None:
+            a = None
+        else:
+            a = np.array(values, dtype=np.float64)
+            if a.shape == (3, 3):
+                pass
+            elif a.ndim in (2, 3) and a.size % 9 == 0 and a.shape[1:] in ((9,), (3, 3)):
+                a = a.reshape(-1, 9)
+                if self._parts and len(a) != self._n:
+                    raise ValueError(f"{len(a)} frames for {self._n} Gauss points")
+            else:
+                raise ValueError(f"frames must have shape (3, 3), (N, 3, 3) or (N, 9), got {a.shape}")
+        self._push_frame(a, restore=self._frame)
+        self._frame = a
+
+    def _push_frame(self, a, restore=None):
+        """Hand every block's handle its frames; if a handle refuses, the ones before it get ``restore`` back."""
+        def one(h, lo, hi, v):
+            if v is None:
+                return self._lib.dxm_set_frame(h, None)
+            block = np.ascontiguousarray(v if v.shape == (3, 3) else v[lo:hi])   # held until the call has returned
+            if v.shape == (3, 3):
+                return self._lib.dxm_set_frame(h, block.ctypes.data)
+            return self._lib.dxm_set_frame_field(h, block.ctypes.data)
+
+        done = []
+        try:
+            for h, lo, hi, _ in self._parts:
+                self._chk(one(h, lo, hi, a))
+                done.append((h, lo, hi))
+        except DxmError:
+            for h, lo, hi in done:
+                one(h, lo, hi, restore)
+            raise
+
+    # the three hooks the reference's QuadratureMap.update() brackets integrate with (quadrature_map.py:315-330, mfront.py:336-343)
+    def rotate_gradients(self, gradient_vals, rotation_values):
+        """Hands the frames to the kernel if they differ from the ones it has and LEAVES THE GRADIENT UNTOUCHED: the kernel is given
+        global strains.  ``rotation_values``: flat, nine numbers per point (``rotation_func.x.array``), or nine in all."""
+        if not self.frame_fused:
+            raise DxmError(f"{self.name} is isotropic and takes no material frame")
+        rot = np.asarray(rotation_values, dtype=np.float64).reshape(-1, 9)
+        if self._parts and len(rot) not in (1, self._n):
+            raise ValueError(f"{len(rot)} frames for {self._n} Gauss points")
+        if len(rot) > 0 and np.all(rot == rot[0]):
+            rot = rot[0].reshape(3, 3)
+        if self._frame is not None and self._frame.shape == rot.shape and np.array_equal(self._frame, rot):
+            return
+        self.set_frame(rot)
+
+    def rotate_fluxes(self, flux_vals, rotation_values):
+        """Nothing: the kernel's stress is global already."""
+
+    def rotate_tangent_operator(self, Ct_vals, rotation_values):
+        """Nothing: the kernel's tangent is global already."""
 
     @property
     def gradients(self):
@@ -217,7 +312,7 @@ class HIPMaterial:
 
     @property
     def algorithmic_bytes_per_point(self):
-        if self._fields and self._parts:   # + 8 per bound kernel-parameter stream
+        if (self._fields or self._frame is not None) and self._parts:   # + 8 per bound kernel-parameter stream, + 72 for a frame field
             return int(self._lib.dxm_algorithmic_bytes(self._parts[0][0]))
         return int(self._info.algorithmic_bytes_per_point)
 
@@ -271,7 +366,8 @@ class HIPMaterial:
         if self.behavior.law not in (_lib.LAW_J2_LINEAR, _lib.LAW_J2_VOCE) or getattr(self.behavior, "custom_hardening", None) is not None:
             raise NotImplementedError(
                 f"material property {key!r} varies from point to point: per-point property fields exist for the small-strain J2 laws "
-                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp, Ogden, Hosford or custom hardening laws)")
+                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp, Ogden, Hosford, orthotropic elasticity or "
+                "custom hardening laws)")
         return list(self.behavior.flat_properties()).index(key)
 
     def _upload_field(self, key, arr, restore=None):
@@ -345,6 +441,14 @@ class HIPMaterial:
         except Exception:
             self.close()
             raise
+        if self._frame is not None:   # frames set before the handles existed, or kept from a data manager of the same size
+            try:
+                if self._frame.shape != (3, 3) and len(self._frame) != self._n:
+                    raise ValueError(f"{len(self._frame)} material frames are held, the data manager has {self._n} Gauss points: set the frames again")
+                self._push_frame(self._frame)
+            except Exception:
+                self.close()
+                raise
         if G > 1:
             from concurrent.futures import ThreadPoolExecutor
 

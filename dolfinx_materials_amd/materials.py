@@ -351,5 +351,72 @@ class HosfordIsotropicHardening(SmallStrainBehavior):
                 "yield_stress.H": self.yield_stress.H, "a": self.a}
 
 
+class OrthotropicElasticity(SmallStrainBehavior):
+    """Small-strain orthotropic elasticity in a material frame (the orthotropic form of MFront's ``StandardElasticity`` brick, as
+    ``tests/mfront/MericCailletaudSingleCrystalViscoPlasticity.mfront:18-28`` sets it up): nine constants ``E1, E2, E3, nu12,
+    nu23, nu13, G12, G23, G13``; all finite, ``E_i > 0``, ``G_ij > 0`` and a positive definite compliance.  No internal state.
+
+    ``JAXMaterial(OrthotropicElasticity(...))`` is the one material here whose ``rotation_matrix`` can be set: a constant 3x3
+    array, or anything else for the quadrature map to evaluate per point (``mfront.py:83``).  The ROWS of the matrix are the
+    material axes in global coordinates -- the matrix ``tests/uniaxial_tension.py:61-66`` builds.  The rotation happens inside the
+    kernel: gradients, fluxes and tangents of every call are global.  Tangent layouts ``"full"`` and ``"sym"``; uniform
+    properties only; the displacement forms need option ``fused_gradient`` off."""
+
+    law = _lib.LAW_ORTHOTROPIC_ELASTIC
+    gradient_name = "Strain"
+    flux_name = "Stress"
+    NAMES = ("E1", "E2", "E3", "nu12", "nu23", "nu13", "G12", "G23", "G13")
+    #: the MFront glossary names of the nine constants, in the order of the parameter vector
+    MFRONT_NAMES = ("YoungModulus1", "YoungModulus2", "YoungModulus3", "PoissonRatio12", "PoissonRatio23", "PoissonRatio13",
+                    "ShearModulus12", "ShearModulus23", "ShearModulus13")
+
+    def __init__(self, E1, E2, E3, nu12, nu23, nu13, G12, G23, G13):
+        for name, v in zip(self.NAMES, (E1, E2, E3, nu12, nu23, nu13, G12, G23, G13)):
+            object.__setattr__(self, name, float(v))
+        self.validate()
+
+    def validate(self):
+        """The rules the library applies in ``dxm_create`` / ``dxm_set_params``, with the offending value in the message."""
+        p = dict(zip(self.NAMES, self.params()))
+        for k, v in p.items():
+            if not _isfinite(v):
+                raise ValueError(f"orthotropic elasticity: {k} must be finite, got {v}")
+        for k in ("E1", "E2", "E3", "G12", "G23", "G13"):
+            if not p[k] > 0.0:
+                raise ValueError(f"orthotropic elasticity: {k} must be > 0, got {p[k]}")
+        # leading minors of the compliance, scaled
+        m2 = 1.0 - p["nu12"] ** 2 * p["E2"] / p["E1"]
+        m3 = (m2 - p["nu23"] ** 2 * p["E3"] / p["E2"] - p["nu13"] ** 2 * p["E3"] / p["E1"]
+              - 2.0 * p["nu12"] * p["nu23"] * p["nu13"] * p["E3"] / p["E1"])
+        if not (m2 > 0.0 and m3 > 0.0):
+            raise ValueError("orthotropic elasticity: the compliance is not positive definite: 1 - nu12^2 E2/E1 = "
+                             f"{m2:g}, det(S) E1 E2 E3 = {m3:g}")
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict):
+        """``material_properties`` keyed by the glossary names (``YoungModulus1`` ... ``ShearModulus13``), all nine."""
+        missing, extra = set(cls.MFRONT_NAMES) - set(props), set(props) - set(cls.MFRONT_NAMES)
+        if missing or extra:
+            raise ValueError(f"orthotropic elasticity material properties: missing {sorted(missing)}, unknown {sorted(extra)}")
+        return cls(*(float(props[k]) for k in cls.MFRONT_NAMES))
+
+    # the properties are read and written under their glossary names (update_material_property("YoungModulus1", ...))
+    def __getattr__(self, name):
+        if name in type(self).MFRONT_NAMES:
+            return getattr(self, self.NAMES[self.MFRONT_NAMES.index(name)])
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        if name in self.MFRONT_NAMES:
+            name = self.NAMES[self.MFRONT_NAMES.index(name)]
+        object.__setattr__(self, name, float(value) if name in self.NAMES else value)
+
+    def params(self):
+        return [getattr(self, k) for k in self.NAMES]
+
+    def flat_properties(self):
+        return {g: getattr(self, k) for g, k in zip(self.MFRONT_NAMES, self.NAMES)}
+
+
 def _isfinite(x):
     return x == x and abs(x) != float("inf")

@@ -218,7 +218,7 @@ class AcceleratedUpdate:
         if len(m.tangent_blocks) != 1:
             raise ValueError("packed tangent layouts are defined for materials with one (flux, gradient) block")
         ((block, shape),) = m.tangent_blocks.items()
-        if getattr(m, "rotation_matrix", None) is not None:
+        if getattr(m, "rotation_matrix", None) is not None and not getattr(m, "frame_fused", False):
             raise ValueError("a packed tangent cannot be rotated block by block (quadrature_map.py:326-330): use tangent_layout='full'")
         if shape[0] != shape[1] or (layout in ("coef", "pack4") and shape[0] != 6):
             raise ValueError(f"tangent layout {layout!r} is not defined for a {shape} block")
@@ -487,7 +487,9 @@ class AcceleratedUpdate:
         with _Timer("dx_mat: External state variable update"):
             if getattr(self, "external_state_variables", None):
                 self.update_external_state_variables()
-        rotate = getattr(m, "rotation_matrix", None) is not None
+        # a material that rotates inside its kernel (frame_fused) takes none of the three host passes; its frames reach the
+        # handle in update_material_rotation_matrix()
+        rotate = getattr(m, "rotation_matrix", None) is not None and not getattr(m, "frame_fused", False)
         rows_mode = plan.row_outputs and not rotate
         grad = None
         with _Timer("dx_mat: Gradients evaluation"):
@@ -535,6 +537,15 @@ class AcceleratedUpdate:
             self.__dict__["_accel_isv_stale"] = bool(m.internal_state_variables) and not delivered
             if self.isv_every_update is True and not delivered:
                 self.refresh_internal_state_variables()
+
+    def update_material_rotation_matrix(self, *args, **kwargs):
+        """``quadrature_map.py:227-229``: evaluate ``material.rotation_matrix`` into ``rotation_func``; for a material that rotates
+        inside its kernel (``frame_fused``) the frames of this map's points are then handed to its handle, once."""
+        super().update_material_rotation_matrix(*args, **kwargs)
+        m = self.material
+        if getattr(m, "frame_fused", False) and getattr(self, "rotation_func", None) is not None:
+            rot = np.asarray(self.rotation_func.x.array, dtype=np.float64).reshape(-1, 9)
+            m.rotate_gradients(None, rot[np.asarray(self.dofs)])
 
     def refresh_internal_state_variables(self):
         """Internal state variables of the last ``update()`` into their Functions (what the reference does in every

@@ -105,7 +105,22 @@ enum {
    * parameter fields, no fused displacement gradient (option fused_gradient 0), not served by a custom-hardening build.
    * params = [E, nu, R0, H, a] with R0 > 0, H >= 0, a >= 2 */
   DXM_LAW_HOSFORD_LINEAR = 10,   /* ids 8 and 9 are not assigned */
-  DXM_LAW_COUNT = 11
+  /* small-strain orthotropic elasticity in a material frame (the orthotropic form of the reference's StandardElasticity brick,
+   * tests/mfront/MericCailletaudSingleCrystalViscoPlasticity.mfront:18-28, driven through a rotated frame in
+   * tests/uniaxial_tension.py:59-68).  In the material frame, Mandel [11, 22, 33, sqrt2 12, sqrt2 13, sqrt2 23]:
+   * sigma_m = C eps_m, C block-diagonal: its 3x3 normal block is the inverse of the compliance S11 = 1/E1, S22 = 1/E2, S33 = 1/E3,
+   * S12 = -nu12/E1, S13 = -nu13/E1, S23 = -nu23/E2 (symmetric), its shear diagonal 2 G12, 2 G13, 2 G23.  No internal state.
+   * FRAME CONVENTION (dxm_set_frame*): R is 3x3 row-major and its ROWS are the material axes in global coordinates, so
+   * eps_m = R eps R^T, sigma = R^T sigma_m R and Ct = Q^T C Q with Q(R) the orthogonal 6x6 Mandel image of R -- the matrix
+   * tests/uniaxial_tension.py:61-66 builds for a material turned by +angle about z, nine numbers per point as rotation_func.x.array
+   * holds them.  (This reading is not pinned against mgis_bv.rotate*: MGIS was not available.)  Gradient, flux and tangent of every
+   * call are GLOBAL: the rotation is inside the kernel.  Without a frame the kernel computes C eps and C with no rotation at all.
+   * The tangent is a general symmetric 6x6: DXM_TANGENT_FULL and DXM_TANGENT_SYM; _COEF and _PACK4 are refused.  No per-point
+   * parameter fields, no fused displacement gradient (option fused_gradient 0), not served by a custom-hardening build.
+   * dxm_stats: n_nan counts points with a non-finite stress or tangent; n_plastic, n_not_converged, max_local_iters are 0.
+   * params = [E1, E2, E3, nu12, nu23, nu13, G12, G23, G13], all finite, E_i > 0, G_ij > 0, compliance positive definite */
+  DXM_LAW_ORTHOTROPIC_ELASTIC = 12,   /* id 11 is not assigned */
+  DXM_LAW_COUNT = 13
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */
@@ -176,13 +191,29 @@ int dxm_set_param_field(dxm_material* m, int param_index, const double* host_val
 int dxm_set_param_field_device(dxm_material* m, int param_index, const double* dev_values, void* hip_stream);
 /* bit i = parameter i is a field */
 int dxm_param_field_mask(const dxm_material* m);
+/* Material frames, DXM_LAW_ORTHOTROPIC_ELASTIC (convention: at the law).  A handle has no frame after dxm_create (identity).
+ * dxm_set_frame: one frame for every point, r9 = 3x3 row-major, passed to the kernel as an argument; NULL: back to no frame.
+ * dxm_set_frame_field: one frame per Gauss point, host_aos (npoints, 9) as rotation_func.x.array holds them; the library keeps its
+ * own device copy (nine streams, transposed once here); NULL unbinds (back to no frame).  Both check every frame -- finite, and
+ * max |R R^T - I| <= 1e-8 -- and a refusal returns < 0, names the first offending point and leaves the handle as it was.
+ * dxm_set_frame_field_device: the same from (npoints, 9) doubles in device memory on the handle's device, asynchronous on
+ * hip_stream and ordered like dxm_set_param_field_device; the frames are NOT checked; dev_aos is not referenced once the call is
+ * complete on that stream; NULL unbinds (that form waits for the last launch).
+ * In the rows forms (dxm_integrate_rows) the frame of point i is row i of the handle's field, not row rows[i].
+ * Every other law refuses all three (< 0, message): a frame changes nothing for an isotropic law.
+ * dxm_frame_kind: 0 none, 1 uniform, 2 field (negative: null handle). */
+int dxm_set_frame(dxm_material* m, const double* r9);
+int dxm_set_frame_field(dxm_material* m, const double* host_aos);
+int dxm_set_frame_field_device(dxm_material* m, const double* dev_aos, void* hip_stream);
+int dxm_frame_kind(const dxm_material* m);
 /* Bytes per point the handle's update kernel moves as it is configured now: dxm_law_info.algorithmic_bytes_per_point plus 8
- * per bound kernel-parameter stream. */
+ * per bound kernel-parameter stream, plus 72 while a frame field is bound. */
 int dxm_algorithmic_bytes(const dxm_material* m);
 /* Tangent layout integrate writes, doubles per point:
  *   DXM_TANGENT_FULL   n_flux*n_grad (36 / 81), row-major: what `jacobian_flatten` holds (quadrature_map.py:83-105);
  *   DXM_TANGENT_SYM    21 upper-triangle entries (i <= j), small-strain laws (symmetric tangent);
- *                      Hosford: the host-buffer forms of a DXM_TANGENT_FULL handle move these 21 and mirror them on the host;
+ *                      Hosford and orthotropic elasticity: the host-buffer forms of a DXM_TANGENT_FULL handle move these 21 and
+ *                      mirror them on the host;
  *   DXM_TANGENT_COEF   9 = (c1, c2, c3, n[0..5]) of Ct = c1 1x1 + c2 I + c3 n x n, J2 laws and Ramberg-Osgood
  *                      (tests/mfront/IsotropicLinearHardeningPlasticity.mfront:66-69 with M expanded);
  *   DXM_TANGENT_PACK4  4 = (c1, c2, c3, w), J2 laws and Ramberg-Osgood: the kernels form n = dev(stress) w, so the stress of the same update
@@ -272,7 +303,7 @@ const char* dxm_kernel_name(const dxm_material* m);
 /* Identity of the launch configuration: changes whenever a launch captured into a HIP graph before would
  * no longer do what a fresh call does -- dxm_advance (the two state buffers swap: the low bit flips and
  * flips back at the next advance), dxm_set_params / dxm_set_newton / dxm_set_tangent_layout /
- * dxm_set_param_field(_device) / dxm_set_option and anything else that moves the resident state (the upper bits increase).  Replay a captured graph only while the
+ * dxm_set_param_field(_device) / dxm_set_frame / dxm_set_frame_field(_device) / dxm_set_option and anything else that moves the resident state (the upper bits increase).  Replay a captured graph only while the
  * value equals the one read at capture time.  dxm_revert does not change it. */
 uint64_t dxm_launch_generation(const dxm_material* m);
 /* Tell the handle that the caller has replayed a HIP graph containing a launch of this handle: the replay

@@ -2,13 +2,18 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
 plateau of the curve).  Its line also carries the time of the arithmetic-free probe with the same three streams
 (stream_mix_elastic_shape_launch in tools/libstreammix.so, same arrays, same grid) and the ratios to it and to the elastic
 kernel when that ran in the same process.
+
+orthotropic: a strongly orthotropic set (E1 / E3 = 20) on the headline strains; three lines -- no frame, one uniform frame, one
+random proper rotation per point (dxm_set_frame / dxm_set_frame_field) -- each with three timings, its ratio to the elastic kernel of
+the same process (run `--laws elastic orthotropic`) next to the byte yardsticks 384 / 384 and 456 / 384, and the spread of the elastic
+kernel's own repeats.
 
 --param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
 (dxm_set_param_field; 1 = sig0, 2 = lambda and mu from an E field, 3 = both, 4 / 5 = H | sigu, b as well), in the same process and on
@@ -115,8 +120,8 @@ def main():
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
-    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws):
-        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden or Hosford law")
+    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws):
+        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford or orthotropic law")
     import torch
 
     import dolfinx_materials_amd.materials as jm
@@ -130,6 +135,7 @@ def main():
     elastic_ms = None
     fefp_ms = None
     j2_linear_ms = None
+    elastic_repeats = None
     for law in a.laws:
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
@@ -143,6 +149,9 @@ def main():
         elif law == "hosford":
             # the J2-linear parameters with the behaviour file's exponent a = 10, uniform (zero) state, the headline increments
             beh, hist = jm.HosfordIsotropicHardening(el, jm.LinearHardening(SIG0_LIN, H_LIN), a=10.0), j2_history(n)[1:3]
+        elif law == "orthotropic":
+            # E1 / E3 = 20 (the "strong" set of tests/orthotropic_ref.py) on the headline increments
+            beh, hist = jm.OrthotropicElasticity(200e3, 40e3, 10e3, 0.25, 0.3, 0.2, 12e3, 4e3, 7e3), j2_history(n)[1:3]
         elif law == "elastic":
             beh, hist = jm.ElasticBehavior(el), j2_history(n)[1:3]
         elif law == "j2_linear":
@@ -192,8 +201,10 @@ def main():
             "plastic_fraction": round(stats["n_plastic"] / n, 4), "max_local_iters": stats["max_local_iters"],
             "not_converged": stats["n_not_converged"], "rc": rc,
         }
-        if law == "elastic" and not sym:
-            elastic_ms = ms
+        if law == "elastic" and not sym:   # two more timings: the spread the orthotropic lines are read against
+            elastic_repeats = [round(ms, 4), round(timed(), 4), round(timed(), 4)]
+            r["kernel_ms_repeats"] = elastic_repeats
+            elastic_ms = float(np.median(elastic_repeats))
         if law in ("j2_linear", "hosford") and not sym:   # same-process comparison with the J2-linear kernel: two more timings each
             r["kernel"] = m.kernel_name
             r["kernel_ms_repeats"] = [round(ms, 4), round(timed(), 4), round(timed(), 4)]
@@ -222,8 +233,32 @@ def main():
                 r["ratio_to_elastic"] = round(ms / elastic_ms, 3)
         if a.cpu_sample:
             r["cpu_port"] = cpu_port(law, a.cpu_sample)
+        if law == "orthotropic":
+            r["law"] += "+noframe"
+            r["kernel"] = m.kernel_name
         print(json.dumps(r), flush=True)
         res.append(r)
+        if law == "orthotropic":
+            from orthotropic_ref import axis_rotation, random_rotations
+
+            first = [ms, timed(), timed()]
+            for tag, frames in (("noframe", None), ("uniform", axis_rotation(2, np.pi / 3) @ axis_rotation(0, 0.4)),
+                                ("field", random_rotations(np.random.default_rng(7), n))):
+                if frames is not None:
+                    m.set_frame(frames)
+                t = first if frames is None else [timed(), timed(), timed()]
+                del frames
+                ab = m.algorithmic_bytes_per_point - (15 * 8 if sym else 0)
+                f = {"law": f"orthotropic+{tag}" + ("+sym21" if sym else ""), "points": n, "kernel": m.kernel_name,
+                     "kernel_ms_repeats": [round(x, 4) for x in t], "kernel_ms": round(float(np.median(t)), 4),
+                     "algorithmic_bytes_per_point": ab, "GBs": round(ab * n / float(np.median(t)) / 1e6, 1)}
+                if elastic_ms and not sym:
+                    f["ratio_to_elastic"] = round(float(np.median(t)) / elastic_ms, 3)
+                    f["byte_ratio_to_elastic"] = round(ab / 384, 3)
+                    f["elastic_ms_repeats"] = elastic_repeats
+                    f["elastic_spread_ms"] = round(max(elastic_repeats) - min(elastic_repeats), 4)
+                    f["excess_over_yardstick_ms"] = round(float(np.median(t)) - elastic_ms * ab / 384, 4)
+                print(json.dumps(f), flush=True)
         if a.param_fields and law in ("j2_linear", "j2_voce") and not sym:
             import ctypes
 
