@@ -106,6 +106,16 @@ def test_host_chunks_take_two_passes_each():
     assert len(chunks) == 3 and sum(c for _, c in chunks) == N and all(c > CU * 256 for _, c in chunks)
     assert all(tc.passes(c, CU, 1) >= 2 for _, c in chunks)
     assert tc.plan_chunks(100_003, True, False, 64) == (3, 33536) and tc.plan_chunks(20_000_000, False, True, 64) == (32, 625152)
+    # the fused displacement form keeps the two alternating streams: no three-stream cap, the planner's own count
+    assert "const bool split_ok = r.split_streams && r.pipeline && !r.staged_grad && !r.fused;" in text
+    for n in (65_535, 65_536, 66_150, 100_003, N, 3_000_000):
+        nchunks, csize = tc.plan_chunks(n, True, False, 64)
+        fused = tc.host_chunks(n, 64, fused=True)
+        assert fused == [(c * csize, min(csize, n - c * csize)) for c in range(nchunks) if c * csize < n]
+        assert sum(c for _, c in fused) == n and all(off % 256 == 0 for off, _ in fused)
+    assert len(tc.host_chunks(65_535, 64, fused=True)) == 1 and len(tc.host_chunks(65_536, 64, fused=True)) == 2   # chunks from 65 536 points
+    assert len(tc.host_chunks(66_150, 64)) == 1 and tc.host_chunks(66_150, 64, fused=True) == [(0, 33280), (33280, 32870)]
+    assert tc.host_chunks(N, 64, fused=True) != chunks and tc.host_chunks(N, 2, fused=True) == tc.host_chunks(N, 2)
 
 
 @pytest.mark.parametrize("kind", ["linear", "voce"])

@@ -104,11 +104,13 @@ def plan_chunks(n, packed, staged_upload, max_chunks, pipeline=True):
     return nchunks, (-(-n // nchunks) + 255) // 256 * 256
 
 
-def host_chunks(n, max_chunks=64):
+def host_chunks(n, max_chunks=64, fused=False):
     """[(first, count)] of the chunks a host-buffer call makes of n points when its transfer is a packed one and the gradient array
-    is page-locked: ``plan_transfer`` then runs the three-stream scheme and caps the chunks at ``int(7 sqrt(n / 1e6))`` in [1, 24]."""
+    is page-locked: ``plan_transfer`` then runs the three-stream scheme and caps the chunks at ``int(7 sqrt(n / 1e6))`` in [1, 24].
+    ``fused``: the displacement form with the gradient evaluated inside the update kernel (short chunks: a packed transfer or a handle
+    whose own layout is packed).  Nothing is uploaded per chunk, the two alternating streams stay and that cap does not apply."""
     split_cap = min(max(int(7.0 * np.sqrt(n / 1e6)), 1), 24)
-    nchunks, csize = plan_chunks(n, True, False, split_cap if max_chunks > split_cap else max_chunks)
+    nchunks, csize = plan_chunks(n, True, False, split_cap if max_chunks > split_cap and not fused else max_chunks)
     return [(c * csize, min(csize, n - c * csize)) for c in range(nchunks) if c * csize < n]
 
 
