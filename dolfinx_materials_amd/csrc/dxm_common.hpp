@@ -144,6 +144,16 @@ __device__ __forceinline__ double fast_rcp(double x) {
 
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
+// tensor indices (SI[I], SJ[I]) of component I of a symmetric 6-vector [11, 22, 33, 12, 13, 23] (the Mandel and the DXM_SYM order)
+constexpr int SI[6] = {0, 1, 2, 0, 0, 1}, SJ[6] = {0, 1, 2, 1, 2, 2};
+
+// A general symmetric 6x6 tangent is staged per point as the 21 entries of its upper triangle, row by row (hosford.hip,
+// orthotropic.hip, written out by tile_tri21_store.hpp; hyperelastic.hip keeps its CC in registers in the same order)
+constexpr int TRI21 = 21;
+#define TRI21_AT(i, k) ((i) * 6 - (i) * ((i) - 1) / 2 + (k) - (i))   // slot of entry (i <= k)
+constexpr int TRI21_STAGE = WAVE * 6;                              // doubles per wave: strain in / stress out staging (tile_rows6_*.hpp)
+constexpr int TRI21_LDS_PER_WAVE = WAVE * TRI21 + TRI21_STAGE;     // doubles: the 64 staged triangles, then the staging region
+
 // Cache policy of the streaming accesses, fixed at build time by the bits of DXM_NT:
 //   bit 0 = non-temporal stores of flux and tangent      bit 1 = of the new state
 //   bit 2 = non-temporal loads of the gradient            bit 3 = of the old state

@@ -16,6 +16,8 @@
 // (point slot, tangent column) then evaluates the 9 rows of its column with compile-time row
 // indices (4 FMAs per entry, no per-entry index arithmetic), the results are transposed through
 // an LDS out-tile and leave as contiguous 1 KiB wave stores (full 64 B HBM write requests).
+// The I/O steps are text shared with the Ogden kernel (hyperelastic.hip): tile_rows9_{load,take,put,store}.hpp, tile_out81_roles.hpp,
+// tile_out81_copyout.hpp.
 #pragma once
 #include "dxm_common.hpp"
 #include "gradient.hpp"
@@ -163,6 +165,7 @@ fefp_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fin
 
   constexpr int TI[9] = {0, 1, 2, 0, 1, 0, 2, 1, 2};  // row index of entry t of the 9-vector
   constexpr int TJ[9] = {0, 1, 2, 1, 0, 2, 0, 2, 1};  // column index           (utils.py:168-190)
+  constexpr bool OUT81_WHOLE_KIB = true;              // tile_out81_copyout.hpp: the ragged branch tests whole KiBs first
   int lane = lane0;
 
   for (int64_t tile = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wid; tile < ntiles; tile += tile_stride) {
@@ -175,50 +178,20 @@ fefp_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fin
     lane &= WAVE - 1;   // gives the value range back to the compiler
     const bool valid = lane < npts;
     const int64_t gi = base + lane;
-    // tangent epilogue: lane = (point slot ps, tangent column cc); lane 63 idles
-    const int ps = lane / 9;
-    const int cc = lane - ps * 9;
-    const int kk = (0x26124 >> (2 * cc)) & 3;   // TI[cc] packed 2 bits each: 0,1,2,0,1,0,2,1,2
-    const int LL = (0x18864 >> (2 * cc)) & 3;   // TJ[cc]: 0,1,2,1,0,2,0,2,1
-    const double mk0 = kk == 0 ? 1.0 : 0.0, mk1 = kk == 1 ? 1.0 : 0.0, mk2 = kk == 2 ? 1.0 : 0.0;
+#include "tile_out81_roles.hpp"
 
     double F[9];
     double p_n = 0.0, g6[6] = {1, 1, 1, 0, 0, 0};
     if constexpr (GRAD == 0) {
       // ---- 1. F through LDS (64 x 9 doubles = 288 double2 per tile) ---------------------------------
-      if (npts == WAVE) {
-        const double2_t* gsrc = reinterpret_cast<const double2_t*>(Fin + base * 9);
-        double2_t v[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-          const int idx = k * WAVE + lane;
-          v[k] = (idx < 288) ? stream_load<2>(gsrc + idx) : double2_t{0.0, 0.0};
-        }
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-          const int idx = k * WAVE + lane;
-          if (idx < 288) stage2[idx] = v[k];
-        }
-      } else {  // ragged last tile: 8-byte accesses, identity for the missing points
-        const double* gsrc = Fin + base * 9;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-          const int idx = k * WAVE + lane;
-          const int c = idx % 9;
-          stage[idx] = (idx < npts * 9) ? gsrc[idx] : (c < 3 ? 1.0 : 0.0);
-        }
-      }
+#include "tile_rows9_load.hpp"
       if (valid) {
         p_n = stream_load<3>(s0 + (int64_t)FEFP_SLOT_P * ld + gi);
 #pragma unroll
         for (int c = 0; c < 6; ++c) g6[c] = stream_load<3>(s0 + (int64_t)(FEFP_SLOT_CPI + c) * ld + gi);
       }
       wave_lds_sync();
-      {
-        const double* f = stage + lane * 9;
-        F[0] = f[0]; F[4] = f[1]; F[8] = f[2]; F[1] = f[3]; F[3] = f[4];
-        F[2] = f[5]; F[6] = f[6]; F[5] = f[7]; F[7] = f[8];
-      }
+#include "tile_rows9_take.hpp"
       wave_lds_sync();
     } else {
       if constexpr (GRAD == 1) {
@@ -298,7 +271,6 @@ fefp_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fin
         h[L * 3 + m] = Jm23 * (G[DXM_SYM(L, 0)] * F[m * 3] + G[DXM_SYM(L, 1)] * F[m * 3 + 1] + G[DXM_SYM(L, 2)] * F[m * 3 + 2]);
     double d[6];  // be_bar_trial = F h (symmetric), then its deviator
     {
-      constexpr int SI[6] = {0, 1, 2, 0, 0, 1}, SJ[6] = {0, 1, 2, 1, 2, 2};
 #pragma unroll
       for (int t = 0; t < 6; ++t)
         d[t] = F[SI[t] * 3] * h[SJ[t]] + F[SI[t] * 3 + 1] * h[3 + SJ[t]] + F[SI[t] * 3 + 2] * h[6 + SJ[t]];
@@ -416,7 +388,6 @@ fefp_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fin
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int Jx = 0; Jx < 3; ++Jx) t[i * 3 + Jx] = P[i * 3 + Jx] * imu + cI * Fi[Jx * 3 + i];
-      constexpr int SI[6] = {0, 1, 2, 0, 0, 1}, SJ[6] = {0, 1, 2, 1, 2, 2};
 #pragma unroll
       for (int k = 0; k < 6; ++k)
         gn[k] = J23 * (Fi[SI[k] * 3] * t[SJ[k]] + Fi[SI[k] * 3 + 1] * t[3 + SJ[k]] + Fi[SI[k] * 3 + 2] * t[6 + SJ[k]]);
@@ -439,27 +410,9 @@ fefp_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fin
     }
 
     // ---- 5. PK1 through LDS, coalesced store -------------------------------------------------------
-    {
-      double* f = stage + lane * 9;
-      f[0] = P[0]; f[1] = P[4]; f[2] = P[8]; f[3] = P[1]; f[4] = P[3];
-      f[5] = P[2]; f[6] = P[6]; f[7] = P[5]; f[8] = P[7];
-    }
+#include "tile_rows9_put.hpp"
     wave_lds_sync();
-    if (npts == WAVE) {
-      double2_t* gdst = reinterpret_cast<double2_t*>(Pout + base * 9);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        const int idx = k * WAVE + lane;
-        if (idx < 288) stream_store<0>(gdst + idx, stage2[idx]);
-      }
-    } else {
-      double* gdst = Pout + base * 9;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const int idx = k * WAVE + lane;
-        if (idx < npts * 9) gdst[idx] = stage[idx];
-      }
-    }
+#include "tile_rows9_store.hpp"
 
     // ---- 6. tangent.  Per point 54 doubles are staged in LDS:
     //   Fi[J][i] 0..8 | Vc[col] 9..17 | U[i][L] 18..26 | Wc[col] 27..35 | Sr[row] 36..44 | g[L][J] 45..53
@@ -564,47 +517,7 @@ fefp_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fin
         }
       }
       wave_lds_sync();
-      {
-        int nv = npts - p0;                                      // valid points of this round
-        nv = nv < 0 ? 0 : (nv > cnt ? cnt : nv);
-        const int nent = nv * 81;                                // wave-uniform
-        double* gct = ct + (base + p0) * 81;                     // 16 B aligned: (base + p0) * 81 is even
-        const double2_t* o2 = reinterpret_cast<const double2_t*>(outt);
-        constexpr int NIT = F2_NIT;
-        double2_t v[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) v[it] = o2[it * WAVE + lane];   // out-tile is padded to NIT KiB
-        double2_t* g2p = reinterpret_cast<double2_t*>(gct) + lane;
-        // the two shapes every full tile consists of: straight-line stores, no per-KiB bookkeeping
-        constexpr int E_FULL = F2_PPR * 81, E_LAST = (WAVE % F2_PPR) * 81;
-        if (nent == E_FULL) {
-#pragma unroll
-          for (int it = 0; it < E_FULL / (2 * WAVE); ++it) stream_store<0>(g2p + it * WAVE, v[it]);
-          if constexpr (E_FULL % (2 * WAVE) != 0) {
-            static_assert(E_FULL % 2 == 0, "whole 16 B elements");
-            if (lane < (E_FULL % (2 * WAVE)) / 2) stream_store<0>(g2p + (E_FULL / (2 * WAVE)) * WAVE, v[E_FULL / (2 * WAVE)]);
-          }
-        } else if (E_LAST > 0 && nent == E_LAST) {
-#pragma unroll
-          for (int it = 0; it < E_LAST / (2 * WAVE); ++it) stream_store<0>(g2p + it * WAVE, v[it]);
-          if constexpr (E_LAST % (2 * WAVE) != 0) {
-            static_assert(E_LAST % 2 == 0, "whole 16 B elements");
-            if (lane < (E_LAST % (2 * WAVE)) / 2) stream_store<0>(g2p + (E_LAST / (2 * WAVE)) * WAVE, v[E_LAST / (2 * WAVE)]);
-          }
-        } else {   // ragged tile: element-wise bounds
-#pragma unroll
-          for (int it = 0; it < NIT; ++it) {
-            const int e0 = (it * WAVE + lane) * 2;
-            if ((it + 1) * 2 * WAVE <= nent) {                     // scalar branch: whole KiB valid
-              stream_store<0>(reinterpret_cast<double2_t*>(gct + e0), v[it]);
-            } else if (e0 + 1 < nent) {
-              stream_store<0>(reinterpret_cast<double2_t*>(gct + e0), v[it]);
-            } else if (e0 < nent) {
-              stream_store<0>(gct + e0, v[it].x);
-            }
-          }
-        }
-      }
+#include "tile_out81_copyout.hpp"
       wave_lds_sync();
     }
   }

@@ -22,47 +22,17 @@
 // quotient cancels where they are close -- repeated trial eigenvalues, i.e. uniaxial loading -- and the sinh-series form of the
 // Ogden kernel takes over (hyperelastic.hip: m (xy)^((m-1)/2) sinhc(m h) / sinhc(h), h = (ln x - ln y) / 2; exact at x = y).
 //
-// Mapping: one thread per point, one wave per tile of 64; strain in and stress out as 16 B-per-lane accesses through wave-private
-// LDS.  The tangent is a general symmetric 6x6: each point stages its 21 upper-triangle entries in LDS (64 x 21 x 8 B = 10.5 KiB per
-// wave, next to the 3 KiB of the strain / stress staging) and the wave writes the (N, 36) stream in output order, 16 B per lane,
-// whole 1 KiB runs, non-temporal -- entry (i, j) and (j, i) are the same staged number; the "sym" layout is the staged region as
-// it is.  State: SoA, 8 B-per-lane.
+// Mapping: one thread per point, one wave per tile of 64; the tile I/O is the shared text of tile_rows6_*.hpp (strain in, stress
+// out) and tile_tri21_store.hpp (the tangent, from the 21 upper-triangle entries each point stages in LDS: 10.5 KiB per wave next to
+// the 3 KiB of the strain / stress staging).  While the local Newton runs, the point's record parks its eigenvectors and strains.
+// State: SoA, 8 B-per-lane.
 #include "hosford.hpp"
+
+#include "principal_axes.hpp"
 
 namespace dxm {
 
-constexpr int HF_TRI = 21;
-constexpr int HF_STAGE = WAVE * 6;                          // doubles per wave: strain in / stress out staging
-constexpr int HF_LDS_PER_WAVE = WAVE * HF_TRI + HF_STAGE;   // doubles
 constexpr int HF_SWEEPS = 5;                     // cyclic Jacobi sweeps (hyperelastic.hip: off-diagonal below 1e-16 after 4)
-#define HF_TRI_AT(i, k) ((i) * 6 - (i) * ((i) - 1) / 2 + (k) - (i))   // slot of entry (i <= k) of the upper triangle, row by row
-
-// one Jacobi rotation in the (p, q) plane of a symmetric 3x3 (r: the third index); vp / vq: the two eigenvector columns
-// (the same rotation as hyperelastic.hip's: each law's translation unit stands alone)
-__device__ __forceinline__ void hf_jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double* vp, double* vq) {
-  const double d = aqq - app;
-  const double den = d + copysign(sqrt(d * d + 4.0 * apq * apq), d);
-  const double t = den != 0.0 ? 2.0 * apq * fast_rcp(den) : 0.0;
-  const double c = fast_rcp(sqrt(t * t + 1.0));
-  const double s = t * c;
-  app -= t * apq;
-  aqq += t * apq;
-  apq = 0.0;
-  const double rp = arp, rq = arq;
-  arp = c * rp - s * rq;
-  arq = s * rp + c * rq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double xp = vp[k], xq = vq[k];
-    vp[k] = c * xp - s * xq;
-    vq[k] = s * xp + c * xq;
-  }
-}
-
-// sinh(y) / y from y^2, |y| <= 0.1
-__device__ __forceinline__ double hf_sinhc(double y2) {
-  return 1.0 + y2 * (1.0 / 6.0) * (1.0 + y2 * (1.0 / 20.0) * (1.0 + y2 * (1.0 / 42.0) * (1.0 + y2 * (1.0 / 72.0) * (1.0 + y2 * (1.0 / 110.0)))));
-}
 
 // |x|^(a-2) of a ratio 0 <= ax <= 1 with lx = log(ax)
 __device__ __forceinline__ double hf_pow_am2(double ax, double lx, double am2) {
@@ -75,7 +45,7 @@ __device__ __forceinline__ double hf_divided_difference(double m, double xs, dou
   const double px = ux * ax, py = uy * ay;
   const bool same = xs * ys > 0.0;
   const double h = 0.5 * (lx - ly), y = m * h;
-  const double series = m * sqrt(ux * uy) * hf_sinhc(y * y) * fast_rcp(hf_sinhc(h * h));
+  const double series = m * sqrt(ux * uy) * sinhc_series(y * y) * fast_rcp(sinhc_series(h * h));
   const double quotient = same ? (px - py) / (ax - ay) : (px + py) / (ax + ay);
   return (same && fmax(fabs(y), fabs(h)) <= 0.1) ? series : quotient;
 }
@@ -85,13 +55,13 @@ __global__ void __launch_bounds__(BLOCK, 2)
 hosford_kernel(const LawParams prm, const int64_t n, const double* __restrict__ eps, const double* __restrict__ s0,
                double* __restrict__ s1, const int64_t ld, double* __restrict__ sig, double* __restrict__ ct,
                BlockStats* __restrict__ stats) {
-  __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * HF_LDS_PER_WAVE];
+  __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * TRI21_LDS_PER_WAVE];
   __shared__ unsigned long long red[4 * WAVES_PER_BLOCK];
 
   int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x >> 6;
-  double* tri = lds_all + wid * HF_LDS_PER_WAVE;                        // 64 x 21 tangent entries
-  double2_t* stage2 = reinterpret_cast<double2_t*>(tri + WAVE * HF_TRI);   // strain in / stress out staging
+  double* tri = lds_all + wid * TRI21_LDS_PER_WAVE;                       // 64 x 21 tangent entries
+  double2_t* stage2 = reinterpret_cast<double2_t*>(tri + WAVE * TRI21);   // strain in / stress out staging
 
   const int64_t ntiles = (n + WAVE - 1) / WAVE;
   const int64_t tile_stride = (int64_t)gridDim.x * WAVES_PER_BLOCK;
@@ -99,7 +69,6 @@ hosford_kernel(const LawParams prm, const int64_t n, const double* __restrict__ 
 
   const double lambda = prm.lambda, mu = prm.mu;
   const double SQ2 = 1.4142135623730950488;
-  constexpr int SI[6] = {0, 1, 2, 0, 0, 1}, SJ[6] = {0, 1, 2, 1, 2, 2};   // tensor indices of Mandel component I
 
   for (int64_t tile = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wid; tile < ntiles; tile += tile_stride) {
     const int64_t base = tile * WAVE;
@@ -112,27 +81,14 @@ hosford_kernel(const LawParams prm, const int64_t n, const double* __restrict__ 
 
     // ---- 1. coalesced strain load (3 x 1 KiB per wave) into LDS; old state, SoA ----------------------------
     double e[6], ep[6] = {0, 0, 0, 0, 0, 0}, p_n = 0.0;
-    {
-      const double2_t* gsrc = reinterpret_cast<const double2_t*>(eps + base * 6);
-      double2_t v[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int idx = k * WAVE + lane;
-        v[k] = (idx < npts * 3) ? stream_load<2>(gsrc + idx) : double2_t{0.0, 0.0};
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) stage2[k * WAVE + lane] = v[k];
-    }
+#include "tile_rows6_load.hpp"
     if (valid) {
       p_n = stream_load<3>(s0 + (int64_t)HF_SLOT_P * ld + gi);
 #pragma unroll
       for (int c = 0; c < 6; ++c) ep[c] = stream_load<3>(s0 + (int64_t)(HF_SLOT_EP + c) * ld + gi);
     }
     wave_lds_sync();
-    {
-      const double2_t a = stage2[lane * 3 + 0], b = stage2[lane * 3 + 1], c = stage2[lane * 3 + 2];
-      e[0] = a.x; e[1] = a.y; e[2] = b.x; e[3] = b.y; e[4] = c.x; e[5] = c.y;
-    }
+#include "tile_rows6_take.hpp"
     wave_lds_sync();   // the staging region is reused for the stress below
 
     // ---- 2. trial state ------------------------------------------------------------------------------------
@@ -142,7 +98,7 @@ hosford_kernel(const LawParams prm, const int64_t n, const double* __restrict__ 
     // the 21 tangent entries of the point go straight into its LDS record (held in registers next to the eigenvectors they
     // spill at 256 VGPRs); cchk: their sum, for the non-finite check.  While the local Newton runs, the record parks the
     // eigenvectors, the trial strain and the old plastic strain (21 doubles; small_strain.hpp does the same for Ramberg-Osgood)
-    int ro = lane * HF_TRI;   // opaque: every access is base + small immediate
+    int ro = lane * TRI21;   // opaque: every access is base + small immediate
     asm volatile("" : "+v"(ro));
     double* rec = tri + ro;
     double cchk = 0.0;   // sum of everything the point writes
@@ -181,9 +137,9 @@ hosford_kernel(const LawParams prm, const int64_t n, const double* __restrict__ 
       double n0[3] = {1.0, 0.0, 0.0}, n1[3] = {0.0, 1.0, 0.0}, n2[3] = {0.0, 0.0, 1.0};
 #pragma unroll 1
       for (int sw = 0; sw < HF_SWEEPS; ++sw) {
-        hf_jacobi_rotate(t0, t1, t01, t02, t12, n0, n1);
-        hf_jacobi_rotate(t0, t2, t02, t01, t12, n0, n2);
-        hf_jacobi_rotate(t1, t2, t12, t01, t02, n1, n2);
+        jacobi_rotate(t0, t1, t01, t02, t12, n0, n1);
+        jacobi_rotate(t0, t2, t02, t01, t12, n0, n2);
+        jacobi_rotate(t1, t2, t12, t01, t02, n1, n2);
       }
 #pragma unroll
       for (int k = 0; k < 3; ++k) { rec[k] = n0[k]; rec[3 + k] = n1[k]; rec[6 + k] = n2[k]; }
@@ -299,7 +255,7 @@ hosford_kernel(const LawParams prm, const int64_t n, const double* __restrict__ 
           for (int K = I; K < 6; ++K) {
             const double v = E0[I] * X0[K] + E1[I] * X1[K] + E2[I] * X2[K] + th01 * G01[I] * G01[K] + th02 * G02[I] * G02[K] +
                              th12 * G12[I] * G12[K];
-            rec[HF_TRI_AT(I, K)] = v;
+            rec[TRI21_AT(I, K)] = v;
             cchk += v;
           }
         if (valid) {
@@ -317,53 +273,15 @@ hosford_kernel(const LawParams prm, const int64_t n, const double* __restrict__ 
 #pragma unroll
       for (int i = 0; i < 6; ++i)
 #pragma unroll
-        for (int k = i; k < 6; ++k) rec[HF_TRI_AT(i, k)] = ((i < 3 && k < 3) ? lambda : 0.0) + ((i == k) ? 2.0 * mu : 0.0);
+        for (int k = i; k < 6; ++k) rec[TRI21_AT(i, k)] = ((i < 3 && k < 3) ? lambda : 0.0) + ((i == k) ? 2.0 * mu : 0.0);
     }
     // stress, state and tangent (quadrature_map.py:322-324 asserts on all three)
     if (valid && !(fabs(cchk) <= 1.79769313486231570e308)) ++c_nan;
     wave_lds_sync();
 
-    // ---- 7. coalesced stress store (3 x 1 KiB) -------------------------------------------------------------
-    {
-      double2_t* gdst = reinterpret_cast<double2_t*>(sig + base * 6);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int idx = k * WAVE + lane;
-        if (idx < npts * 3) stream_store<0>(gdst + idx, stage2[idx]);
-      }
-    }
-
-    // ---- 8. tangent: the wave writes the output stream in order from the staged records ------------------------
-    if constexpr (SYM) {
-      // the staged region IS the (npts, 21) output: 672 pairs per full tile
-      double* gct = ct + base * HF_TRI;
-      const double2_t* t2 = reinterpret_cast<const double2_t*>(tri);
-      const int lim = npts * HF_TRI;
-#pragma unroll
-      for (int it = 0; it < 11; ++it) {
-        const int k = it * WAVE + lane;
-        const int e0 = 2 * k;
-        if (e0 + 1 < lim) stream_store<0>(reinterpret_cast<double2_t*>(gct + e0), t2[k]);
-        else if (e0 < lim) stream_store<0>(gct + e0, tri[e0]);
-      }
-    } else {
-      // full 6x6, row-major: 18 pairs per point, 18 x 1 KiB per full tile; pair (i, j..j+1) of point q reads the staged (min, max) entries
-      double2_t* gct = reinterpret_cast<double2_t*>(ct + base * 36);
-      const int lim = npts * 18;
-#pragma unroll 2
-      for (int it = 0; it < 18; ++it) {
-        const int k = it * WAVE + lane;
-        const int q = k / 18;
-        const int r = k - q * 18;
-        const int i = r / 3;
-        const int j = (r - i * 3) * 2;
-        const int lo0 = i < j ? i : j, hi0 = i < j ? j : i;
-        const int lo1 = i < j + 1 ? i : j + 1, hi1 = i < j + 1 ? j + 1 : i;
-        const double* rec = tri + q * HF_TRI;
-        const double2_t v = {rec[HF_TRI_AT(lo0, hi0)], rec[HF_TRI_AT(lo1, hi1)]};
-        if (k < lim) stream_store<0>(gct + k, v);
-      }
-    }
+    // ---- 7. coalesced stress store; 8. tangent, in output order from the staged records ------------------------
+#include "tile_rows6_store.hpp"
+#include "tile_tri21_store.hpp"
     wave_lds_sync();   // the LDS region is rewritten by the next tile
   }
 

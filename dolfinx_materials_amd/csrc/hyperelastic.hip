@@ -15,48 +15,22 @@
 // max(|m h|, |h|) <= 0.1 and the plain quotient beyond, where it loses at most a factor 5 of the powers' own rounding: both are
 // accurate on either side of the switch, exactly repeated eigenvalues (uniaxial loading, F = I) take the series at h = 0.
 //
-// Mapping and I/O are those of fefp.hpp: one thread per point, one wave per tile of 64; F in and PK1 out as 16 B-per-lane accesses
-// through wave-private LDS; the tangent in rounds of 16 points through an out-tile transposed in LDS, non-temporal 1 KiB wave
-// stores over whole 128 B lines.  The epilogue differs: the owner lane stages F (9), S (6) and CC as a full 6x6 (36, so that the
-// column lanes address it as row * 6 + lane constant); lane (point slot, column (k, L)) forms B[MJ] = sum_P CC[MJ][PL] F[k][P]
-// (symmetric in MJ: 6 values) and the nine rows A[(i,J),(k,L)] = sum_M F[i][M] B[MJ] + delta_ik S[L][J].
+// Mapping and I/O are those of fefp.hpp, as shared text: tile_rows9_*.hpp (F in, PK1 out), tile_out81_roles.hpp and
+// tile_out81_copyout.hpp (the tangent in rounds of 16 points through an out-tile transposed in LDS).  The epilogue between them
+// differs: the owner lane stages F (9), S (6) and CC as a full 6x6 (36, so that the column lanes address it as row * 6 + lane
+// constant); lane (point slot, column (k, L)) forms B[MJ] = sum_P CC[MJ][PL] F[k][P] (symmetric in MJ: 6 values) and the nine rows
+// A[(i,J),(k,L)] = sum_M F[i][M] B[MJ] + delta_ik S[L][J].
 #include "hyperelastic.hpp"
 
 #include "fefp.hpp"   // the shared skeleton's constants (F2_PPR, F2_OUT, F2_NIT, F2_COEF, F2_LDS_PER_WAVE), DXM_SYM
+#include "principal_axes.hpp"
 
 namespace dxm {
 
 constexpr int OG_REC = 51;   // F 0..8 | S 9..14 | CC 15..50; 102 dwords = 38 mod 64: the 16 owner lanes' 8 B writes fall on distinct bank pairs (19 l mod 32)
 static_assert(F2_PPR * OG_REC <= F2_COEF, "the records fit the coefficient region of the FeFp layout: same LDS, two workgroups per CU");
-#define OG_TRI(i, k) ((i) * 6 - (i) * ((i) - 1) / 2 + (k) - (i))   // slot of entry (i <= k) of the 21 upper-triangle values
+static_assert(WAVE % F2_PPR == 0, "every round of a full tile is a full round");
 constexpr int OG_SWEEPS = 5;   // cyclic Jacobi sweeps of the 3x3 eigenproblem (off-diagonal below 1e-16 |C| after 4 on every test family)
-
-// one Jacobi rotation in the (p, q) plane of a symmetric 3x3 (r: the third index); vp / vq: the two eigenvector columns
-__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double* vp, double* vq) {
-  const double d = aqq - app;
-  const double den = d + copysign(sqrt(d * d + 4.0 * apq * apq), d);
-  // t = tan of the rotation angle, the smaller root; an already-zero entry (den == 0 needs apq == 0 too) is left alone
-  const double t = den != 0.0 ? 2.0 * apq * fast_rcp(den) : 0.0;
-  const double c = fast_rcp(sqrt(t * t + 1.0));
-  const double s = t * c;
-  app -= t * apq;
-  aqq += t * apq;
-  apq = 0.0;
-  const double rp = arp, rq = arq;
-  arp = c * rp - s * rq;
-  arq = s * rp + c * rq;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double xp = vp[k], xq = vq[k];
-    vp[k] = c * xp - s * xq;
-    vq[k] = s * xp + c * xq;
-  }
-}
-
-// sinh(y) / y from y^2, |y| <= 0.1
-__device__ __forceinline__ double sinhc_series(double y2) {
-  return 1.0 + y2 * (1.0 / 6.0) * (1.0 + y2 * (1.0 / 20.0) * (1.0 + y2 * (1.0 / 42.0) * (1.0 + y2 * (1.0 / 72.0) * (1.0 + y2 * (1.0 / 110.0)))));
-}
 
 // (c_i^m - c_j^m) / (c_i - c_j) from c, ln c, c^(m-1), c^m of both (header comment)
 __device__ __forceinline__ double divided_difference(double m, double ci, double cj, double li, double lj, double pwi, double pwj, double ui, double uj) {
@@ -86,7 +60,7 @@ ogden_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fi
   const double SQ2 = 1.4142135623730950488;
   constexpr int TI[9] = {0, 1, 2, 0, 1, 0, 2, 1, 2};  // row index of entry t of the 9-vector
   constexpr int TJ[9] = {0, 1, 2, 1, 0, 2, 0, 2, 1};  // column index           (utils.py:168-190)
-  constexpr int SI[6] = {0, 1, 2, 0, 0, 1}, SJ[6] = {0, 1, 2, 1, 2, 2};   // entry I of a symmetric 6-vector (DXM_SYM order)
+  constexpr bool OUT81_WHOLE_KIB = false;             // tile_out81_copyout.hpp: per-lane bounds only in the ragged branch
   int lane = lane0;
 
   for (int64_t tile = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wid; tile < ntiles; tile += tile_stride) {
@@ -97,45 +71,15 @@ ogden_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fi
     lane &= WAVE - 1;
     const bool valid = lane < npts;
     const int64_t gi = base + lane;
-    // tangent epilogue: lane = (point slot ps, tangent column cc = (kk, LL)); lane 63 idles
-    const int ps = lane / 9;
-    const int cc = lane - ps * 9;
-    const int kk = (0x26124 >> (2 * cc)) & 3;   // TI[cc] packed 2 bits each
-    const int LL = (0x18864 >> (2 * cc)) & 3;   // TJ[cc]
-    const double mk0 = kk == 0 ? 1.0 : 0.0, mk1 = kk == 1 ? 1.0 : 0.0, mk2 = kk == 2 ? 1.0 : 0.0;
+#include "tile_out81_roles.hpp"
     // slot of the symmetric pair (P, LL) for P = 0, 1, 2
     const int vL0 = LL == 0 ? 0 : LL + 2, vL1 = LL == 1 ? 1 : LL + 3, vL2 = LL == 2 ? 2 : LL + 4;
 
     // ---- 1. F through LDS (64 x 9 doubles = 288 double2 per tile) -------------------------------------
     double F[9];
-    if (npts == WAVE) {
-      const double2_t* gsrc = reinterpret_cast<const double2_t*>(Fin + base * 9);
-      double2_t v[5];
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        const int idx = k * WAVE + lane;
-        v[k] = (idx < 288) ? stream_load<2>(gsrc + idx) : double2_t{0.0, 0.0};
-      }
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        const int idx = k * WAVE + lane;
-        if (idx < 288) stage2[idx] = v[k];
-      }
-    } else {  // ragged last tile: 8-byte accesses, identity for the missing points
-      const double* gsrc = Fin + base * 9;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const int idx = k * WAVE + lane;
-        const int c = idx % 9;
-        stage[idx] = (idx < npts * 9) ? gsrc[idx] : (c < 3 ? 1.0 : 0.0);
-      }
-    }
+#include "tile_rows9_load.hpp"
     wave_lds_sync();
-    {
-      const double* f = stage + lane * 9;
-      F[0] = f[0]; F[4] = f[1]; F[8] = f[2]; F[1] = f[3]; F[3] = f[4];
-      F[2] = f[5]; F[6] = f[6]; F[5] = f[7]; F[7] = f[8];
-    }
+#include "tile_rows9_take.hpp"
     wave_lds_sync();
 
     // ---- 2. C = F^T F and its eigen-decomposition (cyclic Jacobi, fixed sweeps, registers only) ------------
@@ -218,7 +162,7 @@ ogden_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fi
       for (int I = 0; I < 6; ++I)
 #pragma unroll
         for (int Kx = I; Kx < 6; ++Kx)
-          CC[OG_TRI(I, Kx)] = E0[I] * X0[Kx] + E1[I] * X1[Kx] + E2[I] * X2[Kx] + th01 * G01[I] * G01[Kx] + th02 * G02[I] * G02[Kx] +
+          CC[TRI21_AT(I, Kx)] = E0[I] * X0[Kx] + E1[I] * X1[Kx] + E2[I] * X2[Kx] + th01 * G01[I] * G01[Kx] + th02 * G02[I] * G02[Kx] +
                     th12 * G12[I] * G12[Kx];
       // non-finite results (det F <= 0, a non-finite F): every output of the point is a combination of these with finite weights
       const double chk = ((s0 + sp1) + (s2 + D00)) + ((D11 + D22) + (D01 + D02)) + ((D12 + th01) + (th02 + th12));
@@ -233,26 +177,10 @@ ogden_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fi
 #pragma unroll
         for (int Jx = 0; Jx < 3; ++Jx)
           P[i * 3 + Jx] = F[i * 3] * S6[DXM_SYM(0, Jx)] + F[i * 3 + 1] * S6[DXM_SYM(1, Jx)] + F[i * 3 + 2] * S6[DXM_SYM(2, Jx)];
-      double* f = stage + lane * 9;
-      f[0] = P[0]; f[1] = P[4]; f[2] = P[8]; f[3] = P[1]; f[4] = P[3];
-      f[5] = P[2]; f[6] = P[6]; f[7] = P[5]; f[8] = P[7];
+#include "tile_rows9_put.hpp"
     }
     wave_lds_sync();
-    if (npts == WAVE) {
-      double2_t* gdst = reinterpret_cast<double2_t*>(Pout + base * 9);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        const int idx = k * WAVE + lane;
-        if (idx < 288) stream_store<0>(gdst + idx, stage2[idx]);
-      }
-    } else {
-      double* gdst = Pout + base * 9;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        const int idx = k * WAVE + lane;
-        if (idx < npts * 9) gdst[idx] = stage[idx];
-      }
-    }
+#include "tile_rows9_store.hpp"
     wave_lds_sync();   // the out-tile below aliases the staging region
 
     // ---- 5. tangent, F2_PPR points per round ---------------------------------------------------------------
@@ -271,7 +199,7 @@ ogden_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fi
 #pragma unroll
         for (int I = 0; I < 6; ++I)
 #pragma unroll
-          for (int Kx = 0; Kx < 6; ++Kx) rec[15 + I * 6 + Kx] = CC[I <= Kx ? OG_TRI(I, Kx) : OG_TRI(Kx, I)];
+          for (int Kx = 0; Kx < 6; ++Kx) rec[15 + I * 6 + Kx] = CC[I <= Kx ? TRI21_AT(I, Kx) : TRI21_AT(Kx, I)];
       }
       wave_lds_sync();
 #pragma unroll 1
@@ -313,37 +241,7 @@ ogden_kernel(const LawParams prm, const int64_t n, const double* __restrict__ Fi
         }
       }
       wave_lds_sync();
-      {
-        int nv = npts - p0;                                      // valid points of this round
-        nv = nv < 0 ? 0 : (nv > cnt ? cnt : nv);
-        const int nent = nv * 81;                                // wave-uniform
-        double* gct = ct + (base + p0) * 81;                     // 16 B aligned: (base + p0) * 81 is even
-        const double2_t* o2 = reinterpret_cast<const double2_t*>(outt);
-        constexpr int NIT = F2_NIT;
-        double2_t v[NIT];
-#pragma unroll
-        for (int it = 0; it < NIT; ++it) v[it] = o2[it * WAVE + lane];   // the last, partial KiB reads on into the records: inside the wave's region
-        double2_t* g2p = reinterpret_cast<double2_t*>(gct) + lane;
-        constexpr int E_FULL = F2_PPR * 81;
-        static_assert(WAVE % F2_PPR == 0 && E_FULL % 2 == 0, "every round of a full tile is a full round of whole 16 B elements");
-        if (nent == E_FULL) {   // straight-line stores
-#pragma unroll
-          for (int it = 0; it < E_FULL / (2 * WAVE); ++it) stream_store<0>(g2p + it * WAVE, v[it]);
-          if constexpr (E_FULL % (2 * WAVE) != 0) {
-            if (lane < (E_FULL % (2 * WAVE)) / 2) stream_store<0>(g2p + (E_FULL / (2 * WAVE)) * WAVE, v[E_FULL / (2 * WAVE)]);
-          }
-        } else {   // ragged tile: element-wise bounds
-#pragma unroll
-          for (int it = 0; it < NIT; ++it) {
-            const int e0 = (it * WAVE + lane) * 2;
-            if (e0 + 1 < nent) {
-              stream_store<0>(reinterpret_cast<double2_t*>(gct + e0), v[it]);
-            } else if (e0 < nent) {
-              stream_store<0>(gct + e0, v[it].x);
-            }
-          }
-        }
-      }
+#include "tile_out81_copyout.hpp"
       wave_lds_sync();
     }
   }

@@ -18,20 +18,11 @@
 // rotation), uniform (nine doubles, a kernel argument), field (nine SoA streams of the handle, 8 B per lane each like the state
 // slots and the parameter streams).
 //
-// Mapping: the Hosford kernel's (hosford.hip).  One thread per point, one wave per tile of 64; strain in and stress out as 16
-// B-per-lane accesses through wave-private LDS.  The tangent is a general symmetric 6x6: each point stages its 21 upper-triangle
-// entries in LDS (64 x 21 x 8 B = 10.5 KiB per wave, next to the 3 KiB of the strain / stress staging) and the wave writes the
-// (N, 36) stream in output order, 16 B per lane, whole 1 KiB runs, non-temporal -- entry (i, j) and (j, i) are the same staged
-// number; the "sym" layout is the staged region as it is.
+// Mapping: the Hosford kernel's (hosford.hip): one thread per point, one wave per tile of 64, the tile I/O as the shared text of
+// tile_rows6_*.hpp and tile_tri21_store.hpp; the frame of the point is loaded between the strain load and its LDS round trip.
 #include "orthotropic.hpp"
 
 namespace dxm {
-
-constexpr int OR_TRI = 21;
-constexpr int OR_STAGE = WAVE * 6;                          // doubles per wave: strain in / stress out staging
-constexpr int OR_LDS_PER_WAVE = WAVE * OR_TRI + OR_STAGE;   // doubles
-static_assert(OR_LDS_BYTES == WAVES_PER_BLOCK * OR_LDS_PER_WAVE * 8 + 4 * WAVES_PER_BLOCK * 8, "orthotropic.hpp states the LDS of the kernel");
-#define OR_TRI_AT(i, k) ((i) * 6 - (i) * ((i) - 1) / 2 + (k) - (i))   // slot of entry (i <= k) of the upper triangle, row by row
 
 template <int FRAME, int SYM>
 __global__ void __launch_bounds__(BLOCK, 2)
@@ -39,13 +30,14 @@ orthotropic_kernel(const LawParams prm, const int64_t n, const double* __restric
                    const double* __restrict__ frames, const int64_t ldf, double* __restrict__ sig, double* __restrict__ ct,
                    BlockStats* __restrict__ stats) {
 #pragma clang fp contract(off)
-  __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * OR_LDS_PER_WAVE];
+  __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * TRI21_LDS_PER_WAVE];
   __shared__ unsigned long long red[4 * WAVES_PER_BLOCK];
+  static_assert(OR_LDS_BYTES == sizeof(lds_all) + sizeof(red), "orthotropic.hpp states the LDS of the kernel");
 
   int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x >> 6;
-  double* tri = lds_all + wid * OR_LDS_PER_WAVE;                           // 64 x 21 tangent entries
-  double2_t* stage2 = reinterpret_cast<double2_t*>(tri + WAVE * OR_TRI);   // strain in / stress out staging
+  double* tri = lds_all + wid * TRI21_LDS_PER_WAVE;                       // 64 x 21 tangent entries
+  double2_t* stage2 = reinterpret_cast<double2_t*>(tri + WAVE * TRI21);   // strain in / stress out staging
 
   const int64_t ntiles = (n + WAVE - 1) / WAVE;
   const int64_t tile_stride = (int64_t)gridDim.x * WAVES_PER_BLOCK;
@@ -55,7 +47,6 @@ orthotropic_kernel(const LawParams prm, const int64_t n, const double* __restric
   // the normal block is symmetric by construction (the host mirrors its upper triangle)
   const double A[3][3] = {{C.c[0], C.c[1], C.c[2]}, {C.c[1], C.c[4], C.c[5]}, {C.c[2], C.c[5], C.c[8]}};
   const double SQ2 = 1.4142135623730950488;
-  constexpr int SI[6] = {0, 1, 2, 0, 0, 1}, SJ[6] = {0, 1, 2, 1, 2, 2};   // tensor indices of Mandel component I
 
   for (int64_t tile = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wid; tile < ntiles; tile += tile_stride) {
     const int64_t base = tile * WAVE;
@@ -68,17 +59,7 @@ orthotropic_kernel(const LawParams prm, const int64_t n, const double* __restric
 
     // ---- 1. coalesced strain load (3 x 1 KiB per wave) into LDS; the frame of the point --------------------------
     double e[6];
-    {
-      const double2_t* gsrc = reinterpret_cast<const double2_t*>(eps + base * 6);
-      double2_t v[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int idx = k * WAVE + lane;
-        v[k] = (idx < npts * 3) ? stream_load<2>(gsrc + idx) : double2_t{0.0, 0.0};
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) stage2[k * WAVE + lane] = v[k];
-    }
+#include "tile_rows6_load.hpp"
     double R[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
     if constexpr (FRAME == OR_FRAME_FIELD) {
       if (valid) {
@@ -95,13 +76,10 @@ orthotropic_kernel(const LawParams prm, const int64_t n, const double* __restric
       }
     }
     wave_lds_sync();
-    {
-      const double2_t a = stage2[lane * 3 + 0], b = stage2[lane * 3 + 1], c = stage2[lane * 3 + 2];
-      e[0] = a.x; e[1] = a.y; e[2] = b.x; e[3] = b.y; e[4] = c.x; e[5] = c.y;
-    }
+#include "tile_rows6_take.hpp"
     wave_lds_sync();   // the staging region is reused for the stress below
 
-    int ro = lane * OR_TRI;   // opaque: every access is base + small immediate
+    int ro = lane * TRI21;   // opaque: every access is base + small immediate
     asm volatile("" : "+v"(ro));
     double* rec = tri + ro;
     double cchk = 0.0;   // sum of everything the point writes
@@ -116,7 +94,7 @@ orthotropic_kernel(const LawParams prm, const int64_t n, const double* __restric
 #pragma unroll
       for (int i = 0; i < 6; ++i)
 #pragma unroll
-        for (int k = i; k < 6; ++k) rec[OR_TRI_AT(i, k)] = (k < 3) ? A[i][k] : ((i == k) ? C.g2[i - 3] : 0.0);
+        for (int k = i; k < 6; ++k) rec[TRI21_AT(i, k)] = (k < 3) ? A[i][k] : ((i == k) ? C.g2[i - 3] : 0.0);
     } else {
       // ---- 2. the Mandel image of R -------------------------------------------------------------------------------
       double Q[6][6];
@@ -163,7 +141,7 @@ orthotropic_kernel(const LawParams prm, const int64_t n, const double* __restric
           double t = Q[0][I] * X[0];
 #pragma unroll
           for (int r = 1; r < 6; ++r) t = __builtin_fma(Q[r][I], X[r], t);
-          rec[OR_TRI_AT(I, K)] = t;
+          rec[TRI21_AT(I, K)] = t;
           cchk += t;
         }
       }
@@ -177,47 +155,9 @@ orthotropic_kernel(const LawParams prm, const int64_t n, const double* __restric
     if (valid && !(fabs(cchk) <= 1.79769313486231570e308)) ++c_nan;
     wave_lds_sync();
 
-    // ---- 5. coalesced stress store (3 x 1 KiB) -------------------------------------------------------------
-    {
-      double2_t* gdst = reinterpret_cast<double2_t*>(sig + base * 6);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int idx = k * WAVE + lane;
-        if (idx < npts * 3) stream_store<0>(gdst + idx, stage2[idx]);
-      }
-    }
-
-    // ---- 6. tangent: the wave writes the output stream in order from the staged records (hosford.hip, step 8) --
-    if constexpr (SYM) {
-      // the staged region IS the (npts, 21) output: 672 pairs per full tile
-      double* gct = ct + base * OR_TRI;
-      const double2_t* t2 = reinterpret_cast<const double2_t*>(tri);
-      const int lim = npts * OR_TRI;
-#pragma unroll
-      for (int it = 0; it < 11; ++it) {
-        const int k = it * WAVE + lane;
-        const int e0 = 2 * k;
-        if (e0 + 1 < lim) stream_store<0>(reinterpret_cast<double2_t*>(gct + e0), t2[k]);
-        else if (e0 < lim) stream_store<0>(gct + e0, tri[e0]);
-      }
-    } else {
-      // full 6x6, row-major: 18 pairs per point, 18 x 1 KiB per full tile; pair (i, j..j+1) of point q reads the staged (min, max) entries
-      double2_t* gct = reinterpret_cast<double2_t*>(ct + base * 36);
-      const int lim = npts * 18;
-#pragma unroll 2
-      for (int it = 0; it < 18; ++it) {
-        const int k = it * WAVE + lane;
-        const int q = k / 18;
-        const int r = k - q * 18;
-        const int i = r / 3;
-        const int j = (r - i * 3) * 2;
-        const int lo0 = i < j ? i : j, hi0 = i < j ? j : i;
-        const int lo1 = i < j + 1 ? i : j + 1, hi1 = i < j + 1 ? j + 1 : i;
-        const double* rq = tri + q * OR_TRI;
-        const double2_t v = {rq[OR_TRI_AT(lo0, hi0)], rq[OR_TRI_AT(lo1, hi1)]};
-        if (k < lim) stream_store<0>(gct + k, v);
-      }
-    }
+    // ---- 5. coalesced stress store; 6. tangent, in output order from the staged records ------------------------
+#include "tile_rows6_store.hpp"
+#include "tile_tri21_store.hpp"
     wave_lds_sync();   // the LDS region is rewritten by the next tile
   }
 

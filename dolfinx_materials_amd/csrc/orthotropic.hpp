@@ -32,7 +32,7 @@ struct Frame9 { double r[9]; };   // row-major 3x3: the rows are the material ax
 constexpr int OR_BLOCKS_PER_CU = 64;
 
 // static LDS of one workgroup: per wave the 64 x 21 staged tangent entries and the strain / stress staging, plus the block-stats words
-constexpr int OR_LDS_BYTES = WAVES_PER_BLOCK * (WAVE * 21 + WAVE * 6) * 8 + 4 * WAVES_PER_BLOCK * 8;
+constexpr int OR_LDS_BYTES = WAVES_PER_BLOCK * TRI21_LDS_PER_WAVE * 8 + 4 * WAVES_PER_BLOCK * 8;
 
 // the full-layout kernel without a frame (what dxm_create asks the resources of)
 __attribute__((visibility("hidden"))) const void* orthotropic_kernel_fn();

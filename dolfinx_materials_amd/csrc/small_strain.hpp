@@ -37,6 +37,8 @@
 // The elastic and Ramberg-Osgood branches are never instantiated with FIELDS.  The two smaller fragments, small_strain_stage_coef.hpp
 // (the nine staged numbers of a point) and small_strain_expand_store.hpp (the rebuild kernels' store loop), are shared the same way
 // for the same reason: as helper functions they change dxmat.hip's code (about 1 200 differing assembly lines for the loop alone).
+// The row load / take / store steps themselves (steps 1, 2 and 6 of the strain-array path) are tile_rows6_{load,take,store}.hpp, the
+// text the Hosford and orthotropic kernels include as well.
 #pragma once
 #include "dxm_common.hpp"
 #include "gradient.hpp"

@@ -39,17 +39,7 @@
     double p_n = 0.0, ep[6] = {0, 0, 0, 0, 0, 0};
     if constexpr (GRAD == 0) {
       // ---- 1. coalesced strain load (3 x 1 KiB per wave) into LDS ------------------------------
-      {
-        const double2_t* gsrc = reinterpret_cast<const double2_t*>(eps + base * 6);
-        double2_t v[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const int idx = k * WAVE + lane;
-          v[k] = (idx < npts * 3) ? stream_load<2>(gsrc + idx) : double2_t{0.0, 0.0};
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) stage2[k * WAVE + lane] = v[k];
-      }
+#include "tile_rows6_load.hpp"
       // ---- old state, SoA (issued before the LDS round trip completes) -------------------------
       if constexpr (ss_has_state<LAW>) {
         if (valid) {
@@ -60,10 +50,7 @@
       }
       wave_lds_sync();
       // ---- 2. my point's strain ----------------------------------------------------------------
-      {
-        const double2_t a = stage2[lane * 3 + 0], b = stage2[lane * 3 + 1], c = stage2[lane * 3 + 2];
-        e[0] = a.x; e[1] = a.y; e[2] = b.x; e[3] = b.y; e[4] = c.x; e[5] = c.y;
-      }
+#include "tile_rows6_take.hpp"
       wave_lds_sync();  // staging region is reused for the stress below
     } else {
       double Hd[9];
@@ -263,16 +250,7 @@
     wave_lds_sync();
 
     // ---- 6. coalesced stress store (3 x 1 KiB) -----------------------------------------------
-    {
-      double2_t* gdst = reinterpret_cast<double2_t*>(sig + base * 6);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int idx = k * WAVE + lane;
-        if (idx < npts * 3) {
-          stream_store<0>(gdst + idx, stage2[idx]);
-        }
-      }
-    }
+#include "tile_rows6_store.hpp"
     // ---- 7. coalesced tangent store: entry pair (i, j..j+1) of point q ---------------------------
     if constexpr (TL == TL_PACK4) {
       static_assert(ss_has_coef<LAW>, "the elastic tangent is a constant: nothing to write");

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Build-time checks of the device code of libdxmat's five translation units (csrc/{dxmat,ramberg_osgood,param_fields,hyperelastic,
-hosford}.hip), on the cross-compiler alone:
+"""Build-time checks of the device code of libdxmat's six translation units (csrc/{dxmat,ramberg_osgood,param_fields,hyperelastic,
+hosford,orthotropic}.hip), on the cross-compiler alone:
 
 1. the resources of every kernel, read from -Rpass-analysis=kernel-resource-usage: no scratch and no spilled VGPR anywhere, and
    the kernels with per-point parameter fields within the bounds of the uniform J2 kernels (at most 128 VGPRs, the same static LDS,
@@ -11,7 +11,7 @@ hosford}.hip), on the cross-compiler alone:
     python tools/check_device_asm.py [--parent HEAD~1] [--write-digests FILE.json]
 
 Prints one line per kernel, one line per unit and a JSON summary; exit status 1 if a bound is broken or an assembly file differs.
-The helpers are what tests/test_{param_fields,hyperelastic,hosford}_build.py assert with."""
+The helpers are what tests/test_{param_fields,hyperelastic,hosford,orthotropic}_build.py and tests/test_tile_fragments.py assert with."""
 import argparse
 import hashlib
 import json
@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "dolfinx_materials_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-S", "--cuda-device-only"]
-UNITS = ("dxmat", "ramberg_osgood", "param_fields", "hyperelastic", "hosford")
+UNITS = ("dxmat", "ramberg_osgood", "param_fields", "hyperelastic", "hosford", "orthotropic")
 MAX_VGPRS = 128
 J2_STATIC_LDS = 30848     # small_strain.hpp: 4 waves x (64 x 6 + 64 x 9) doubles + the 4 x 4 status words
 
@@ -76,7 +76,7 @@ def sha(path):
 
 
 def build_units(csrc, tmp, tag):
-    """unit -> (sha256 of its device assembly, resource table), the five units compiled side by side"""
+    """unit -> (sha256 of its device assembly, resource table), the six units compiled side by side"""
     def one(unit):
         out = os.path.join(tmp, f"{unit}_{tag}.s")
         remarks = device_asm(csrc, unit, out, remarks=True)
