@@ -29,6 +29,7 @@
 #include "gradient.hpp"
 #include "small_strain.hpp"
 #include "ramberg_osgood.hpp"
+#include "small_strain_clean.hpp"
 #include "param_fields.hpp"
 #include "hyperelastic.hpp"
 #include "hosford.hpp"
@@ -616,12 +617,30 @@ struct dxm_material {
   int frame_kind = 0;
   Frame9 frame_uniform{};
   double* frame_streams = nullptr;          // the field as nine SoA streams of ld doubles each (the kernel reads 8 B per lane)
+  // clean-tile stamps (the J2 laws; small_strain_clean.hpp): stamps[t] == clean_stamp means that tile t holds
+  // the same bytes in state[0] and state[1].  Whoever writes either buffer without maintaining them calls bump_clean_stamp first
+  uint32_t* stamps = nullptr;               // ceil(ld / 64) words, zeroed at dxm_create
+  uint32_t clean_stamp = 1;                 // never 0
+  bool stamps_stale = false;                // the counter wrapped: no stamp is believed until the next eager launch has zeroed them
+  bool opt_elide_clean_state = true;
+  mutable bool state_exposed = false;       // dxm_state_ptr handed out an address: the plain kernels from then on
 };
 
 static int sync_last(dxm_material* m);
 static int pf_refresh_elastic(dxm_material* m, hipStream_t st);
 
+// Called BEFORE anything but a clean kernel writes either state buffer (and by whoever learns of a write it could not see): all
+// stamps turn stale at once.  Launches still in flight may go on writing the old value, which is stale too.
+static void bump_clean_stamp(dxm_material* m) {
+  if (!m->stamps) return;
+  bool wrapped = false;
+  m->clean_stamp = dxm_host::next_clean_stamp(m->clean_stamp, &wrapped);
+  if (wrapped) m->stamps_stale = true;
+}
+static int64_t stamp_words(const dxm_material* m) { return (m->ld + 63) / 64; }
+
 static void free_state(dxm_material* m) {
+  if (m->stamps) { (void)hipFree(m->stamps); m->stamps = nullptr; }
   if (!m->state_base) return;
   (void)hipFree(m->state_base);
   m->state_base = nullptr;
@@ -810,6 +829,14 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
     fail(-3, "hipMalloc of stats failed"); return bail();
   }
   if (init_state(m) != 0) return bail();
+#ifndef DXM_CUSTOM_HARDENING
+  if (law == DXM_LAW_J2_LINEAR || law == DXM_LAW_J2_VOCE) {
+    const size_t bytes = sizeof(uint32_t) * (size_t)stamp_words(m);
+    if (hipMalloc(&m->stamps, bytes) != hipSuccess || hipMemset(m->stamps, 0, bytes) != hipSuccess) {
+      fail(-3, "hipMalloc / hipMemset of %zu stamp bytes failed", bytes); return bail();
+    }
+  }
+#endif
   g_last_error.clear();
   return m;
 }
@@ -916,6 +943,7 @@ static double* state_of(const dxm_material* m, int which) {
 static int materialize_s1(dxm_material* m) {
   if (!m->s1_alias) return 0;
   const LawDesc& d = kLaws[m->law];
+  bump_clean_stamp(m);   // (the copy makes the buffers equal, the writer that asked for it then changes one of them)
   if (d.n_slots > 0)
     HIP_TRY(hipMemcpy(m->state[1], m->state[0], (size_t)d.n_slots * m->ld * sizeof(double),
                       hipMemcpyDeviceToDevice));
@@ -1052,6 +1080,7 @@ int dxm_set_state(dxm_material* m, int which, int field, const double* host_aos)
   hipStream_t st = m->own_stream;
   if (int rc = upload_from_host(m->d_field, host_aos, sizeof(double) * n * dim, st)) return rc;
   const int blocks = (int)((n * dim + 255) / 256);
+  bump_clean_stamp(m);   // one of the two buffers changes
   hipLaunchKernelGGL(unpack_isv_kernel, dim3(blocks), dim3(256), 0, st, state_of(m, which), m->ld, n,
                      m->d_field, map);
   HIP_TRY(hipGetLastError());
@@ -1163,6 +1192,42 @@ static void launch_small_strain(const LaunchArgs& a) {
   // a fifth wave per SIMD would fit and costs 0.65 % (0.8169 vs 0.8116 / 0.8123 ms per 1e7 points in one process,
   // profiles/archive/r03_j2_ab_pack4.jsonl); the elastic kernel keeps its five.
   constexpr int dyn_lds = LAW == LAW_ELASTIC ? 0 : 2304;
+  // the J2 laws: the kernel that leaves unchanged tiles' state where it is, or the plain one behind a moved-on stamp
+  // (dxm_host::choose_state_launch holds the rule; every writer of the state buffers is listed in DESIGN.md section 2)
+  if constexpr (ss_has_state<LAW>) {
+    if (m->stamps) {
+      hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+      if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusActive; }
+      const bool capturing = cap != hipStreamCaptureStatusNone;
+      if (m->stamps_stale && !capturing && m->opt_elide_clean_state && !m->state_exposed) {
+        // every stamp value has been used: start over from zeroed stamps, behind whatever this handle still has in flight
+        if (sync_last(m) == 0 && hipMemsetAsync(m->stamps, 0, sizeof(uint32_t) * (size_t)stamp_words(m), st) == hipSuccess) {
+          m->stamps_stale = false;
+          m->clean_stamp = 1;
+        } else {
+          (void)hipGetLastError();
+        }
+      }
+      dxm_host::StateLaunchFlags f{};
+      f.has_stamps = true;
+      f.option = m->opt_elide_clean_state;
+      f.fields = m->pf_mask != 0;
+      f.frame = m->frame_kind != 0;
+      f.fused = a.fused != nullptr;
+      f.whole_tiles = dxm_host::covers_whole_tiles(a.off, cnt, m->n);
+      f.capturing = capturing;
+      f.exposed = m->state_exposed;
+      f.stamps_stale = m->stamps_stale;
+      const dxm_host::StateLaunch how = dxm_host::choose_state_launch(f);
+#ifndef DXM_CUSTOM_HARDENING
+      if (how == dxm_host::StateLaunch::clean &&
+          small_strain_clean_launch(LAW, tl, grid, dyn_lds, st, m->prm, cnt, grad, s0, s1, m->ld, flux, ct, bs, m->stamps + a.off / WAVE,
+                                    m->clean_stamp))
+        return;
+#endif
+      bump_clean_stamp(m);
+    }
+  }
 #ifndef DXM_CUSTOM_HARDENING
   if constexpr (LAW != LAW_ELASTIC) {
     if (m->pf_mask) {   // param_fields.hip: the streams advance with the range like the state slots
@@ -2033,7 +2098,26 @@ const double* dxm_state_ptr(const dxm_material* m, int which, int field, int com
   if (check_field(m, which, field)) return nullptr;
   const LawDesc& d = kLaws[m->law];
   if (comp < 0 || comp >= d.isv_dim[field]) { fail(-1, "component out of range"); return nullptr; }
+  m->state_exposed = true;   // what is written through the address is not seen here: no state store is elided from now on
   return state_of(m, which) + (size_t)(d.isv_slot[field] + comp) * m->ld;
+}
+
+int dxm_clean_tiles(dxm_material* m, int64_t* clean, int64_t* tiles) {
+  if (!m || !clean || !tiles) return fail(-1, "null argument");
+  *clean = *tiles = 0;
+  if (!m->stamps || m->n == 0) return 0;
+  DEVICE_GUARD(m);
+  if (int rc = sync_last(m)) return rc;
+  const int64_t nt = (m->n + WAVE - 1) / WAVE;
+  *tiles = nt;
+  // a handle that launches the plain kernels only (option off, address handed out) has no clean tile in use
+  if (!m->opt_elide_clean_state || m->state_exposed || m->stamps_stale) return 0;
+  std::vector<uint32_t> host((size_t)nt);
+  if (int rc = download_to_host(host.data(), m->stamps, sizeof(uint32_t) * (size_t)nt, m->own_stream)) return rc;   // pageable: through the page-locked staging
+  int64_t c = 0;
+  for (uint32_t v : host) c += v == m->clean_stamp;
+  *clean = c;
+  return 0;
 }
 
 const char* dxm_kernel_name(const dxm_material* m) {
@@ -2316,6 +2400,7 @@ int dxm_notify_replay(dxm_material* m) {
   m->launched = true;
   m->last_event_recorded = false;   // nothing of the replay is known here: waits fall back to the device
   m->s1_alias = false;              // the replayed kernel rewrote every slot of s1
+  bump_clean_stamp(m);              // ... without maintaining the stamps
   return 0;
 }
 
@@ -2357,6 +2442,9 @@ int dxm_set_option(dxm_material* m, const char* name, double value) {
   } else if (k == "blocks_per_cu") {
     if (!(value >= 1 && value <= 256)) return fail(-1, "blocks_per_cu must be in [1, 256]");
     m->blocks_per_cu = (int)value;
+  } else if (k == "elide_clean_state") {
+    m->opt_elide_clean_state = on;
+    bump_clean_stamp(m);
   } else {
     return fail(-1, "unknown option '%s'", name);
   }

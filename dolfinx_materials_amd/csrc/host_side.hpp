@@ -344,6 +344,39 @@ inline int launch_grid(int64_t cnt, int num_cu, int blocks_per_cu) {
 }
 
 // ------------------------------------------------------------------------------------------
+// which update kernel a launch of a J2 handle uses, and what it means for the handle's clean-tile stamps
+// ------------------------------------------------------------------------------------------
+// The invariant: stamps[t] == clean_stamp  =>  tile t (64 points) holds the same bytes in both state buffers.
+// Only the clean kernels (small_strain_clean.hip) maintain it.  Every other launch rewrites s1 without looking at the stamps, so it
+// makes all of them stale first: the handle's clean_stamp moves on (plain_bump).  A handle without stamps has nothing to maintain.
+enum class StateLaunch { clean, plain, plain_bump };
+struct StateLaunchFlags {
+  bool has_stamps;     // a J2 law with its stamps allocated (LAW_J2_LINEAR / LAW_J2_VOCE in a stock build)
+  bool option;         // option elide_clean_state
+  bool fields;         // per-point parameter fields are bound (param_fields.hip serves the launch)
+  bool frame;          // a material frame is bound (no J2 law accepts one; listed so that the rule does not depend on that)
+  bool fused;          // the gradient is evaluated inside the kernel
+  bool whole_tiles;    // the range starts on a tile of the handle and ends on one or with the handle's last point: a tile of the
+                       // handle that the launch covered in part could not be called the same in both buffers
+  bool capturing;      // the stream is being captured: the launch may run any number of times later, unseen
+  bool exposed;        // dxm_state_ptr has handed out a state address: writes through it are unseen
+  bool stamps_stale;   // the stamp counter wrapped and the stamps have not been zeroed since
+};
+inline StateLaunch choose_state_launch(const StateLaunchFlags& f) {
+  if (!f.has_stamps) return StateLaunch::plain;
+  if (f.option && !f.fields && !f.frame && !f.fused && f.whole_tiles && !f.capturing && !f.exposed && !f.stamps_stale) return StateLaunch::clean;
+  return StateLaunch::plain_bump;
+}
+inline bool covers_whole_tiles(int64_t off, int64_t cnt, int64_t npoints) { return off % 64 == 0 && (cnt % 64 == 0 || off + cnt == npoints); }
+// the stamp after `s`: never 0 (what a tile that yielded is marked with); *wrapped: every stamp value has been used once, the
+// stamps must be zeroed before one of them is believed again
+inline uint32_t next_clean_stamp(uint32_t s, bool* wrapped) {
+  const uint32_t t = s + 1u;
+  *wrapped = t == 0u;
+  return t == 0u ? 1u : t;
+}
+
+// ------------------------------------------------------------------------------------------
 // transfer plan of the host-buffer form: every decision run_and_download (dxmat.hip) executes
 // ------------------------------------------------------------------------------------------
 // What the call is asked to do, as plain values.

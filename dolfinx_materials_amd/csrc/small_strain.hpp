@@ -34,6 +34,8 @@
 //   * Voce: the Newton tolerance rtol max(|sig0|, 2e-8 mu) of dxmat.hip::build_params is formed per point when sig0 or mu is a stream;
 //   * linear hardening: the H < 0 gate of the "rho <= 0" report is a per-lane test when H is a stream;
 //   * the opaque re-read of the lane index once per tile is done for both J2 laws, not for Voce only.
+// A third kernel of the same text, small_strain_clean_kernel (small_strain_clean.hip, CLEAN = true: the J2 laws, strain-array form),
+// adds the per-tile stamp load, the wave-wide vote after the yield test and the skipped state store; here CLEAN is false.
 // The elastic and Ramberg-Osgood branches are never instantiated with FIELDS.  The two smaller fragments, small_strain_stage_coef.hpp
 // (the nine staged numbers of a point) and small_strain_expand_store.hpp (the rebuild kernels' store loop), are shared the same way
 // for the same reason: as helper functions they change dxmat.hip's code (about 1 200 differing assembly lines for the loop alone).
@@ -210,6 +212,9 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
                     BlockStats* __restrict__ stats, const MeshSource src) {
   constexpr bool FIELDS = false;
   constexpr ParamStreams pf = {};   // no stream: named by the discarded FIELDS blocks of the body only
+  constexpr bool CLEAN = false;
+  constexpr uint32_t* stamps = nullptr;   // (small_strain_clean.hip: named by the discarded CLEAN blocks of the body only)
+  constexpr uint32_t stamp = 0;
 #include "small_strain_body.hpp"
 }
 
@@ -223,6 +228,9 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
                           BlockStats* __restrict__ stats, const MeshSource src) {
   static_assert(LAW == LAW_J2_LINEAR || LAW == LAW_J2_VOCE, "parameter fields: the J2 laws");
   constexpr bool FIELDS = true;
+  constexpr bool CLEAN = false;
+  constexpr uint32_t* stamps = nullptr;
+  constexpr uint32_t stamp = 0;
 #include "small_strain_body.hpp"
 }
 

@@ -1,6 +1,8 @@
 // The tile body of the small-strain update kernels: NOT a header of its own.  small_strain.hpp includes this text inside the braces
 // of small_strain_kernel (FIELDS = false) and of small_strain_field_kernel (FIELDS = true); each defines, just before the include,
 //   constexpr bool FIELDS    and    pf (ParamStreams: the kernel's argument, or an all-null constant that only discarded code names)
+//   constexpr bool CLEAN     and    stamps, stamp (small_strain_clean.hip: the per-tile stamps of the handle and the value that means
+//                                   "this tile's bytes are the same in both state buffers"; null constants elsewhere, as for pf)
 // beside the common arguments (prm, n, eps, s0, s1, ld, sig, ct, stats, src) and template parameters (LAW, TL, GRAD).  Shared as
 // text and not through a function: see the comment at the top of small_strain.hpp.
   __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * SS_LDS_PER_WAVE];
@@ -34,6 +36,8 @@
     }
     const bool valid = lane < npts;
     const int64_t gi = base + lane;
+    [[maybe_unused]] uint32_t tile_stamp = 0;     // CLEAN only
+    [[maybe_unused]] bool any_plastic = true;     // CLEAN only: some valid lane of the tile yields, i.e. s1 gets bits that s0 does not hold
 
     double e[6];
     double p_n = 0.0, ep[6] = {0, 0, 0, 0, 0, 0};
@@ -48,6 +52,8 @@
           for (int c = 0; c < 6; ++c) ep[c] = stream_load<3>(s0 + (int64_t)(1 + c) * ld + gi);
         }
       }
+      // CLEAN: the tile's stamp travels with the old state (one word per wave, made scalar: the skip below is a uniform branch)
+      if constexpr (CLEAN) tile_stamp = __builtin_amdgcn_readfirstlane(stamps[tile]);
       wave_lds_sync();
       // ---- 2. my point's strain ----------------------------------------------------------------
 #include "tile_rows6_take.hpp"
@@ -205,6 +211,7 @@
           c_maxit = iters > c_maxit ? iters : c_maxit;
         }
       }
+      if constexpr (CLEAN) any_plastic = __ballot(valid && f > 0.0) != 0;
     }
     // sigma = lambda tr(eel) 1 + 2 mu eel                                      mfront:76
     const double ltr = lambda * (e[0] + e[1] + e[2]);
@@ -228,11 +235,20 @@
     }
 
     // ---- 4. new state, SoA -------------------------------------------------------------------
+    // CLEAN: a tile without a yielding lane stores into s1 the bits it read from s0 (p_new = p_n, ep untouched); where the
+    // stamp says that s1 holds them already, the seven stores are skipped.  The stamp follows what was stored: a tile that
+    // yielded is no longer the same in both buffers (0 is never current), one that did not is from now on.
     if constexpr (ss_has_state<LAW>) {
-      if (valid) {
+      if (CLEAN ? (valid && (any_plastic || tile_stamp != stamp)) : valid) {
         stream_store<1>(s1 + gi, p_new);
 #pragma unroll
         for (int c = 0; c < 6; ++c) stream_store<1>(s1 + (int64_t)(1 + c) * ld + gi, ep[c]);
+      }
+      if constexpr (CLEAN) {
+        if (lane == 0) {
+          if (any_plastic) { if (tile_stamp == stamp) stamps[tile] = 0u; }
+          else if (tile_stamp != stamp) stamps[tile] = stamp;
+        }
       }
     }
 

@@ -286,8 +286,15 @@ int dxm_get_stats(dxm_material* m, dxm_stats* stats);
 /* Packs the user-visible ISVs of state `which` into a device AoS (npoints, n_isv_total) array,
  * enqueued on hip_stream (the `_hcat_mixed` of jaxmat.py:46-58, :227-229, on device). */
 int dxm_isv_device(dxm_material* m, int which, double* isv_aos_dev, void* hip_stream);
-/* Device address of component `comp` of SoA state field `field` (npoints contiguous doubles). */
+/* Device address of component `comp` of SoA state field `field` (npoints contiguous doubles).
+ * The library cannot see what is written through such an address.  A handle whose state address was handed out (S0 or S1,
+ * any field) therefore stops eliding state stores for good (option "elide_clean_state" below): from this call on its launches use
+ * the kernel that rewrites s1 in full, and dxm_clean_tiles reports no clean tile. */
 const double* dxm_state_ptr(const dxm_material* m, int which, int field, int comp);
+/* The J2 laws: how many 64-point tiles of the handle are currently known to hold the same bytes in both state buffers (*clean), of
+ * how many (*tiles = ceil(npoints / 64)); a launch with option "elide_clean_state" skips the state store of such a tile while no point
+ * of it yields.  Waits for the last launch.  Other laws (and a custom-hardening build) report 0 of 0.  Returns 0 or < 0. */
+int dxm_clean_tiles(dxm_material* m, int64_t* clean, int64_t* tiles);
 /* Rebuild full tangents from their coefficient form on the device: coef_dev (npoints, 9) as written with
  * DXM_TANGENT_COEF -> ct_dev (npoints, 36), the block DXM_TANGENT_FULL writes, bit for bit; asynchronous on
  * hip_stream of `device`.  For consumers that move the 72 B/point form (e.g. across xGMI: an all-gather of
@@ -298,7 +305,9 @@ int dxm_expand_tangent_device(const double* coef_dev, int64_t npoints, double* c
  * stress + this form moves 80 instead of 120 (coefficients) or 336 (full blocks) B/point across xGMI. */
 int dxm_expand_tangent_pack4_device(const double* flux_dev, const double* pack_dev, int64_t npoints, double* ct_dev, int device,
                                     void* hip_stream);
-/* Name of the HIP kernel integrate launches for this handle (for profile filtering). */
+/* Name of the HIP kernel integrate launches for this handle (for profile filtering).  A J2 handle whose launches elide state stores
+ * (option "elide_clean_state") runs the same tile body as small_strain_clean_kernel<law, layout>; the name reported stays that of the
+ * plain kernel. */
 const char* dxm_kernel_name(const dxm_material* m);
 /* Identity of the launch configuration: changes whenever a launch captured into a HIP graph before would
  * no longer do what a fresh call does -- dxm_advance (the two state buffers swap: the low bit flips and
@@ -355,6 +364,12 @@ int dxm_notify_replay(dxm_material* m);
  *                            allows (default 1)
  *   "blocks_per_cu"  1..256  grid size of the update kernel in workgroups per CU (default 32 small strain,
  *                            the resident 2 for FeFp)
+ *   "elide_clean_state" 1 | 0  the J2 laws (uniform parameters, strain-array forms): a 64-point tile without a yielding point
+ *                            stores into s1 exactly the bits it read from s0; 1 (default) skips that store where the handle knows
+ *                            that s1 holds them already (one 32-bit stamp per tile), 56 of 496 B/point for
+ *                            such a tile.  Results and both state buffers are bit for bit those of 0.  Launches captured into a
+ *                            HIP graph, launches with parameter fields or a fused gradient, and every launch after dxm_state_ptr
+ *                            use the kernel of 0; a replayed graph must be reported with dxm_notify_replay as before
  *   "verbose"        0 | 1   host-buffer form: log the chunk timeline, page-locking and upload-mode decisions to stderr (default 0) */
 int dxm_set_option(dxm_material* m, const char* name, double value);
 /* get_initial_state_dict / get_final_state_dict without a device array of the caller: packs the
