@@ -19,6 +19,7 @@ LAW_RAMBERG_OSGOOD = 5
 LAW_OGDEN = 7   # (6 is not assigned)
 LAW_HOSFORD_LINEAR = 10   # (8 and 9 are not assigned)
 LAW_ORTHOTROPIC_ELASTIC = 12   # (11 is not assigned)
+LAW_SINGLE_CRYSTAL_FCC = 14   # (13 is not assigned)
 S0, S1 = 0, 1
 
 

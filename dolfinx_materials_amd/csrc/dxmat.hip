@@ -34,6 +34,7 @@
 #include "hyperelastic.hpp"
 #include "hosford.hpp"
 #include "orthotropic.hpp"
+#include "single_crystal.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -114,6 +115,7 @@ struct LaunchArgs {
   const MeshSource* fused;   // gradient evaluated inside the kernel from this mesh; null: read from `grad`
   int tl;                    // tangent layout of THIS launch (the host path may ask for the coefficient form although the
                              // handle's layout is the full block: it rebuilds the block on the host)
+  double dt;                 // the time increment of the call: read by the rate-dependent laws only (LawDesc::rate_dependent)
 };
 
 constexpr unsigned L_FULL = 1u << TL_FULL, L_SYM = 1u << TL_SYM, L_COEF = 1u << TL_COEF, L_PACK4 = 1u << TL_PACK4;
@@ -146,6 +148,7 @@ struct LawDesc {
   const char* no_frame;                   // null: the kernel reads a material frame (dxm_set_frame*); else the refusal
   const char* frame_kernel[2];            // the kernel while a uniform frame / a frame field is bound
   void (*launch)(const LaunchArgs& a);    // null: not launchable in this build
+  bool rate_dependent;                    // the update reads the dt of the dxm_integrate* call; the other laws ignore it
 };
 
 // ---- parameters: [E, nu, ...] for all laws but Ogden ----
@@ -271,6 +274,22 @@ static int build_orthotropic(const double* p, LawParams& q) {
   return 0;
 }
 
+// [E1, E2, E3, nu12, nu23, nu13, G12, G23, G13, n, K, tau0, Q, b, d, C, h_self, h_coplanar, h_Hirth, h_collinear, h_glissile, h_Lomer]:
+// the stiffness is the orthotropic law's, in the same twelve doubles; the rest is read from the handle's parameters by the launcher
+static int build_single_crystal(const double* p, LawParams& q) {
+  static const char* const names[13] = {"n", "K", "tau0", "Q", "b", "d", "C", "h_self", "h_coplanar", "h_Hirth", "h_collinear", "h_glissile", "h_Lomer"};
+  for (int k = 9; k < 22; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "single-crystal viscoplasticity: %s must be finite, got %g", names[k - 9], p[k]);
+  if (int rc = build_orthotropic(p, q)) return rc;
+  if (!(p[9] >= 1.0)) return fail(-1, "single-crystal viscoplasticity: the Norton exponent n must be >= 1, got %g", p[9]);
+  if (!(p[10] > 0.0)) return fail(-1, "single-crystal viscoplasticity: K must be > 0, got %g", p[10]);
+  if (!(p[11] >= 0.0)) return fail(-1, "single-crystal viscoplasticity: tau0 must be >= 0, got %g", p[11]);
+  if (!(p[13] >= 0.0)) return fail(-1, "single-crystal viscoplasticity: b must be >= 0, got %g", p[13]);
+  if (!(p[14] >= 0.0)) return fail(-1, "single-crystal viscoplasticity: d must be >= 0, got %g", p[14]);
+  if (!(p[15] >= 0.0)) return fail(-1, "single-crystal viscoplasticity: C must be >= 0, got %g", p[15]);
+  return 0;
+}
+
 // ---- launchers (defined in the launch section, where the handle is complete) ----
 template <int LAW> static void launch_small_strain(const LaunchArgs& a);
 static void launch_fefp_voce(const LaunchArgs& a);
@@ -279,6 +298,7 @@ static void launch_ramberg_osgood(const LaunchArgs& a);
 static void launch_ogden(const LaunchArgs& a);
 static void launch_hosford(const LaunchArgs& a);
 static void launch_orthotropic(const LaunchArgs& a);
+static void launch_single_crystal(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -300,7 +320,7 @@ static void launch_orthotropic(const LaunchArgs& a);
 
 // what every isotropic law answers dxm_set_frame* with
 constexpr const char* kNoFrame = "this law is isotropic: a material frame changes nothing in its update, and accepting one would hide a "
-                                 "mistake of the caller (frames are read by DXM_LAW_ORTHOTROPIC_ELASTIC)";
+                                 "mistake of the caller (frames are read by DXM_LAW_ORTHOTROPIC_ELASTIC and DXM_LAW_SINGLE_CRYSTAL_FCC)";
 
 constexpr void state_field(LawDesc& d, int f, const char* name, int dim, int slot) {
   d.isv_name[f] = name; d.isv_dim[f] = dim; d.isv_slot[f] = slot;
@@ -485,10 +505,44 @@ constexpr LawDesc law_orthotropic() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9 and 11 are not assigned and stay empty rows (law_known)
+// FCC single-crystal viscoplasticity: strain in (48 B) and slips, cumulated slips, back strains read (288); stress (48), the
+// non-symmetric tangent (288) and the four state fields (336) out: 1008 B/point, plus nine 8 B streams with a frame field
+constexpr LawDesc law_single_crystal() {
+  LawDesc d{};
+  d.id = DXM_LAW_SINGLE_CRYSTAL_FCC;
+  d.n_grad = d.n_flux = 6;
+  d.n_params = d.n_params_custom = 22;
+  d.n_isv_fields = d.n_fields = 4;
+  state_field(d, 0, "ElasticStrain", 6, SC_SLOT_EEL);
+  state_field(d, 1, "ViscoplasticSlip", 12, SC_SLOT_G);
+  state_field(d, 2, "EquivalentViscoplasticSlip", 12, SC_SLOT_P);
+  state_field(d, 3, "BackStrain", 12, SC_SLOT_A);
+  d.n_slots = SC_NSLOTS;
+  d.alg_bytes = 1008;
+  d.kernel = "single_crystal_kernel<0";
+  d.frame_kernel[0] = "single_crystal_kernel<1";
+  d.frame_kernel[1] = "single_crystal_kernel<2";
+  d.no_fields = "per-point parameter fields are not served for single-crystal viscoplasticity: its constants are formed once per handle";
+  d.build = build_single_crystal;
+  d.stock_only = "single-crystal viscoplasticity has no isotropic hardening law to replace: it is served by the stock libdxmat, not by a "
+                 "custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(single_crystal_kernel_fn);
+  d.blocks_per_cu = SC_BLOCKS_PER_CU;   // single_crystal.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.set_refusal = "the single-crystal tangent is not symmetric (interaction hardening): only DXM_TANGENT_FULL is available, no packed "
+                  "record (sym / coef / pack4) exists for this law";
+  d.launch_refusal = "the single-crystal tangent is not symmetric: only the full 36-entry block exists for this law";
+  d.no_fused = "the single-crystal kernel has no fused displacement-gradient form: set option fused_gradient to 0 (the strain is then "
+               "evaluated by the gradient kernel) or pass the strain as an array";
+  d.launch = DXM_STOCK_ONLY(launch_single_crystal);   // single_crystal.hip: strain from the (N, 6) array, the handle's frame, dt
+  d.rate_dependent = true;
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11 and 13 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
-    law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(),
+    law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(),
 };
 
 constexpr bool rows_in_place() {
@@ -497,7 +551,8 @@ constexpr bool rows_in_place() {
   return true;
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
-static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel, "ids 6, 8, 9 and 11 are not assigned");
+static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel,
+              "ids 6, 8, 9, 11 and 13 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -614,6 +669,7 @@ struct dxm_material {
   double* pf_law[2] = {nullptr, nullptr};   // device copies of the E / nu fields, n doubles each
   double* pf_stream[PF_COUNT] = {};         // device streams (lambda, mu, sig0, h1, h2), n doubles each; null = uniform
   // material frame (dxm_set_frame*; the laws whose row has no `no_frame`): 0 none (identity), 1 uniform, 2 one per Gauss point
+  double dt = 0.0;                          // the time increment of the call in progress (the rate-dependent laws; take_dt)
   int frame_kind = 0;
   Frame9 frame_uniform{};
   double* frame_streams = nullptr;          // the field as nine SoA streams of ld doubles each (the kernel reads 8 B per lane)
@@ -657,6 +713,22 @@ static int build_params(dxm_material* m, const double* p, int np) {
   m->prm = q;
   m->raw_params.assign(p, p + np);
   return 0;
+}
+
+// What every dxm_integrate* form does with its dt: a rate-dependent law keeps it for its launches (a captured graph bakes it in),
+// every other law ignores it as it always has.  A null handle is reported by the form itself.
+static int take_dt(dxm_material* m, double dt) {
+  if (!m || !kLaws[m->law].rate_dependent) return 0;
+  if (!std::isfinite(dt) || dt < 0.0) return fail(-1, "law %d is rate-dependent: dt must be finite and >= 0, got %g", m->law, dt);
+  m->dt = dt;
+  return 0;
+}
+
+// the widest state field: the AoS scratch of dxm_set_state / dxm_get_state holds one field
+static int widest_field(const LawDesc& d) {
+  int w = 6;
+  for (int f = 0; f < d.n_fields; ++f) w = d.isv_dim[f] > w ? d.isv_dim[f] : w;
+  return w;
 }
 
 static int tangent_size(const dxm_material* m) {
@@ -1073,7 +1145,7 @@ int dxm_set_state(dxm_material* m, int which, int field, const double* host_aos)
   if (int rc = materialize_s1(m)) return rc;
   // upload the AoS block and transpose on the device (a host-side transposition of 6 x 1e7
   // doubles costs more than the PCIe transfer)
-  if (!m->d_field) HIP_TRY(hipMalloc(&m->d_field, sizeof(double) * n * 6));
+  if (!m->d_field) HIP_TRY(hipMalloc(&m->d_field, sizeof(double) * n * widest_field(d)));
   PackMap map{};
   map.n = dim;
   for (int c = 0; c < dim; ++c) map.slot[c] = d.isv_slot[field] + c;
@@ -1097,7 +1169,7 @@ int dxm_get_state(dxm_material* m, int which, int field, double* host_aos) {
   const int dim = d.isv_dim[field];
   const int64_t n = m->n;
   if (n == 0) return 0;
-  if (!m->d_field) HIP_TRY(hipMalloc(&m->d_field, sizeof(double) * n * 6));
+  if (!m->d_field) HIP_TRY(hipMalloc(&m->d_field, sizeof(double) * n * widest_field(d)));
   PackMap map{};
   map.n = dim;
   for (int c = 0; c < dim; ++c) map.slot[c] = d.isv_slot[field] + c;
@@ -1301,6 +1373,20 @@ static void launch_orthotropic(const LaunchArgs& a) {
   orthotropic_launch(m->frame_kind, a.tl, a.grid, a.st, m->prm, a.cnt, a.grad, m->frame_uniform,
                      m->frame_streams ? m->frame_streams + a.off : nullptr, m->ld, a.flux, a.ct, m->d_stats + a.stats_off);
 }
+
+static void launch_single_crystal(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  const double* p = m->raw_params.data();   // 22 values (build_single_crystal)
+  ScParams sp{};
+  sp.n = p[9]; sp.K = p[10]; sp.tau0 = p[11]; sp.b = p[13]; sp.d = p[14]; sp.C = p[15];
+  for (int k = 0; k < 6; ++k) sp.qh[k] = p[12] * p[16 + k];
+  sp.guard = 1.1 * sp.K;
+  sp.floor_f = 1e-12 * ortho_load(m->prm).c[0];
+  sp.dt = a.dt;
+  single_crystal_launch(m->frame_kind, a.grid, a.st, m->prm, sp, a.cnt, a.grad, m->frame_uniform,
+                        m->frame_streams ? m->frame_streams + a.off : nullptr, m->ld, m->state[0] + a.off, m->state[1] + a.off, m->ld,
+                        a.flux, a.ct, m->d_stats + a.stats_off);
+}
 #endif
 
 // tl: tangent layout of THIS launch (LaunchArgs)
@@ -1318,7 +1404,7 @@ static int launch_range(dxm_material* m, int64_t off, int64_t cnt, const double*
   if (!d.launch) return fail(-1, "law %d not launchable", m->law);
   if (fused && d.no_fused) return fail(-1, "%s", d.no_fused);
   if (!(d.launch_layouts & (1u << tl))) return fail(-1, "%s", d.launch_refusal);
-  d.launch(LaunchArgs{m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl});
+  d.launch(LaunchArgs{m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl, m->dt});
   HIP_TRY(hipGetLastError());
   *grid_out = grid;
   return 0;
@@ -1347,8 +1433,8 @@ extern "C" {
 
 int dxm_integrate_device(dxm_material* m, const double* grad_dev, double dt, double* flux_dev,
                          double* ct_dev, void* hip_stream) {
-  (void)dt;  // rate-independent laws; QuadratureMap never forwards dt (quadrature_map.py:321)
   if (!m) return fail(-1, "null handle");
+  if (int rc = take_dt(m, dt)) return rc;   // read by the rate-dependent laws only; QuadratureMap never forwards dt (quadrature_map.py:321)
   if (m->n > 0 && (!grad_dev || !flux_dev || !ct_dev)) return fail(-1, "null device pointer");
   DEVICE_GUARD(m);
   return launch(m, grad_dev, flux_dev, ct_dev, (hipStream_t)hip_stream);
@@ -1381,6 +1467,18 @@ static int pack_isv_range(dxm_material* m, int which, int64_t off, int64_t cnt, 
                           hipStream_t st) {
   const LawDesc& d = kLaws[m->law];
   const int total = isv_total(d);
+#ifndef DXM_CUSTOM_HARDENING
+  if (total > (int)(sizeof(PackMap::slot) / sizeof(int))) {   // wider than the slot map: served where the visible fields are consecutive slots
+    int next = d.isv_slot[0];
+    for (int f = 0; f < d.n_isv_fields; ++f) {
+      if (d.isv_slot[f] != next) return fail(-1, "internal: %d visible state numbers exceed the slot map and are not in consecutive slots", total);
+      next += d.isv_dim[f];
+    }
+    pack_consecutive_slots(state_of(m, which) + off, m->ld, cnt, d.isv_slot[0], total, isv_aos_dev, st);
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
+#endif
   PackMap map{};
   map.n = total;
   int k = 0;
@@ -1799,14 +1897,14 @@ static int integrate_host(dxm_material* m, const double* grad_aos, double* flux_
 
 int dxm_integrate(dxm_material* m, const double* grad_aos, double dt, double* flux_aos,
                   double* isv_aos, double* ct_aos, dxm_stats* stats) {
-  (void)dt;
+  if (int rc = take_dt(m, dt)) return rc;
   return integrate_host(m, grad_aos, flux_aos, isv_aos, ct_aos, stats, nullptr);
 }
 
 int dxm_integrate_rows(dxm_material* m, const double* grad_aos, double dt, double* flux_rows, double* ct_rows,
                        const int64_t* rows, dxm_stats* stats) {
-  (void)dt;
   if (!m) return fail(-1, "null handle");
+  if (int rc = take_dt(m, dt)) return rc;
   if (m->n > 0 && (!flux_rows || !ct_rows || !rows)) return fail(-1, "dxm_integrate_rows needs the flux array, the tangent array and the row index");
   return integrate_host(m, grad_aos, flux_rows, nullptr, ct_rows, stats, rows);
 }
@@ -2061,22 +2159,22 @@ static int integrate_displacement_host(dxm_material* m, dxm_mesh* mesh, const do
 
 int dxm_integrate_displacement(dxm_material* m, dxm_mesh* mesh, const double* u_host, double dt,
                                double* flux_aos, double* isv_aos, double* ct_aos, dxm_stats* stats) {
-  (void)dt;
+  if (int rc = take_dt(m, dt)) return rc;
   return integrate_displacement_host(m, mesh, u_host, flux_aos, isv_aos, ct_aos, stats, nullptr);
 }
 
 int dxm_integrate_displacement_rows(dxm_material* m, dxm_mesh* mesh, const double* u_host, double dt, double* flux_rows,
                                     double* ct_rows, const int64_t* rows, dxm_stats* stats) {
-  (void)dt;
   if (!m) return fail(-1, "null argument");
+  if (int rc = take_dt(m, dt)) return rc;
   if (m->n > 0 && (!flux_rows || !ct_rows || !rows)) return fail(-1, "dxm_integrate_displacement_rows needs the flux array, the tangent array and the row index");
   return integrate_displacement_host(m, mesh, u_host, flux_rows, nullptr, ct_rows, stats, rows);
 }
 
 int dxm_integrate_displacement_device(dxm_material* m, dxm_mesh* mesh, const double* u_dev, double dt,
                                       double* flux_dev, double* ct_dev, void* hip_stream) {
-  (void)dt;
   if (!m || !mesh) return fail(-1, "null argument");
+  if (int rc = take_dt(m, dt)) return rc;
   if (mesh->device != m->device) return fail(-1, "mesh and material live on different devices");
   if (dxm_mesh_npoints(mesh) != m->n) return fail(-1, "mesh has %lld Gauss points, material %lld",
                                                    (long long)dxm_mesh_npoints(mesh), (long long)m->n);

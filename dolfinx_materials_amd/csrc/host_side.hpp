@@ -432,12 +432,13 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   p.req = r;
   // Ogden: the kernel writes the 81 entries only (no record to rebuild from): they are downloaded as they are, and the rows forms
   // move them like a handle's own packed layout
-  const bool plain81 = r.law == DXM_LAW_OGDEN;
+  // single-crystal viscoplasticity: the same for its 36 entries (the block is not symmetric: no packed record)
+  const bool plain_block = r.law == DXM_LAW_OGDEN || r.law == DXM_LAW_SINGLE_CRYSTAL_FCC;
   // Hosford: a general symmetric 6x6 with no coefficient form.  A full-layout handle's packed transfer is the kernel's 21
   // upper-triangle entries (168 instead of 288 B/point), mirrored into the block by the workers; a "sym" handle downloads its 21
   // orthotropic elasticity: the same (Q^T C Q is a general symmetric 6x6 per point)
   const bool gsym = r.law == DXM_LAW_HOSFORD_LINEAR || r.law == DXM_LAW_ORTHOTROPIC_ELASTIC;
-  const bool fefp = r.n_grad == 9 && !plain81, elastic = r.law == DXM_LAW_ELASTIC_ISO;
+  const bool fefp = r.n_grad == 9 && !plain_block, elastic = r.law == DXM_LAW_ELASTIC_ISO;
   int total = 0;
   for (int f = 0; f < r.n_isv_fields; ++f) total += r.isv_dim[f];
   // rows (dxm_integrate_rows: J2 laws, full layout, flux and tangent requested): flux_aos / ct_aos are the BASES of larger
@@ -452,10 +453,10 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   // page-locked memory like the pack4 form below, else the kernel's own 21 entries are downloaded
   const bool sym_packed = !r.rows && r.packed_transfer >= 2 && r.layout == DXM_TANGENT_SYM && !elastic && !fefp && !gsym && r.ct && r.flux &&
                           r.n >= r.packed_min_points && flux_locked;
-  p.packed = r.rows || sym_packed || (r.packed_transfer && r.layout == DXM_TANGENT_FULL && r.ct && r.n >= r.packed_min_points && !plain81);
+  p.packed = r.rows || sym_packed || (r.packed_transfer && r.layout == DXM_TANGENT_FULL && r.ct && r.n >= r.packed_min_points && !plain_block);
   // the rows forms of a handle whose OWN layout is packed (sym / coef / pack4): the kernel writes that layout, it lands in the
   // library's page-locked area like the stress, and the worker threads MOVE point i to row rows[i] -- nothing is rebuilt
-  const bool rows_plain = r.rows && (r.layout != DXM_TANGENT_FULL || plain81);
+  const bool rows_plain = r.rows && (r.layout != DXM_TANGENT_FULL || plain_block);
   const bool constant = p.packed && !rows_plain && elastic;   // the elastic block is a constant and is only filled in
   // small strain: (c1, c2, c3, w) only -- the direction n is rebuilt from the stress, which the caller receives in
   // page-locked memory as part of the same chunk -- else the nine coefficients

@@ -418,5 +418,81 @@ class OrthotropicElasticity(SmallStrainBehavior):
         return {g: getattr(self, k) for g, k in zip(self.MFRONT_NAMES, self.NAMES)}
 
 
+class MericCailletaudSingleCrystalViscoPlasticity(OrthotropicElasticity):
+    """Small-strain FCC single-crystal viscoplasticity (the reference's ``MericCailletaudSingleCrystalViscoPlasticity`` MFront
+    behaviour, ``tests/mfront/test_elastoplasticity.py::test_mfront_single_cristal``): the orthotropic elasticity of
+    :class:`OrthotropicElasticity`, twelve ``{111}<01-1>`` slip systems with Norton flow ``(f/K)^n``, nonlinear isotropic hardening
+    ``tau0 + Q sum_j h_ij (1 - exp(-b p_j))`` through the six-coefficient interaction matrix ``h = [self, coplanar, Hirth,
+    collinear, glissile, Lomer]``, and Armstrong-Frederick kinematic hardening ``x = C a``.  Rate-dependent: the time increment is
+    ``material.dt`` (or the ``dt`` of the call).  Internal state variables, all in the material frame: ``ElasticStrain`` (6),
+    ``ViscoplasticSlip`` (12), ``EquivalentViscoplasticSlip`` (12), ``BackStrain`` (12); the systems are numbered plane-major over
+    (1,1,1), (-1,1,1), (1,-1,1), (1,1,-1), which is this library's order, not necessarily MFront's.
+
+    ``rotation_matrix`` and ``set_frame`` as for :class:`OrthotropicElasticity` (rows = material axes); the frame must not change
+    while slip has accumulated.  Tangent layout ``"full"`` only (the tangent is not symmetric); uniform properties only; the
+    displacement forms need option ``fused_gradient`` off."""
+
+    law = _lib.LAW_SINGLE_CRYSTAL_FCC
+    FLOW_NAMES = ("n", "K", "tau0", "Q", "b", "d", "C")
+    #: the constants of the behaviour file next to the one material property it declares (``YoungModulus1``)
+    MFRONT_DEFAULTS = {"YoungModulus2": 208000.0, "YoungModulus3": 208000.0, "PoissonRatio12": 0.3, "PoissonRatio23": 0.3,
+                       "PoissonRatio13": 0.3, "ShearModulus12": 80000.0, "ShearModulus23": 80000.0, "ShearModulus13": 80000.0}
+    MFRONT_FLOW = {"n": 10.0, "K": 25.0, "tau0": 66.62, "Q": 11.43, "b": 2.1, "d": 494.0, "C": 14363.0}
+    #: the published copper values, [self, coplanar, Hirth, collinear, glissile, Lomer]
+    INTERACTION = (1.0, 1.0, 0.6, 12.3, 1.6, 1.8)
+
+    def __init__(self, E1, E2, E3, nu12, nu23, nu13, G12, G23, G13, n=10.0, K=25.0, tau0=66.62, Q=11.43, b=2.1, d=494.0, C=14363.0,
+                 interaction=INTERACTION):
+        for name, v in zip(self.FLOW_NAMES, (n, K, tau0, Q, b, d, C)):
+            object.__setattr__(self, name, float(v))
+        h = tuple(float(v) for v in interaction)
+        if len(h) != 6:
+            raise ValueError(f"single-crystal viscoplasticity: the interaction matrix takes six coefficients, got {len(h)}")
+        object.__setattr__(self, "interaction", h)
+        super().__init__(E1, E2, E3, nu12, nu23, nu13, G12, G23, G13)
+
+    def validate(self):
+        super().validate()
+        for k in self.FLOW_NAMES:
+            if not _isfinite(getattr(self, k)):
+                raise ValueError(f"single-crystal viscoplasticity: {k} must be finite, got {getattr(self, k)}")
+        for k, v in zip(("h_self", "h_coplanar", "h_Hirth", "h_collinear", "h_glissile", "h_Lomer"), self.interaction):
+            if not _isfinite(v):
+                raise ValueError(f"single-crystal viscoplasticity: {k} must be finite, got {v}")
+        if not self.n >= 1.0:
+            raise ValueError(f"single-crystal viscoplasticity: the Norton exponent n must be >= 1, got {self.n}")
+        if not self.K > 0.0:
+            raise ValueError(f"single-crystal viscoplasticity: K must be > 0, got {self.K}")
+        for k in ("tau0", "b", "d", "C"):
+            if not getattr(self, k) >= 0.0:
+                raise ValueError(f"single-crystal viscoplasticity: {k} must be >= 0, got {getattr(self, k)}")
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict):
+        """``material_properties`` of the reference test: ``{"YoungModulus1": ...}``; the other elastic constants, the flow and
+        hardening parameters and the interaction matrix are those of the behaviour file unless given (glossary names for the
+        elastic constants, ``n, K, tau0, Q, b, d, C``, ``interaction``)."""
+        known = set(cls.MFRONT_NAMES) | set(cls.FLOW_NAMES) | {"interaction"}
+        extra = set(props) - known
+        if "YoungModulus1" not in props or extra:
+            raise ValueError(f"single-crystal material properties: YoungModulus1 is required, unknown {sorted(extra)}")
+        el = {**cls.MFRONT_DEFAULTS, **{k: props[k] for k in cls.MFRONT_NAMES if k in props}}
+        flow = {k: float(props.get(k, v)) for k, v in cls.MFRONT_FLOW.items()}
+        return cls(*(float(el[k]) for k in cls.MFRONT_NAMES), interaction=props.get("interaction", cls.INTERACTION), **flow)
+
+    def __setattr__(self, name, value):
+        if name in self.FLOW_NAMES:
+            object.__setattr__(self, name, float(value))
+        else:
+            super().__setattr__(name, value)
+
+    def params(self):
+        return super().params() + [getattr(self, k) for k in self.FLOW_NAMES] + list(self.interaction)
+
+    def flat_properties(self):
+        return {**super().flat_properties(), **{k: getattr(self, k) for k in self.FLOW_NAMES},
+                **{f"interaction.{i}": v for i, v in enumerate(self.interaction)}}
+
+
 def _isfinite(x):
     return x == x and abs(x) != float("inf")

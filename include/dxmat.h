@@ -120,7 +120,24 @@ enum {
    * dxm_stats: n_nan counts points with a non-finite stress or tangent; n_plastic, n_not_converged, max_local_iters are 0.
    * params = [E1, E2, E3, nu12, nu23, nu13, G12, G23, G13], all finite, E_i > 0, G_ij > 0, compliance positive definite */
   DXM_LAW_ORTHOTROPIC_ELASTIC = 12,   /* id 11 is not assigned */
-  DXM_LAW_COUNT = 13
+  /* small-strain FCC single-crystal viscoplasticity (the reference's MericCailletaudSingleCrystalViscoPlasticity behaviour,
+   * restated from its equations; DESIGN.md section "Single-crystal viscoplasticity" lists them).  Orthotropic stiffness and the
+   * FRAME CONVENTION of DXM_LAW_ORTHOTROPIC_ELASTIC (dxm_set_frame*; gradient, flux and tangent are global).  Twelve {111}<01-1>
+   * systems in the library's own order (plane-major over (1,1,1), (-1,1,1), (1,-1,1), (1,1,-1)): MFront's numbering is not pinned,
+   * so the slip fields compare with MFront's up to a permutation and sign of systems; stress and tangent do not depend on it.
+   * RATE-DEPENDENT: the only law that reads the dt of dxm_integrate* (finite, >= 0, else the call fails; dt = 0 is the elastic
+   * response).  A graph captured around dxm_integrate_device bakes the dt of the capture in.
+   * State, all in the material frame: ElasticStrain (6, written by every update, read by none), ViscoplasticSlip (12),
+   * EquivalentViscoplasticSlip (12), BackStrain (12).  The plastic strain is sum g_i mu_i: a frame that changes while g != 0 is
+   * the caller's business.  The tangent is NOT symmetric: DXM_TANGENT_FULL only.  No per-point parameter fields, no fused
+   * displacement gradient (option fused_gradient 0), not served by a custom-hardening build.
+   * dxm_stats: n_plastic counts points with any f_i > 0 at the trial state; n_not_converged those that reach the iteration cap of
+   * dxm_set_newton (whose rtol is the absolute bound on the slip residuals) or whose trial state trips the f_i > 1.1 K guard -- such
+   * a point writes its elastic trial stress and Q^T D Q and keeps the state bits it read; max_local_iters counts halvings too.
+   * params = [E1, E2, E3, nu12, nu23, nu13, G12, G23, G13, n, K, tau0, Q, b, d, C, h_self, h_coplanar, h_Hirth, h_collinear,
+   * h_glissile, h_Lomer]: all finite, the first nine as for DXM_LAW_ORTHOTROPIC_ELASTIC, n >= 1, K > 0, tau0, b, d, C >= 0 */
+  DXM_LAW_SINGLE_CRYSTAL_FCC = 14,   /* id 13 is not assigned */
+  DXM_LAW_COUNT = 15
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

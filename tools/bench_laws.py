@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -14,6 +14,14 @@ orthotropic: a strongly orthotropic set (E1 / E3 = 20) on the headline strains; 
 random proper rotation per point (dxm_set_frame / dxm_set_frame_field) -- each with three timings, its ratio to the elastic kernel of
 the same process (run `--laws elastic orthotropic`) next to the byte yardsticks 384 / 384 and 456 / 384, and the spread of the elastic
 kernel's own repeats.
+
+single_crystal: the file's constants (YoungModulus1 = 208000, the copper interaction matrix), dt = 0.1, on the 512 directions of the
+`pool` of tests/test_gpu_single_crystal.py, repeated over the batch: a yielded point carries the state of 14 increments of norm 1e-4
+and takes the 15th, an elastic one is virgin at 2e-4.  Nine lines: the three frame states of a handle (none, one uniform frame, one
+frame per point; the history of a point belongs to its frame) x 0 %, 50 % (every other point: 32 per tile, 8 Newton rounds) and 100 %
+yielded points (16 rounds per tile), each with three timings, the
+restatement's iteration count, and its ratio to the J2-linear kernel of the same process (run `--laws j2_linear single_crystal`) next
+to the byte yardstick 1008 (1080) / 496.
 
 --param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
 (dxm_set_param_field; 1 = sig0, 2 = lambda and mu from an E field, 3 = both, 4 / 5 = H | sigu, b as well), in the same process and on
@@ -107,6 +115,86 @@ def probe_ms(g, flux, ct, n, blocks, reps, warmup):
     return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
 
 
+def single_crystal_inputs(n, frame, fraction):
+    """(strain (n, 6), frames or None, state dict by MFront name, yielded mask) of the single_crystal lines: see the module docstring"""
+    import single_crystal_ref as sc
+    from test_gpu_single_crystal import DT, POOL, PRM, make_pool
+
+    pool = make_pool()
+    d = pool["d"]
+    R = {"noframe": None, "uniform": pool["R"][5], "field": pool["R"]}[frame]
+    if frame == "field":
+        st = pool["state"]
+    else:   # the same directions, their history walked under the frame of this line
+        st = sc.zero_state(POOL)
+        for k in range(1, 15):
+            st = sc.next_state(sc.update(k * 1e-4 * d, st, PRM, DT, R=R))
+    idx = np.arange(n) % POOL
+    y = {0.0: np.zeros(n, dtype=bool), 0.5: np.arange(n) % 2 == 0, 1.0: np.ones(n, dtype=bool)}[fraction]
+    eps = np.where(y[:, None], 15e-4, 2e-4) * d[idx]
+    names = {"ElasticStrain": "eel", "ViscoplasticSlip": "g", "EquivalentViscoplasticSlip": "p", "BackStrain": "a"}
+    state = {k: np.ascontiguousarray(np.where(y[:, None], st[v][idx], 0.0)) for k, v in names.items()}
+    frames = None if R is None else (R if frame == "uniform" else np.ascontiguousarray(R[idx]))
+    # the restatement over one period of the inputs: what the kernel's status words are read against
+    m = min(n, 2 * POOL)
+    ref = sc.update(eps[:m], {v: state[k][:m] for k, v in names.items()}, PRM, DT, R=None if R is None else (R if frame == "uniform" else frames[:m]))
+    return eps, frames, state, y, ref
+
+
+def bench_single_crystal(a, j2_linear_ms):
+    """nine lines: frame state x yielded fraction (module docstring)"""
+    import torch
+
+    import dolfinx_materials_amd.materials as jm
+    from dolfinx_materials_amd.jaxmat import JAXMaterial
+    from helpers import to_device
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+    for frame in ("noframe", "uniform", "field"):
+        for fraction in (0.0, 0.5, 1.0):
+            eps, frames, state, y, ref = single_crystal_inputs(n, frame, fraction)
+            m = JAXMaterial(jm.MericCailletaudSingleCrystalViscoPlasticity.from_mfront_properties({"YoungModulus1": 208000.0}))
+            m.set_data_manager(n)
+            m.dt = 0.1
+            if frames is not None:
+                m.set_frame(frames)
+            m.set_initial_state_dict(state)
+            g = to_device(eps)
+            del eps, frames, state
+            flux = torch.empty((n, 6), dtype=torch.float64, device=g.device)
+            ct = torch.empty((n, 36), dtype=torch.float64, device=g.device)
+
+            def timed():
+                for _ in range(a.warmup):
+                    m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)   # every launch reads the same s0: no advance
+                torch.cuda.synchronize()
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+                for e0, e1 in ev:
+                    e0.record()
+                    m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+                    e1.record()
+                torch.cuda.synchronize()
+                return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+            t = [timed(), timed(), timed()]
+            ms = float(np.median(t))
+            rc, stats = m.stats()
+            ab = m.algorithmic_bytes_per_point
+            r = {"law": f"single_crystal+{frame}+yielded{int(100 * fraction)}", "points": n, "dt": 0.1, "kernel": m.kernel_name,
+                 "kernel_ms_repeats": [round(x, 4) for x in t], "kernel_ms": round(ms, 4), "Mpoints_per_s": round(n / ms / 1e3, 1),
+                 "algorithmic_bytes_per_point": ab, "GBs": round(ab * n / ms / 1e6, 1), "frac_of_8TBs": round(ab * n / ms / 1e6 / 8000, 4),
+                 "plastic_fraction": round(stats["n_plastic"] / n, 4), "plastic_fraction_asked": round(float(y.mean()), 4),
+                 "max_local_iters": stats["max_local_iters"], "restatement_max_iters": int(ref["iters"].max(initial=0)),
+                 "not_converged": stats["n_not_converged"], "nan": stats["n_nan"], "rc": rc}
+            if j2_linear_ms:
+                r["ratio_to_j2_linear"] = round(ms / j2_linear_ms, 3)
+                r["byte_ratio_to_j2_linear"] = round(ab / 496, 3)
+            print(json.dumps(r), flush=True)
+            del m, g, flux, ct
+            torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -120,8 +208,8 @@ def main():
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
-    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws):
-        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford or orthotropic law")
+    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws):
+        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic or single-crystal law")
     import torch
 
     import dolfinx_materials_amd.materials as jm
@@ -137,6 +225,9 @@ def main():
     j2_linear_ms = None
     elastic_repeats = None
     for law in a.laws:
+        if law == "single_crystal":   # its own inputs, state and nine lines
+            bench_single_crystal(a, j2_linear_ms)
+            continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
             beh, hist = jm.RambergOsgoodNonLinearElasticity(jm.LinearElasticIsotropic(E=RO_E, nu=RO_NU), RO_SIG0, RO_ALPHA, RO_N), [ro_eps, ro_eps]
