@@ -20,6 +20,8 @@ LAW_OGDEN = 7   # (6 is not assigned)
 LAW_HOSFORD_LINEAR = 10   # (8 and 9 are not assigned)
 LAW_ORTHOTROPIC_ELASTIC = 12   # (11 is not assigned)
 LAW_SINGLE_CRYSTAL_FCC = 14   # (13 is not assigned)
+LAW_HEAT_STATIONARY, LAW_HEAT_PHASE_CHANGE = 16, 17   # (15 is not assigned)
+DXM_MAX_EXTERNAL_STATE, DXM_MAX_TANGENT_BLOCKS = 2, 4
 S0, S1 = 0, 1
 
 
@@ -37,6 +39,25 @@ class LawInfo(C.Structure):
         ("isv_name", C.c_char_p * DXM_MAX_STATE_FIELDS),
         ("n_isv_total", C.c_int32),
         ("algorithmic_bytes_per_point", C.c_int32),
+    ]
+
+
+class TangentBlock(C.Structure):
+    _fields_ = [("row_kind", C.c_int32), ("row_index", C.c_int32), ("col_kind", C.c_int32), ("col_index", C.c_int32),
+                ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
+class LawBlocks(C.Structure):
+    """``dxm_law_blocks``: the external state variables of a law and the blocks of its tangent."""
+
+    _fields_ = [
+        ("n_external", C.c_int32),
+        ("n_blocks", C.c_int32),
+        ("tangent_width", C.c_int32),
+        ("reserved", C.c_int32),
+        ("external_name", C.c_char_p * DXM_MAX_EXTERNAL_STATE),
+        ("external_default", C.c_double * DXM_MAX_EXTERNAL_STATE),
+        ("block", TangentBlock * DXM_MAX_TANGENT_BLOCKS),
     ]
 
 
@@ -71,6 +92,11 @@ SYMBOLS = {
     "dxm_last_error": (C.c_char_p, []),
     "dxm_device_count": (C.c_int, []),
     "dxm_law_info_get": (C.c_int, [C.c_int, C.POINTER(LawInfo)]),
+    "dxm_law_blocks_get": (C.c_int, [C.c_int, C.POINTER(LawBlocks)]),
+    "dxm_set_external_state": (C.c_int, [_h, C.c_int, C.c_void_p]),
+    "dxm_set_external_state_uniform": (C.c_int, [_h, C.c_int, C.c_double]),
+    "dxm_set_external_state_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_void_p]),
+    "dxm_external_state_kind": (C.c_int, [_h, C.c_int]),
     "dxm_create": (_h, [C.c_int, _dp, C.c_int, C.c_int64, C.c_int]),
     "dxm_destroy": (C.c_int, [_h]),
     "dxm_npoints": (C.c_int64, [_h]),
@@ -367,3 +393,10 @@ def law_info(law: int, lib=None) -> LawInfo:
     lib = lib or load()
     check(lib.dxm_law_info_get(law, C.byref(info)), lib)
     return info
+
+
+def law_blocks(law: int, lib=None) -> LawBlocks:
+    out = LawBlocks()
+    lib = lib or load()
+    check(lib.dxm_law_blocks_get(law, C.byref(out)), lib)
+    return out

@@ -35,6 +35,7 @@
 #include "hosford.hpp"
 #include "orthotropic.hpp"
 #include "single_crystal.hpp"
+#include "heat_transfer.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -84,6 +85,22 @@ struct DeviceGuard {
 #define DEVICE_GUARD(m)                                                        \
   DeviceGuard _guard((m)->device);                                             \
   if (!_guard.ok) return fail(-2, "hipSetDevice(%d) failed", (m)->device)
+
+// A handle, a mesh or a page-locked block may be released while ANOTHER part of the application is capturing a stream on this thread:
+// a garbage collector runs finalizers wherever it likes, inside `with torch.cuda.graph(...)` for one, whose capture mode is global, and
+// there a free or a wait counts as an unsafe call that invalidates the capture (hipErrorStreamCaptureInvalidated at its next launch).
+// What is released here is no part of that capture, so the releasing calls run in the thread's relaxed mode.
+struct RelaxedCaptureMode {
+  hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+  bool swapped = false;
+  RelaxedCaptureMode() {
+    swapped = hipThreadExchangeStreamCaptureMode(&mode) == hipSuccess;
+    if (!swapped) (void)hipGetLastError();
+  }
+  ~RelaxedCaptureMode() {
+    if (swapped && hipThreadExchangeStreamCaptureMode(&mode) != hipSuccess) (void)hipGetLastError();
+  }
+};
 
 // ------------------------------------------------------------------------------------------
 // law descriptors: one row of kLaws per law carries everything that law decides; the host code below reads the row of the
@@ -147,9 +164,21 @@ struct LawDesc {
   const char* no_fused;                   // null: the kernel can evaluate the displacement gradient itself; else the refusal
   const char* no_frame;                   // null: the kernel reads a material frame (dxm_set_frame*); else the refusal
   const char* frame_kernel[2];            // the kernel while a uniform frame / a frame field is bound
+  const char* ext_kernel;                 // the kernel while an external state variable is held as a field
   void (*launch)(const LaunchArgs& a);    // null: not launchable in this build
   bool rate_dependent;                    // the update reads the dt of the dxm_integrate* call; the other laws ignore it
+  // external state variables (scalars, one value per point: dxm_set_external_state*) and the blocks of the tangent
+  int n_ext;
+  const char* ext_name[DXM_MAX_EXTERNAL_STATE];
+  double ext_default[DXM_MAX_EXTERNAL_STATE];
+  int n_blocks;                           // 0: the single block n_flux x n_grad
+  dxm_tangent_block blocks[DXM_MAX_TANGENT_BLOCKS];
+  int ct_full;                            // doubles per point of the full tangent; 0: n_flux * n_grad (ct_full_of)
+  const char* no_displacement;            // null: the gradient may be evaluated from a displacement (dxm_integrate_displacement*); else the refusal
 };
+
+// doubles per point of the full tangent layout: the sum of the law's blocks
+constexpr int ct_full_of(const LawDesc& d) { return d.ct_full ? d.ct_full : d.n_flux * d.n_grad; }
 
 // ---- parameters: [E, nu, ...] for all laws but Ogden ----
 static int elastic_constants(const double* p, LawParams& q) {
@@ -290,6 +319,24 @@ static int build_single_crystal(const double* p, LawParams& q) {
   return 0;
 }
 
+// [A, B]: A + B T <= 0 is the caller's business, as it is MFront's
+static int build_heat_stationary(const double* p, LawParams&) {
+  static const char* const names[2] = {"A", "B"};
+  for (int k = 0; k < 2; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "stationary heat transfer: %s must be finite, got %g", names[k], p[k]);
+  return 0;
+}
+
+// [Tm, ks, cs, kl, cl, dhsl, Tsmooth]; what the kernel reads is formed by the launcher (heat_transfer.hpp: HeatParams)
+static int build_heat_phase_change(const double* p, LawParams&) {
+  static const char* const names[7] = {"MeltingTemperature", "SolidConductivity", "SolidHeatCapacity", "LiquidConductivity", "LiquidHeatCapacity",
+                                       "FusionEnthalpy", "Tsmooth"};
+  for (int k = 0; k < 7; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "heat transfer with phase change: %s must be finite, got %g", names[k], p[k]);
+  if (!(p[6] > 0.0)) return fail(-1, "heat transfer with phase change: Tsmooth must be > 0, got %g", p[6]);
+  return 0;
+}
+
 // ---- launchers (defined in the launch section, where the handle is complete) ----
 template <int LAW> static void launch_small_strain(const LaunchArgs& a);
 static void launch_fefp_voce(const LaunchArgs& a);
@@ -299,6 +346,8 @@ static void launch_ogden(const LaunchArgs& a);
 static void launch_hosford(const LaunchArgs& a);
 static void launch_orthotropic(const LaunchArgs& a);
 static void launch_single_crystal(const LaunchArgs& a);
+static void launch_heat_stationary(const LaunchArgs& a);
+static void launch_heat_phase_change(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -539,10 +588,81 @@ constexpr LawDesc law_single_crystal() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11 and 13 are not assigned and stay empty rows (law_known)
+constexpr dxm_tangent_block tangent_block(int row_kind, int row_index, int col_kind, int col_index, int rows, int cols) {
+  return dxm_tangent_block{row_kind, row_index, col_kind, col_index, rows, cols};
+}
+
+// The two heat-transfer laws (heat_transfer.hip): temperature gradient in (24 B), heat flux (24) and the blocks of the tangent out;
+// the temperature is an external state variable, a kernel argument or one more 8 B stream (dxm_algorithmic_bytes)
+constexpr LawDesc heat_law(int id, int n_params, const char* kernel) {
+  LawDesc d{};
+  d.id = id;
+  d.n_grad = d.n_flux = 3;
+  d.n_params = d.n_params_custom = n_params;
+  d.kernel = kernel;
+  d.n_ext = 1;
+  d.ext_name[0] = "Temperature";
+  d.ext_default[0] = 293.15;   // mfront.py:109-110
+  d.blocks[0] = tangent_block(DXM_BLOCK_ROW_FLUX, 0, DXM_BLOCK_COL_GRADIENT, 0, 3, 3);
+  d.blocks[1] = tangent_block(DXM_BLOCK_ROW_FLUX, 0, DXM_BLOCK_COL_EXTERNAL, 0, 3, 1);
+  d.n_blocks = 2;
+  d.ct_full = 12;
+  d.blocks_per_cu = HT_BLOCKS_PER_CU;   // heat_transfer.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  return d;
+}
+
+// counted as 120 B/point: temperature gradient in (24) and tangent out (96); with the flux (24) the kernel moves 144
+constexpr LawDesc law_heat_stationary() {
+  LawDesc d = heat_law(DXM_LAW_HEAT_STATIONARY, 2, "heat_transfer_kernel<0, 0");
+  d.alg_bytes = 120;
+  d.ext_kernel = "heat_transfer_kernel<0, 1";
+  d.build = build_heat_stationary;
+  d.residency_kernel = DXM_STOCK_ONLY(heat_stationary_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_heat_stationary);
+  d.no_fields = "per-point parameter fields are not served for stationary heat transfer: A and B are per-handle constants (the "
+                "temperature is an external state variable: dxm_set_external_state)";
+  d.stock_only = "stationary heat transfer has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build";
+  // (one sentence: the host path asks these laws for no other layout than the handle's, so a launch never meets the second check)
+  d.set_refusal = d.launch_refusal = "the stationary heat-transfer tangent is two blocks of 9 + 3 entries, not a symmetric 6x6: only "
+                                     "DXM_TANGENT_FULL is available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fused = d.no_displacement = "stationary heat transfer takes a temperature gradient, not a strain or a deformation gradient: the "
+                                   "displacement forms (dxm_integrate_displacement*) do not apply; pass grad(T) as an array";
+  d.no_frame = "stationary heat transfer is isotropic (a scalar conductivity): a material frame changes nothing in its update";
+  return d;
+}
+
+// counted as 136 B/point: gradient in (24), tangent (104) and enthalpy (8) out; with the flux (24) the kernel moves 160.  The
+// enthalpy is written, never read
+constexpr LawDesc law_heat_phase_change() {
+  LawDesc d = heat_law(DXM_LAW_HEAT_PHASE_CHANGE, 7, "heat_transfer_kernel<1, 0");
+  d.alg_bytes = 136;
+  d.ext_kernel = "heat_transfer_kernel<1, 1";
+  d.n_isv_fields = d.n_fields = 1;
+  state_field(d, 0, "Enthalpy", 1, 0);
+  d.n_slots = 1;
+  d.blocks[2] = tangent_block(DXM_BLOCK_ROW_STATE, 0, DXM_BLOCK_COL_EXTERNAL, 0, 1, 1);
+  d.n_blocks = 3;
+  d.ct_full = 13;
+  d.build = build_heat_phase_change;
+  d.residency_kernel = DXM_STOCK_ONLY(heat_phase_change_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_heat_phase_change);
+  d.no_fields = "per-point parameter fields are not served for heat transfer with phase change: its constants are formed once per "
+                "handle (the temperature is an external state variable: dxm_set_external_state)";
+  d.stock_only = "heat transfer with phase change has no hardening law: it is served by the stock libdxmat, not by a custom-hardening build";
+  d.set_refusal = d.launch_refusal = "the phase-change tangent is three blocks of 9 + 3 + 1 entries, not a symmetric 6x6: only "
+                                     "DXM_TANGENT_FULL is available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fused = d.no_displacement = "heat transfer with phase change takes a temperature gradient, not a strain or a deformation gradient: "
+                                   "the displacement forms (dxm_integrate_displacement*) do not apply; pass grad(T) as an array";
+  d.no_frame = "heat transfer with phase change is isotropic (a scalar conductivity): a material frame changes nothing in its update";
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13 and 15 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
-    law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(),
+    law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
+    law_heat_stationary(), law_heat_phase_change(),
 };
 
 constexpr bool rows_in_place() {
@@ -551,8 +671,8 @@ constexpr bool rows_in_place() {
   return true;
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
-static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel,
-              "ids 6, 8, 9, 11 and 13 are not assigned");
+static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel,
+              "ids 6, 8, 9, 11, 13 and 15 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -670,6 +790,11 @@ struct dxm_material {
   double* pf_stream[PF_COUNT] = {};         // device streams (lambda, mu, sig0, h1, h2), n doubles each; null = uniform
   // material frame (dxm_set_frame*; the laws whose row has no `no_frame`): 0 none (identity), 1 uniform, 2 one per Gauss point
   double dt = 0.0;                          // the time increment of the call in progress (the rate-dependent laws; take_dt)
+  // external state variables (dxm_set_external_state*; LawDesc::n_ext): 0 uniform (a kernel argument), 1 field (the handle's own
+  // device copy, n doubles, allocated by the first field and kept until dxm_destroy: rewriting a field keeps its address)
+  int ext_kind[DXM_MAX_EXTERNAL_STATE] = {};
+  double ext_uniform[DXM_MAX_EXTERNAL_STATE] = {};
+  double* ext_field[DXM_MAX_EXTERNAL_STATE] = {};
   int frame_kind = 0;
   Frame9 frame_uniform{};
   double* frame_streams = nullptr;          // the field as nine SoA streams of ld doubles each (the kernel reads 8 B per lane)
@@ -736,7 +861,7 @@ static int tangent_size(const dxm_material* m) {
   if (m->tangent_layout == DXM_TANGENT_SYM) return d.n_flux * (d.n_flux + 1) / 2;
   if (m->tangent_layout == DXM_TANGENT_COEF) return 9;
   if (m->tangent_layout == DXM_TANGENT_PACK4) return 4;
-  return d.n_flux * d.n_grad;
+  return ct_full_of(d);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -796,6 +921,25 @@ int dxm_device_count(void) {
   return n;
 }
 
+int dxm_law_blocks_get(int law, dxm_law_blocks* out) {
+  if (!law_known(law) || !out) return fail(-1, "unknown law id %d", law);
+  const LawDesc& d = kLaws[law];
+  memset(out, 0, sizeof(*out));
+  out->n_external = d.n_ext;
+  for (int k = 0; k < d.n_ext; ++k) {
+    out->external_name[k] = d.ext_name[k];
+    out->external_default[k] = d.ext_default[k];
+  }
+  out->n_blocks = d.n_blocks ? d.n_blocks : 1;
+  if (d.n_blocks) {
+    for (int b = 0; b < d.n_blocks; ++b) out->block[b] = d.blocks[b];
+  } else {
+    out->block[0] = tangent_block(DXM_BLOCK_ROW_FLUX, 0, DXM_BLOCK_COL_GRADIENT, 0, d.n_flux, d.n_grad);
+  }
+  out->tangent_width = ct_full_of(d);
+  return 0;
+}
+
 int dxm_law_info_get(int law, dxm_law_info* out) {
   if (!law_known(law) || !out) return fail(-1, "unknown law id %d", law);
   const LawDesc& d = kLaws[law];
@@ -850,6 +994,7 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
   m->law = law;
   m->device = device;
   m->n = npoints;
+  for (int k = 0; k < kLaws[law].n_ext; ++k) m->ext_uniform[k] = kLaws[law].ext_default[k];
   // SoA leading dimension: N rounded up to 256 plus 32 doubles.  With a slot stride that is a
   // multiple of 2 KiB the s0 read streams and s1 write streams of all slots stay congruent and the
   // kernel falls into a slow mode (0.91 vs 0.83 ms at 1e7 points, bimodal by allocation address);
@@ -915,6 +1060,7 @@ dxm_material* dxm_create(int law, const double* params, int n_params, int64_t np
 
 int dxm_destroy(dxm_material* m) {
   if (!m) return 0;
+  RelaxedCaptureMode relaxed;
   DeviceGuard guard(m->device);
   (void)sync_last(m);
   delete m->pool;
@@ -939,6 +1085,7 @@ int dxm_destroy(dxm_material* m) {
   for (double* q : m->pf_law) if (q) (void)hipFree(q);
   for (double* q : m->pf_stream) if (q) (void)hipFree(q);
   if (m->frame_streams) (void)hipFree(m->frame_streams);
+  for (double* q : m->ext_field) if (q) (void)hipFree(q);
   for (hipEvent_t e : m->ring_done) if (e) (void)hipEventDestroy(e);
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
   if (m->pipe_stream) (void)hipStreamDestroy(m->pipe_stream);
@@ -1387,6 +1534,39 @@ static void launch_single_crystal(const LaunchArgs& a) {
                         m->frame_streams ? m->frame_streams + a.off : nullptr, m->ld, m->state[0] + a.off, m->state[1] + a.off, m->ld,
                         a.flux, a.ct, m->d_stats + a.stats_off);
 }
+
+// the external state variable of the range: the field advances with it like the state slots
+static void launch_heat_stationary(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  HeatParams hp{};
+  hp.p[HT_A] = m->raw_params[0];
+  hp.p[HT_B] = m->raw_params[1];
+  heat_transfer_launch(HT_STATIONARY, a.grid, a.st, hp, a.cnt, a.grad, m->ext_uniform[0], m->ext_kind[0] ? m->ext_field[0] + a.off : nullptr,
+                       nullptr, a.flux, a.ct, m->d_stats + a.stats_off);
+}
+
+static void launch_heat_phase_change(const LaunchArgs& a) {
+#pragma clang fp contract(off)
+  dxm_material* m = a.m;
+  const double* p = m->raw_params.data();   // [Tm, ks, cs, kl, cl, dhsl, Tsmooth] (build_heat_phase_change)
+  const double Tm = p[0], ks = p[1], cs = p[2], kl = p[3], cl = p[4], dhsl = p[5], Tsm = p[6];
+  HeatParams hp{};
+  const double half = Tsm / 2;
+  hp.p[HT_TS] = Tm - half;
+  hp.p[HT_TL] = Tm + half;
+  hp.p[HT_KS] = ks; hp.p[HT_KL] = kl; hp.p[HT_CS] = cs; hp.p[HT_CL] = cl;
+  hp.p[HT_DK] = kl - ks;
+  hp.p[HT_TSM] = Tsm;
+  const double c_mean = (cs + cl) / 2, c_latent = dhsl / Tsm;
+  hp.p[HT_CTR] = c_mean + c_latent;
+  hp.p[HT_NSLOPE] = -(kl - ks) / Tsm;
+  hp.p[HT_DHSL] = dhsl;
+  hp.p[HT_CSTS] = cs * hp.p[HT_TS];
+  const double cc = (cs + cl) * Tsm;
+  hp.p[HT_HL3] = cc / 2;
+  heat_transfer_launch(HT_PHASE_CHANGE, a.grid, a.st, hp, a.cnt, a.grad, m->ext_uniform[0], m->ext_kind[0] ? m->ext_field[0] + a.off : nullptr,
+                       m->state[1] + a.off, a.flux, a.ct, m->d_stats + a.stats_off);
+}
 #endif
 
 // tl: tangent layout of THIS launch (LaunchArgs)
@@ -1531,7 +1711,7 @@ static int ensure_host_path_buffers(dxm_material* m, bool need_grad = true) {
   const int total = isv_total(d);
   if (need_grad && !m->d_grad) HIP_TRY(hipMalloc(&m->d_grad, sizeof(double) * n * d.n_grad));
   if (!m->d_flux) HIP_TRY(hipMalloc(&m->d_flux, sizeof(double) * n * d.n_flux));
-  if (!m->d_ct) HIP_TRY(hipMalloc(&m->d_ct, sizeof(double) * n * d.n_flux * d.n_grad));  // sized for the full layout
+  if (!m->d_ct) HIP_TRY(hipMalloc(&m->d_ct, sizeof(double) * n * ct_full_of(d)));  // sized for the full layout
   if (total > 0 && !m->d_isv) HIP_TRY(hipMalloc(&m->d_isv, sizeof(double) * n * total));
   return 0;
 }
@@ -1551,6 +1731,7 @@ static dxm_host::TransferRequest transfer_request(const dxm_material* m, const d
     if (m->isv_out[f]) r.bound_fields |= 1u << f;
   }
   r.layout = m->tangent_layout; r.tangent_size = tangent_size(m); r.n = n;
+  r.plain_blocks = d.n_blocks > 1;
   r.flux = flux_aos != nullptr; r.isv_aos = isv_aos != nullptr; r.ct = ct_aos != nullptr;
   r.rows = rows; r.staged_grad = staged_grad; r.fused = fused;
   const bool any = m->opt_pageable_dma;
@@ -1924,6 +2105,7 @@ void* dxm_host_alloc(uint64_t bytes) {
 
 int dxm_host_free(void* p) {
   if (p) {
+    RelaxedCaptureMode relaxed;
     forget_locked(p);
     HIP_TRY(hipHostFree(p));
   }
@@ -2057,6 +2239,7 @@ dxm_mesh* dxm_mesh_create_simplex(int tdim, const double* coords, int64_t n_vert
 
 int dxm_mesh_destroy(dxm_mesh* mesh) {
   if (!mesh) return 0;
+  RelaxedCaptureMode relaxed;
   DeviceGuard guard(mesh->device);
   if (mesh->d_coords) (void)hipFree(mesh->d_coords);
   if (mesh->d_conn) (void)hipFree(mesh->d_conn);
@@ -2131,6 +2314,7 @@ static bool fusable(const dxm_mesh* mesh) { return fused_kind(mesh) != 0; }
 static int integrate_displacement_host(dxm_material* m, dxm_mesh* mesh, const double* u_host, double* flux_aos, double* isv_aos,
                                        double* ct_aos, dxm_stats* stats, const int64_t* rows) {
   if (!m || !mesh || !u_host) return fail(-1, "null argument");
+  if (kLaws[m->law].no_displacement) return fail(-1, "%s", kLaws[m->law].no_displacement);
   if (mesh->device != m->device) return fail(-1, "mesh and material live on different devices");
   if (dxm_mesh_npoints(mesh) != m->n) return fail(-1, "mesh has %lld Gauss points, material %lld",
                                                    (long long)dxm_mesh_npoints(mesh), (long long)m->n);
@@ -2174,6 +2358,7 @@ int dxm_integrate_displacement_rows(dxm_material* m, dxm_mesh* mesh, const doubl
 int dxm_integrate_displacement_device(dxm_material* m, dxm_mesh* mesh, const double* u_dev, double dt,
                                       double* flux_dev, double* ct_dev, void* hip_stream) {
   if (!m || !mesh) return fail(-1, "null argument");
+  if (kLaws[m->law].no_displacement) return fail(-1, "%s", kLaws[m->law].no_displacement);
   if (int rc = take_dt(m, dt)) return rc;
   if (mesh->device != m->device) return fail(-1, "mesh and material live on different devices");
   if (dxm_mesh_npoints(mesh) != m->n) return fail(-1, "mesh has %lld Gauss points, material %lld",
@@ -2221,6 +2406,7 @@ int dxm_clean_tiles(dxm_material* m, int64_t* clean, int64_t* tiles) {
 const char* dxm_kernel_name(const dxm_material* m) {
   if (!m) return "";
   if (m->frame_kind) return kLaws[m->law].frame_kernel[m->frame_kind - 1];
+  for (int k : m->ext_kind) if (k) return kLaws[m->law].ext_kernel;
   return m->pf_mask ? kLaws[m->law].field_kernel : kLaws[m->law].kernel;
 }
 
@@ -2485,11 +2671,83 @@ int dxm_set_frame_field_device(dxm_material* m, const double* dev_aos, void* hip
 
 int dxm_frame_kind(const dxm_material* m) { return m ? m->frame_kind : -1; }
 
+// ---- external state variables --------------------------------------------------------------------------
+static int ext_check(const dxm_material* m, int index) {
+  if (!m) return fail(-1, "null handle");
+  const LawDesc& d = kLaws[m->law];
+  if (d.n_ext == 0)
+    return fail(-1, "law %d has no external state variable: its update reads the gradient, its parameters and its own state only "
+                    "(DXM_LAW_HEAT_STATIONARY and DXM_LAW_HEAT_PHASE_CHANGE read a Temperature)", m->law);
+  if (index < 0 || index >= d.n_ext) return fail(-1, "law %d has no external state variable %d", m->law, index);
+  return 0;
+}
+
+static int ext_reserve(dxm_material* m, int index) {
+  if (m->ext_field[index]) return 0;
+  const size_t bytes = sizeof(double) * (size_t)(m->n > 0 ? m->n : 1);
+  if (hipMalloc(&m->ext_field[index], bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    m->ext_field[index] = nullptr;
+    return fail(-3, "hipMalloc of a %zu-byte external-state field failed", bytes);
+  }
+  return 0;
+}
+
+static void ext_set_kind(dxm_material* m, int index, int kind) {
+  if (m->ext_kind[index] == kind) return;
+  m->ext_kind[index] = kind;
+  ++m->epoch;   // the launches read another argument from now on
+}
+
+int dxm_set_external_state(dxm_material* m, int index, const double* host_values) {
+  if (int rc = ext_check(m, index)) return rc;
+  DEVICE_GUARD(m);
+  if (int rc = sync_last(m)) return rc;
+  if (!host_values) { ext_set_kind(m, index, 0); return 0; }
+  const char* name = kLaws[m->law].ext_name[index];
+  for (int64_t i = 0; i < m->n; ++i)
+    if (!std::isfinite(host_values[i])) return fail(-1, "%s is not finite at point %lld (%g)", name, (long long)i, host_values[i]);
+  if (int rc = ext_reserve(m, index)) return rc;
+  if (int rc = upload_from_host(m->ext_field[index], host_values, sizeof(double) * (size_t)m->n, m->own_stream)) return rc;
+  ext_set_kind(m, index, 1);
+  return 0;
+}
+
+int dxm_set_external_state_uniform(dxm_material* m, int index, double value) {
+  if (int rc = ext_check(m, index)) return rc;
+  if (!std::isfinite(value)) return fail(-1, "%s must be finite, got %g", kLaws[m->law].ext_name[index], value);
+  if (m->ext_kind[index] == 0 && m->ext_uniform[index] == value) return 0;   // nothing changed: captured launches stay valid
+  m->ext_uniform[index] = value;
+  m->ext_kind[index] = 0;
+  ++m->epoch;
+  return 0;
+}
+
+int dxm_set_external_state_device(dxm_material* m, int index, const double* dev_values, void* hip_stream) {
+  if (int rc = ext_check(m, index)) return rc;
+  if (!dev_values) return dxm_set_external_state(m, index, nullptr);
+  DEVICE_GUARD(m);
+  hipStream_t st = (hipStream_t)hip_stream;
+  // the last launch may still read the field from another stream: this one waits for it, the host does not
+  if (m->launched && m->last_event_recorded) HIP_TRY(hipStreamWaitEvent(st, m->last_event, 0));
+  else if (int rc = sync_last(m)) return rc;
+  if (int rc = ext_reserve(m, index)) return rc;
+  if (m->n > 0) HIP_TRY(hipMemcpyAsync(m->ext_field[index], dev_values, sizeof(double) * (size_t)m->n, hipMemcpyDeviceToDevice, st));
+  ext_set_kind(m, index, 1);
+  return 0;
+}
+
+int dxm_external_state_kind(const dxm_material* m, int index) {
+  if (!m || index < 0 || index >= kLaws[m->law].n_ext) return -1;
+  return m->ext_kind[index];
+}
+
 int dxm_algorithmic_bytes(const dxm_material* m) {
   if (!m) return -1;
   int bytes = kLaws[m->law].alg_bytes;
   for (const double* q : m->pf_stream) if (q) bytes += 8;
   if (m->frame_kind == 2) bytes += 9 * 8;   // the nine frame streams
+  for (int k : m->ext_kind) if (k) bytes += 8;   // an external state variable held as a field
   return bytes;
 }
 
@@ -2607,6 +2865,7 @@ int dxm_host_register(void* p, uint64_t bytes) {
 
 int dxm_host_unregister(void* p) {
   if (p) {
+    RelaxedCaptureMode relaxed;
     forget_locked(p);
     HIP_TRY(hipHostUnregister(p));
   }

@@ -384,6 +384,7 @@ struct TransferRequest {
   int law;                                        // DXM_LAW_*
   int n_grad, n_flux, n_isv_fields, isv_dim[DXM_MAX_STATE_FIELDS];
   int layout, tangent_size;                       // the handle's DXM_TANGENT_* and dxm_tangent_size
+  bool plain_blocks;                              // the law's tangent is several blocks (its kLaws row): tangent_size numbers per point, moved as they are
   int64_t n;
   bool flux, isv_aos, ct;                         // the destinations the caller passed
   bool rows;                                      // the rows forms: flux / ct / bound fields are BASES, point i goes to row rows[i]
@@ -433,7 +434,9 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   // Ogden: the kernel writes the 81 entries only (no record to rebuild from): they are downloaded as they are, and the rows forms
   // move them like a handle's own packed layout
   // single-crystal viscoplasticity: the same for its 36 entries (the block is not symmetric: no packed record)
-  const bool plain_block = r.law == DXM_LAW_OGDEN || r.law == DXM_LAW_SINGLE_CRYSTAL_FCC;
+  // a law whose row declares several tangent blocks (the heat-transfer laws: 12 / 13 entries): the same, whatever its id
+  const bool blocks = r.plain_blocks;
+  const bool plain_block = r.law == DXM_LAW_OGDEN || r.law == DXM_LAW_SINGLE_CRYSTAL_FCC || blocks;
   // Hosford: a general symmetric 6x6 with no coefficient form.  A full-layout handle's packed transfer is the kernel's 21
   // upper-triangle entries (168 instead of 288 B/point), mirrored into the block by the workers; a "sym" handle downloads its 21
   // orthotropic elasticity: the same (Q^T C Q is a general symmetric 6x6 per point)
@@ -464,7 +467,7 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   p.tl = rows_plain ? r.layout : (p.packed && !constant ? (gsym ? DXM_TANGENT_SYM : (pack4 ? DXM_TANGENT_PACK4 : DXM_TANGENT_COEF)) : r.layout);
   p.np = rows_plain ? r.tangent_size : (fefp ? FEFP_RECORD : (gsym ? 21 : (pack4 ? 4 : 9)));
   p.land = fefp ? FEFP_RECORD : std::max(p.np, 9);   // (9 covers both packed forms of the J2 laws; a "sym" handle in the rows forms lands 21)
-  p.nfull = sym_packed ? 21 : r.n_flux * r.n_grad;
+  p.nfull = sym_packed ? 21 : (blocks ? r.tangent_size : r.n_flux * r.n_grad);   // (several blocks: their widths' sum, which the handle's full layout is)
   p.job = constant ? 0 : (sym_packed ? -4 : p.np);
   p.nt = p.packed && !constant ? p.np : r.tangent_size;   // the packed form of this call, else the handle's layout
   if (!r.ct) p.ct = CtRoute::none;

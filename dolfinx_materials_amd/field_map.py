@@ -197,6 +197,37 @@ class FieldMapBase:
             raise ValueError(f"Gradient '{name}' is not available from the material law.")
         self.gradients[name] = ExpressionField(name, self.material.gradients[name], evaluator, self.num_cells_total, self.nqp)
 
+    def _make_external_state_variable(self, name, value):
+        """``quadrature_map.py:184-191``: a number / an array (one value per point of all cells, or per point and component) is a
+        constant expression, a callable ``evaluator(cells) -> (len(cells) * nqp, dim)`` stands for a UFL expression."""
+        dim = self.material.external_state_variables.get(name, 1) if hasattr(self.material, "external_state_variables") else 1
+        if callable(value):
+            evaluator = value
+        else:
+            const = np.asarray(value, dtype=np.float64)
+            total = self.num_cells_total * self.nqp
+
+            def evaluator(cells, const=const):
+                if const.size == total * max(1, dim):   # a field over all cells
+                    return const.reshape(self.num_cells_total, -1)[np.asarray(cells)]
+                return np.broadcast_to(const.reshape(-1), (len(cells) * self.nqp, max(1, dim)))
+        return ExpressionField(name, dim, evaluator, self.num_cells_total, self.nqp)
+
+    def register_external_state_variable(self, name, ext_state_var):
+        """``quadrature_map.py:174-195``: register an evaluator, a number or an array as an external state variable of the material,
+        evaluate it over this map's cells and initialise the material with the values of all cells (the reference hands
+        ``function.x.array``; :class:`AcceleratedUpdate` overrides this to hand the rows of the map's own points)."""
+        state_var = self._make_external_state_variable(name, ext_state_var)
+        self.external_state_variables[name] = state_var
+        state_var.eval(self.cells)
+        self.material.initialize_external_state_variable(name, state_var.function.x.array)
+
+    def update_external_state_variables(self):
+        """``quadrature_map.py:220-225``."""
+        for name, esv in self.external_state_variables.items():
+            esv.eval(self.cells)
+            self.material.update_external_state_variable(name, esv.function.x.array)
+
     def get_gradient_vals(self, gradient, cells):
         gradient.eval(cells)
         return gradient.function.values[self.dofs, :]

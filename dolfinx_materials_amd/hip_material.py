@@ -119,6 +119,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_SINGLE_CRYSTAL_FCC:
             raise ValueError("the single-crystal tangent is not symmetric (interaction hardening): no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for this law; use 'full'")
+        if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_HEAT_STATIONARY, _lib.LAW_HEAT_PHASE_CHANGE):
+            raise ValueError("the heat-transfer tangent is several blocks (flux / gradient, flux / temperature, enthalpy / temperature), not "
+                             f"a symmetric 6x6: no packed tangent record (tangent_layout={tangent_layout!r}) exists for these laws; use 'full'")
         if not isinstance(jit, (bool, type(None))):
             raise TypeError("the second argument of JAXMaterial / HIPMaterial is `jit` (jaxmat.py:144); pass the GPU index as device=")
         self.jit = bool(jit)
@@ -139,6 +142,10 @@ class HIPMaterial:
         # a user-supplied hardening law lives in its own JIT-compiled copy of the library
         self._lib = _lib.load_custom(custom.expr_R, custom.expr_dR) if custom is not None else _lib.load()
         self._info = _lib.law_info(behavior.law, self._lib)
+        self._law_blocks = _lib.law_blocks(behavior.law, self._lib)
+        # external state variables: name -> a number or one value per point, as last set (handed to new handles by set_data_manager)
+        self._ext = {self._law_blocks.external_name[k].decode(): float(self._law_blocks.external_default[k])
+                     for k in range(self._law_blocks.n_external)}
         self._gname = gradient_name or behavior.gradient_name
         self._fname = flux_name or behavior.flux_name
         self.material_properties = dict(behavior.flat_properties())  # jaxmat.py:146
@@ -270,11 +277,23 @@ class HIPMaterial:
 
     @property
     def tangent_blocks(self):
-        # generic.py:141-146
-        return {
-            (kf, kg): (vf, vg)
-            for (kf, vf), (kg, vg) in zip(self.fluxes.items(), self.gradients.items())
-        }
+        """``generic.py:141-146`` / ``mfront.py``: (row name, column name) -> (rows, cols), in the order the tangent array holds the
+        blocks (``dxm_law_blocks_get``).  A row is the flux or an internal state variable, a column the gradient or an external
+        state variable; the laws without an external state variable have the single (flux, gradient) block."""
+        b = self._law_blocks
+        isv, ext = list(self.internal_state_variables), list(self.external_state_variables)
+        out = {}
+        for k in range(b.n_blocks):
+            blk = b.block[k]
+            row = self._fname if blk.row_kind == 0 else isv[blk.row_index]
+            col = self._gname if blk.col_kind == 0 else ext[blk.col_index]
+            out[(row, col)] = (int(blk.rows), int(blk.cols))
+        return out
+
+    @property
+    def external_state_variables(self):
+        """name -> size (``mfront.py:100-107``); empty for the laws that read none."""
+        return {self._law_blocks.external_name[k].decode(): 1 for k in range(self._law_blocks.n_external)}
 
     @property
     def internal_state_variables(self):
@@ -315,12 +334,12 @@ class HIPMaterial:
     def tangent_size(self):
         """Doubles per point of the tangent array ``integrate`` returns (``dxm_tangent_size``): 36 / 81 for the
         full block, 21 / 9 for the ``"sym"`` / ``"coef"`` layouts."""
-        nf, ng = int(self._info.n_flux), int(self._info.n_grad)
-        return {"full": nf * ng, "sym": nf * (nf + 1) // 2, "coef": 9, "pack4": 4}[self.tangent_layout]
+        nf = int(self._info.n_flux)
+        return {"full": int(self._law_blocks.tangent_width), "sym": nf * (nf + 1) // 2, "coef": 9, "pack4": 4}[self.tangent_layout]
 
     @property
     def algorithmic_bytes_per_point(self):
-        if (self._fields or self._frame is not None) and self._parts:   # + 8 per bound kernel-parameter stream, + 72 for a frame field
+        if (self._fields or self._frame is not None or self._ext) and self._parts:   # + 8 per bound kernel-parameter stream, + 72 for a frame field, + 8 per external-state field
             return int(self._lib.dxm_algorithmic_bytes(self._parts[0][0]))
         return int(self._info.algorithmic_bytes_per_point)
 
@@ -457,6 +476,10 @@ class HIPMaterial:
             except Exception:
                 self.close()
                 raise
+        # mfront.py:106-110: a new data manager starts from the default of every external state variable (Temperature: 293.15),
+        # which is what dxm_create leaves the handles with
+        self._ext = {self._law_blocks.external_name[k].decode(): float(self._law_blocks.external_default[k])
+                     for k in range(self._law_blocks.n_external)}
         if G > 1:
             from concurrent.futures import ThreadPoolExecutor
 
@@ -467,7 +490,7 @@ class HIPMaterial:
         self._flux = [np.zeros((self._n, nf)), np.zeros((self._n, nf))]
         # output arrays owned by the material: page-locked so that D2H runs at full PCIe rate, allocated when the first
         # host-buffer call needs them (a bound array or a device-pointer caller never does)
-        self._ct_shape = {"full": (self._n, nf, ng), "sym": (self._n, nf * (nf + 1) // 2), "coef": (self._n, 9), "pack4": (self._n, 4)}[self.tangent_layout]
+        self._ct_shape = {"full": (self._n, nf, ng) if self._law_blocks.n_blocks == 1 else (self._n, int(self._law_blocks.tangent_width)), "sym": (self._n, nf * (nf + 1) // 2), "coef": (self._n, 9), "pack4": (self._n, 4)}[self.tangent_layout]
         self._pinned = {}
         self._out_isv = self._out_ct = None
         self._flux_buf = []
@@ -517,12 +540,63 @@ class HIPMaterial:
 
     # ---- protocol: external state variables (quadrature_map.py:195, :225) --------------------------
     def initialize_external_state_variable(self, name, values):
-        raise NotImplementedError(
-            f"external state variable {name!r}: the HIP laws (elastic, J2, FeFp J2) take none "
-            "(neither do the jaxmat behaviours they replace: JAXMaterial has no such method either)")
+        """``mfront.py:109-125``: a scalar, or one value per point of this material, for an external state variable of the law
+        (``external_state_variables``; the heat-transfer laws read ``Temperature``).
+
+        Deviation from MGIS: MGIS keeps a pair, ``s0.external_state_variables`` (beginning of the step) and ``s1`` (end), and
+        ``initialize`` writes both while ``update`` writes ``s1`` only.  The handle holds ONE field, the value at the end of the
+        step -- the served laws read nothing else -- so both methods set that field.
+
+        An array whose values are all equal is handed over as the NUMBER (a kernel argument, no 8 B/point stream) -- what a
+        ``fem.Constant`` registered with the map arrives as (``quadrature_map.py:184-195``).  The switch between number and field
+        moves ``launch_generation``, as does a changed number, while a field rewritten with other values does not: a caller that
+        replays a captured graph while the temperature passes through a constant state (an initial condition, say) checks
+        ``launch_generation`` as for every other setter, or sets the field on the handle itself (``dxm_set_external_state``), which
+        keeps whatever it is given as a field."""
+        if name not in self._ext:
+            raise NotImplementedError(
+                f"external state variable {name!r}: the HIP laws (elastic, J2, FeFp J2) take none "
+                "(neither do the jaxmat behaviours they replace: JAXMaterial has no such method either)")
+        a = np.asarray(values, dtype=np.float64).reshape(-1)
+        if a.size == 0:
+            raise ValueError(f"empty value for external state variable {name!r}")
+        if a.size == 1 or bool(np.all(a == a[0])):
+            value = float(a[0])    # a uniform field is a number: a kernel argument, no stream
+        else:
+            if self._parts and a.size != self._n:
+                raise ValueError(f"external state variable {name!r}: {a.size} values for {self._n} Gauss points")
+            value = a.copy()
+        self._push_external_state(name, value)
+        self._ext[name] = value
 
     def update_external_state_variable(self, name, values):
         self.initialize_external_state_variable(name, values)
+
+    def _push_external_state(self, name, value):
+        """Hand every block's handle its slice of the field (or the number).  A refusal leaves the handles that had accepted
+        with the previous value."""
+        if not self._parts:
+            return
+        idx = list(self._ext).index(name)
+        if isinstance(value, np.ndarray) and value.size != self._n:
+            raise ValueError(f"external state variable {name!r} holds {value.size} values, the data manager has {self._n} Gauss points: "
+                             "set it again (an array of the new size, or a number)")
+
+        def one(h, lo, hi, v):
+            if isinstance(v, np.ndarray):
+                part = np.ascontiguousarray(v[lo:hi])
+                return self._lib.dxm_set_external_state(h, idx, part.ctypes.data)
+            return self._lib.dxm_set_external_state_uniform(h, idx, float(v))
+
+        done = []
+        try:
+            for h, lo, hi, _ in self._parts:
+                self._chk(one(h, lo, hi, value))
+                done.append((h, lo, hi))
+        except DxmError:
+            for h, lo, hi in done:
+                one(h, lo, hi, self._ext[name])
+            raise
 
     def __del__(self):
         try:
@@ -834,7 +908,9 @@ class HIPMaterial:
         (``get_initial_state_dict()``, :meth:`natural_state`): the internal state variables the update starts from; for the FeFp
         laws also the previous ``F`` (the kernel's state is rebuilt from ``(F_n, be_bar_n)``); other keys (the previous strain and
         stress of the small-strain laws) are not read by these laws, absent keys take the natural state.  Returns the consistent
-        tangent ``(N, nf, ng)`` -- ``d flux / d gradient`` of the algorithm, what ``jacfwd`` differentiates -- and the new state
+        tangent ``(N, nf, ng)`` -- ``d flux / d gradient`` of the algorithm, what ``jacfwd`` differentiates; for a law with several
+        tangent blocks ``(N, tangent_size)``, the blocks one after the other, evaluated at the material's external state variables
+        as they stand -- and the new state
         (gradient, flux and every internal state variable, ``(N, dim)`` each, owned by the caller).  The material's own
         ``s0`` / ``s1`` are not touched: the update runs on a scratch material of the same behaviour (one ``dxm_integrate``)."""
         ng, nf = int(self._info.n_grad), int(self._info.n_flux)
@@ -848,6 +924,11 @@ class HIPMaterial:
         for key, value in state.items():
             start[key] = _as_c(value, start[key].shape)
         sc = self._scratch(n)
+        for name, value in self._ext.items():   # the external state variables of this material, as they stand now
+            if isinstance(value, np.ndarray) and value.size != n:
+                raise DxmError(f"explicit-state update of {n} points: external state variable {name!r} is a field over the {self._n} Gauss "
+                               "points of this material, so the call must pass one gradient row per Gauss point")
+            sc.update_external_state_variable(name, value)
         wanted = list(self.internal_state_variables) + ([self._gname] if ng == 9 else [])
         sc.set_initial_state_dict({k: start[k] for k in wanted})
         flux, isv, ct = sc.integrate(g, self._dt(dt))
@@ -858,7 +939,7 @@ class HIPMaterial:
             w = max(1, dim)
             new_state[name] = np.array(isv[:, col:col + w])
             col += w
-        return np.array(ct).reshape(n, nf, ng), new_state
+        return (np.array(ct).reshape(n, nf, ng) if self._law_blocks.n_blocks == 1 else np.array(ct).reshape(n, -1)), new_state
 
     def constitutive_update(self, gradients, state, dt=None):
         """``sig, new_state = material.constitutive_update(eps, state, dt)`` at ONE material point (``jaxmat.py:158-164``,

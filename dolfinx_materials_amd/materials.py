@@ -494,5 +494,97 @@ class MericCailletaudSingleCrystalViscoPlasticity(OrthotropicElasticity):
                 **{f"interaction.{i}": v for i, v in enumerate(self.interaction)}}
 
 
+class HeatTransferBehavior(Behavior):
+    """Base of the heat-transfer laws: gradient ``TemperatureGradient`` (3), flux ``HeatFlux`` (3) and one external state variable,
+    ``Temperature``, the value at the end of the step (``HIPMaterial.update_external_state_variable``).  The gradient is 3 wide
+    whatever the dimension of the problem: a 2-D caller pads ``grad(T)`` with a zero."""
+
+    gradient_name = "TemperatureGradient"
+    flux_name = "HeatFlux"
+    ngrad = 3
+    nflux = 3
+    external_state_variables = {"Temperature": 1}
+    NAMES = ()
+
+    def validate(self):
+        for k in self.NAMES:
+            if not _isfinite(getattr(self, k)):
+                raise ValueError(f"{type(self).__name__}: {k} must be finite, got {getattr(self, k)}")
+
+    def __setattr__(self, name, value):
+        object.__setattr__(self, name, float(value) if name in self.NAMES else value)
+
+    def get_parameter(self, name):
+        """``mgis.behaviour.getParameterDefaultValue`` as the demos use it (``material.get_parameter("A")``): the current value."""
+        if name not in self.NAMES:
+            raise ValueError(f"{type(self).__name__} has no parameter {name!r} (it has {list(self.NAMES)})")
+        return getattr(self, name)
+
+    def params(self):
+        return [getattr(self, k) for k in self.NAMES]
+
+    def flat_properties(self):
+        return {k: getattr(self, k) for k in self.NAMES}
+
+
+class StationaryHeatTransfer(HeatTransferBehavior):
+    """``demos/mfront/heat_transfer/StationaryHeatTransfer.mfront``: ``k = 1 / (A + B T)``, ``j = -k grad(T)``; tangent blocks
+    ``(HeatFlux, TemperatureGradient) = -k I`` and ``(HeatFlux, Temperature) = B k^2 grad(T)``.  ``A + B T <= 0`` is not refused
+    (MFront does not refuse it either)."""
+
+    law = _lib.LAW_HEAT_STATIONARY
+    NAMES = ("A", "B")
+    MFRONT_DEFAULTS = {"A": 0.0375, "B": 2.165e-4}
+
+    def __init__(self, A: float = MFRONT_DEFAULTS["A"], B: float = MFRONT_DEFAULTS["B"]):
+        self.A, self.B = A, B
+        self.validate()
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict | None = None):
+        props = dict(props or {})
+        extra = set(props) - set(cls.NAMES)
+        if extra:
+            raise ValueError(f"stationary heat transfer parameters: unknown {sorted(extra)}")
+        return cls(**{**cls.MFRONT_DEFAULTS, **props})
+
+
+class HeatTransferPhaseChange(HeatTransferBehavior):
+    """``demos/mfront/heat_transfer/HeatTransferPhaseChange.mfront`` (its lines 41-56, not the demo's prose: the transition's heat
+    capacity is ``(cs + cl) / 2 + dhsl / Tsmooth``): conductivity and enthalpy of a solid / liquid with a transition of width
+    ``Tsmooth`` around the melting temperature.  One internal state variable, ``Enthalpy`` (1), and three tangent blocks:
+    ``(HeatFlux, TemperatureGradient)``, ``(HeatFlux, Temperature)``, ``(Enthalpy, Temperature)``.  The parameters carry the file's
+    entry names."""
+
+    law = _lib.LAW_HEAT_PHASE_CHANGE
+    NAMES = ("MeltingTemperature", "SolidConductivity", "SolidHeatCapacity", "LiquidConductivity", "LiquidHeatCapacity", "FusionEnthalpy",
+             "Tsmooth")
+    MFRONT_DEFAULTS = {"MeltingTemperature": 933.15, "SolidConductivity": 210.0, "SolidHeatCapacity": 3.0e6, "LiquidConductivity": 95.0,
+                       "LiquidHeatCapacity": 2.58e6, "FusionEnthalpy": 1.08048e9, "Tsmooth": 0.1}
+
+    def __init__(self, MeltingTemperature=MFRONT_DEFAULTS["MeltingTemperature"], SolidConductivity=MFRONT_DEFAULTS["SolidConductivity"],
+                 SolidHeatCapacity=MFRONT_DEFAULTS["SolidHeatCapacity"], LiquidConductivity=MFRONT_DEFAULTS["LiquidConductivity"],
+                 LiquidHeatCapacity=MFRONT_DEFAULTS["LiquidHeatCapacity"], FusionEnthalpy=MFRONT_DEFAULTS["FusionEnthalpy"],
+                 Tsmooth=MFRONT_DEFAULTS["Tsmooth"]):
+        for k, v in zip(self.NAMES, (MeltingTemperature, SolidConductivity, SolidHeatCapacity, LiquidConductivity, LiquidHeatCapacity,
+                                     FusionEnthalpy, Tsmooth)):
+            setattr(self, k, v)
+        self.validate()
+
+    def validate(self):
+        super().validate()
+        if not self.Tsmooth > 0.0:
+            raise ValueError(f"HeatTransferPhaseChange: Tsmooth must be > 0, got {self.Tsmooth}")
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict | None = None):
+        """Parameters keyed by the file's entry names; those not given keep the file's defaults."""
+        props = dict(props or {})
+        extra = set(props) - set(cls.NAMES)
+        if extra:
+            raise ValueError(f"heat transfer with phase change parameters: unknown {sorted(extra)}")
+        return cls(**{**cls.MFRONT_DEFAULTS, **props})
+
+
 def _isfinite(x):
     return x == x and abs(x) != float("inf")

@@ -239,7 +239,8 @@ class AcceleratedUpdate:
             ns = getattr(init, "__globals__", None)
             if ns is not None and "create_quadrature_functionspace" in ns and "to_mat" in ns and "fem" in ns:
                 return ns
-        raise TypeError("a packed tangent layout needs the reference's QuadratureMap (or field_map.FieldMapBase) under AcceleratedUpdate")
+        raise TypeError("this needs the reference's QuadratureMap (or field_map.FieldMapBase) under AcceleratedUpdate: its module's names "
+                        "(fem, create_quadrature_functionspace, to_mat) build the quadrature Functions")
 
     # ---- set-up, once ------------------------------------------------------------------------------------------
     def _accel_plan(self):
@@ -414,6 +415,39 @@ class AcceleratedUpdate:
             w = max(1, int(dim))
             self._put(funs[name], dim, block[:, col:col + w])
             col += w
+
+    # ---- external state variables ----------------------------------------------------------------------------------
+    def _accel_own_rows(self, name, esv):
+        """The values of external state variable ``name`` at this map's points, in the order the material sees them: the reference
+        hands ``function.x.array``, the values over ALL cells (``quadrature_map.py:194, :224``), which is one value per point of the
+        material only for a map over every cell."""
+        rows = rows_of(esv.function, getattr(self.material, "external_state_variables", {}).get(name, 1))
+        return rows if self._accel_plan().identity else rows[np.asarray(self.dofs)]
+
+    def register_external_state_variable(self, name, ext_state_var):
+        """``quadrature_map.py:174-195`` with the material handed the rows of this map's own points."""
+        make = getattr(self, "_make_external_state_variable", None)
+        if make is not None:
+            state_var = make(name, ext_state_var)
+        else:   # the reference's own construction (quadrature_map.py:184-191), from the names of its module
+            ns = self._accel_reference_namespace()
+            if "QuadratureExpression" not in ns:
+                raise TypeError("register_external_state_variable needs the reference's QuadratureMap (its QuadratureExpression) or "
+                                "field_map.FieldMapBase under AcceleratedUpdate")
+            fem = ns["fem"]
+            if isinstance(ext_state_var, (int, float, np.ndarray, np.generic)):
+                ext_state_var = fem.Constant(self.mesh, ext_state_var)
+            points = getattr(self, "quadrature_points")   # quadrature_map.py:239-243: the reference's own property, read by this branch alone
+            state_var = ns["QuadratureExpression"](name, fem.Expression(ext_state_var, points), self.mesh, self.degree)
+        self.external_state_variables[name] = state_var
+        state_var.eval(self.cells)
+        self.material.initialize_external_state_variable(name, self._accel_own_rows(name, state_var))
+
+    def update_external_state_variables(self):
+        """``quadrature_map.py:220-225`` with the material handed the rows of this map's own points."""
+        for name, esv in self.external_state_variables.items():
+            esv.eval(self.cells)
+            self.material.update_external_state_variable(name, self._accel_own_rows(name, esv))
 
     # ---- gradients -----------------------------------------------------------------------------------------------
     def _evaluate_into(self, grad, out_rows):

@@ -137,7 +137,32 @@ enum {
    * params = [E1, E2, E3, nu12, nu23, nu13, G12, G23, G13, n, K, tau0, Q, b, d, C, h_self, h_coplanar, h_Hirth, h_collinear,
    * h_glissile, h_Lomer]: all finite, the first nine as for DXM_LAW_ORTHOTROPIC_ELASTIC, n >= 1, K > 0, tau0, b, d, C >= 0 */
   DXM_LAW_SINGLE_CRYSTAL_FCC = 14,   /* id 13 is not assigned */
-  DXM_LAW_COUNT = 15
+  /* stationary nonlinear heat transfer (the reference's demos/mfront/heat_transfer/StationaryHeatTransfer.mfront, restated from its
+   * equations).  Gradient TemperatureGradient g (3), flux HeatFlux j (3), one EXTERNAL state variable Temperature T (the value at
+   * the end of the step, MFront's T + dT; dxm_set_external_state*): k = 1 / (A + B T), j = -k g.  The tangent has TWO blocks
+   * (dxm_law_blocks_get), 12 doubles per point in this order: (HeatFlux, TemperatureGradient) 3x3 = -k I row-major with its six
+   * zeros written, then (HeatFlux, Temperature) 3x1 = B k^2 g.  No internal state.  A + B T <= 0 is not refused (MFront does not
+   * refuse it either): A + B T = 0 gives non-finite results, counted in n_nan.  The gradient is 3 wide whatever the dimension of
+   * the problem: a 2-D caller pads grad(T) with a zero; 2-component hypotheses are not served.
+   * DXM_TANGENT_FULL only; no material frame, no per-point parameter fields, none of the displacement forms
+   * (dxm_integrate_displacement*), not served by a custom-hardening build.
+   * dxm_stats: n_nan counts points with a non-finite flux or tangent entry; n_plastic, n_not_converged, max_local_iters are 0.
+   * dxm_law_info.algorithmic_bytes_per_point counts 120 (gradient 24 + tangent 96; the flux, 24 more, is written too), 136 for the
+   * phase-change law (+ 8 of tangent + 8 of Enthalpy); dxm_algorithmic_bytes adds 8 with a temperature per point.
+   * params = [A, B], finite */
+  DXM_LAW_HEAT_STATIONARY = 16,   /* id 15 is not assigned */
+  /* heat transfer with a smoothed solid/liquid phase change (demos/mfront/heat_transfer/HeatTransferPhaseChange.mfront, its lines
+   * 41-56).  Gradient, flux and external state variable as for DXM_LAW_HEAT_STATIONARY.  With Ts = Tm - Tsmooth/2 and
+   * Tl = Tm + Tsmooth/2, each formed on the host by one rounded operation and compared against as doubles:
+   *   T < Ts:  k = ks, c = cs, h = cs T, k' = 0
+   *   T > Tl:  k = kl, c = cl, h = cl (T - Tl) + dhsl + cs Ts + (cs + cl) Tsmooth / 2, k' = 0
+   *   else:    k = ks + (kl - ks)(T - Ts)/Tsmooth, c = (cs + cl)/2 + dhsl/Tsmooth, h = cs Ts + c (T - Ts), k' = -(kl - ks)/Tsmooth
+   * j = -k g.  One internal state variable, Enthalpy h (1): every update writes it and none reads it.  THREE blocks, 13 doubles
+   * per point: (HeatFlux, TemperatureGradient) = -k I (9), (HeatFlux, Temperature) = k' g (3), (Enthalpy, Temperature) = c (1).
+   * Restrictions and dxm_stats as for DXM_LAW_HEAT_STATIONARY (n_nan also counts a non-finite Enthalpy).
+   * params = [Tm, ks, cs, kl, cl, dhsl, Tsmooth], finite, Tsmooth > 0 */
+  DXM_LAW_HEAT_PHASE_CHANGE = 17,
+  DXM_LAW_COUNT = 18
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */
@@ -181,11 +206,39 @@ const char* dxm_last_error(void);
 int dxm_device_count(void);
 int dxm_law_info_get(int law, dxm_law_info* out);
 
+/* External state variables and tangent blocks of a law (generic.py:141-146 `tangent_blocks`, quadrature_map.py:84-105).  The
+ * tangent array of DXM_TANGENT_FULL holds the blocks one after the other, each rows x cols row-major, tangent_width doubles per
+ * point.  A block's row is a flux (row_index 0) or internal state field row_index of dxm_law_info; its column the gradient
+ * (col_index 0) or external state variable col_index.  External state variables are scalars.  The laws without one report the
+ * single block n_flux x n_grad and n_external = 0. */
+#define DXM_MAX_EXTERNAL_STATE 2
+#define DXM_MAX_TANGENT_BLOCKS 4
+enum { DXM_BLOCK_ROW_FLUX = 0, DXM_BLOCK_ROW_STATE = 1 };
+enum { DXM_BLOCK_COL_GRADIENT = 0, DXM_BLOCK_COL_EXTERNAL = 1 };
+typedef struct dxm_tangent_block {
+  int32_t row_kind, row_index;   /* DXM_BLOCK_ROW_* */
+  int32_t col_kind, col_index;   /* DXM_BLOCK_COL_* */
+  int32_t rows, cols;
+} dxm_tangent_block;
+typedef struct dxm_law_blocks {
+  int32_t n_external;                                  /* number of external state variables */
+  int32_t n_blocks;
+  int32_t tangent_width;                               /* sum of rows * cols = dxm_tangent_size of a DXM_TANGENT_FULL handle */
+  int32_t reserved;
+  const char* external_name[DXM_MAX_EXTERNAL_STATE];   /* e.g. "Temperature" */
+  double external_default[DXM_MAX_EXTERNAL_STATE];     /* the uniform value after dxm_create */
+  dxm_tangent_block block[DXM_MAX_TANGENT_BLOCKS];
+} dxm_law_blocks;
+int dxm_law_blocks_get(int law, dxm_law_blocks* out);
+
 /* ---- life cycle: Material.set_data_manager(ngauss)  (generic.py:172-174, jaxmat.py:195-197,
  *      quadrature_map.py:231-233) ---------------------------------------------------------- */
 /* Allocates device-resident SoA state s0/s1 for npoints Gauss points on `device` and
  * initialises it (p = 0, epsp = 0, be_bar = identity; cf. behavior.init_state, jaxmat.py:35). */
 dxm_material* dxm_create(int law, const double* params, int n_params, int64_t npoints, int device);
+/* dxm_destroy, dxm_mesh_destroy, dxm_host_free and dxm_host_unregister may be called while another stream of the application is
+ * being captured on the calling thread (a garbage collector's finalizer inside a graph capture): they run in the thread's relaxed
+ * capture mode and leave that capture valid. */
 int dxm_destroy(dxm_material* m);
 int64_t dxm_npoints(const dxm_material* m);
 int dxm_law(const dxm_material* m);
@@ -223,11 +276,29 @@ int dxm_set_frame(dxm_material* m, const double* r9);
 int dxm_set_frame_field(dxm_material* m, const double* host_aos);
 int dxm_set_frame_field_device(dxm_material* m, const double* dev_aos, void* hip_stream);
 int dxm_frame_kind(const dxm_material* m);
+/* External state variables (dxm_law_blocks_get: DXM_LAW_HEAT_STATIONARY and DXM_LAW_HEAT_PHASE_CHANGE have one, Temperature,
+ * index 0).  The handle holds ONE value per variable and point, the value at the end of the step (MGIS keeps a pair s0 / s1; the
+ * served laws read nothing else).  After dxm_create every variable is uniform at its default (Temperature: 293.15, mfront.py:109-110).
+ * dxm_set_external_state: host_values holds npoints doubles, of which the handle keeps its own device copy; writing the values
+ * again reuses that allocation at the same address; NULL returns to the uniform value.  dxm_set_external_state_uniform: one value
+ * for every point, a kernel argument.  Both refuse a non-finite value (< 0, the message names it and the first offending point)
+ * and leave the handle as it was.  dxm_set_external_state_device: npoints doubles in device memory on the handle's device,
+ * asynchronous on hip_stream and ordered like dxm_set_param_field_device; the values are NOT checked; dev_values is not
+ * referenced once the call is complete on that stream; NULL returns to the uniform value (that form waits for the last launch).
+ * dxm_launch_generation moves when a uniform value or the kind changes, NOT when a field is rewritten in place: a captured launch
+ * bakes in the field's address, not its contents.  In chunked launches and in the rows forms the value of point i is entry i of
+ * the handle's field (not entry rows[i]).  Laws without an external state variable refuse all of these (< 0, message).
+ * dxm_external_state_kind: 0 uniform, 1 field (negative: null handle, no such variable). */
+int dxm_set_external_state(dxm_material* m, int index, const double* host_values);
+int dxm_set_external_state_uniform(dxm_material* m, int index, double value);
+int dxm_set_external_state_device(dxm_material* m, int index, const double* dev_values, void* hip_stream);
+int dxm_external_state_kind(const dxm_material* m, int index);
 /* Bytes per point the handle's update kernel moves as it is configured now: dxm_law_info.algorithmic_bytes_per_point plus 8
- * per bound kernel-parameter stream, plus 72 while a frame field is bound. */
+ * per bound kernel-parameter stream, plus 72 while a frame field is bound, plus 8 per external state variable held as a field. */
 int dxm_algorithmic_bytes(const dxm_material* m);
 /* Tangent layout integrate writes, doubles per point:
- *   DXM_TANGENT_FULL   n_flux*n_grad (36 / 81), row-major: what `jacobian_flatten` holds (quadrature_map.py:83-105);
+ *   DXM_TANGENT_FULL   n_flux*n_grad (36 / 81), row-major: what `jacobian_flatten` holds (quadrature_map.py:83-105); for a law
+ *                      with several blocks their widths' sum (dxm_law_blocks.tangent_width: 12 / 13 for the heat-transfer laws);
  *   DXM_TANGENT_SYM    21 upper-triangle entries (i <= j), small-strain laws (symmetric tangent);
  *                      Hosford and orthotropic elasticity: the host-buffer forms of a DXM_TANGENT_FULL handle move these 21 and
  *                      mirror them on the host;
@@ -329,7 +400,7 @@ const char* dxm_kernel_name(const dxm_material* m);
 /* Identity of the launch configuration: changes whenever a launch captured into a HIP graph before would
  * no longer do what a fresh call does -- dxm_advance (the two state buffers swap: the low bit flips and
  * flips back at the next advance), dxm_set_params / dxm_set_newton / dxm_set_tangent_layout /
- * dxm_set_param_field(_device) / dxm_set_frame / dxm_set_frame_field(_device) / dxm_set_option and anything else that moves the resident state (the upper bits increase).  Replay a captured graph only while the
+ * dxm_set_param_field(_device) / dxm_set_frame / dxm_set_frame_field(_device) / dxm_set_external_state* (a changed kind or uniform value) / dxm_set_option and anything else that moves the resident state (the upper bits increase).  Replay a captured graph only while the
  * value equals the one read at capture time.  dxm_revert does not change it. */
 uint64_t dxm_launch_generation(const dxm_material* m);
 /* Tell the handle that the caller has replayed a HIP graph containing a launch of this handle: the replay

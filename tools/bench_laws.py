@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -22,6 +22,12 @@ frame per point; the history of a point belongs to its frame) x 0 %, 50 % (every
 yielded points (16 rounds per tile), each with three timings, the
 restatement's iteration count, and its ratio to the J2-linear kernel of the same process (run `--laws j2_linear single_crystal`) next
 to the byte yardstick 1008 (1080) / 496.
+
+heat_stationary, heat_phase_change: the behaviour files' parameters (the phase-change law with the demo's Tsmooth = 1.0) on seeded
+temperature gradients.  Two lines each: a uniform temperature (the phase-change law: inside the transition) and one temperature per
+point (the phase-change law: spread over the three branches), each with three timings and, when the elastic kernel ran in the same
+process (run `--laws elastic heat_stationary heat_phase_change`), its time next to the elastic kernel's scaled by the byte ratio
+120 (128) / 384 or 136 (144) / 384.
 
 --param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
 (dxm_set_param_field; 1 = sig0, 2 = lambda and mu from an E field, 3 = both, 4 / 5 = H | sigu, b as well), in the same process and on
@@ -195,6 +201,59 @@ def bench_single_crystal(a, j2_linear_ms):
             torch.cuda.empty_cache()
 
 
+def bench_heat_transfer(a, law, elastic_ms, elastic_repeats):
+    """two lines: uniform temperature, one temperature per point (module docstring)"""
+    import torch
+
+    import dolfinx_materials_amd.materials as jm
+    from dolfinx_materials_amd.jaxmat import JAXMaterial
+    from helpers import to_device
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(2026)
+    beh = jm.StationaryHeatTransfer() if law == "heat_stationary" else jm.HeatTransferPhaseChange.from_mfront_properties({"Tsmooth": 1.0})
+    m = JAXMaterial(beh)
+    m.set_data_manager(n)
+    g = to_device(rng.normal(size=(n, 3)) * 100.0)
+    flux = torch.empty((n, 3), dtype=torch.float64, device=g.device)
+    ct = torch.empty((n, m.tangent_size), dtype=torch.float64, device=g.device)
+
+    def timed():
+        for _ in range(a.warmup):
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+        for e0, e1 in ev:
+            e0.record()
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+            e1.record()
+        torch.cuda.synchronize()
+        return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+    for tag in ("uniformT", "fieldT"):
+        if tag == "uniformT":
+            m.update_external_state_variable("Temperature", 933.4 if law == "heat_phase_change" else 700.0)
+        else:
+            m.update_external_state_variable("Temperature", rng.uniform(600.0, 1300.0, n) if law == "heat_phase_change" else rng.uniform(300.0, 1500.0, n))
+        t = [timed(), timed(), timed()]
+        ms = float(np.median(t))
+        rc, stats = m.stats()
+        ab = m.algorithmic_bytes_per_point
+        r = {"law": f"{law}+{tag}", "points": n, "kernel": m.kernel_name, "kernel_ms_repeats": [round(x, 4) for x in t], "kernel_ms": round(ms, 4),
+             "Mpoints_per_s": round(n / ms / 1e3, 1), "algorithmic_bytes_per_point": ab, "GBs": round(ab * n / ms / 1e6, 1),
+             "frac_of_8TBs": round(ab * n / ms / 1e6 / 8000, 4), "nan": stats["n_nan"], "rc": rc}
+        if elastic_ms:
+            r["ratio_to_elastic"] = round(ms / elastic_ms, 3)
+            r["byte_ratio_to_elastic"] = round(ab / 384, 4)
+            r["elastic_scaled_ms"] = round(elastic_ms * ab / 384, 4)
+            r["ratio_to_yardstick"] = round(ms / (elastic_ms * ab / 384), 3)
+            r["elastic_ms_repeats"] = elastic_repeats
+        print(json.dumps(r), flush=True)
+    del m, g, flux, ct
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -208,8 +267,9 @@ def main():
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
-    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws):
-        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic or single-crystal law")
+    if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
+                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws):
+        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal or heat-transfer law")
     import torch
 
     import dolfinx_materials_amd.materials as jm
@@ -227,6 +287,9 @@ def main():
     for law in a.laws:
         if law == "single_crystal":   # its own inputs, state and nine lines
             bench_single_crystal(a, j2_linear_ms)
+            continue
+        if law in ("heat_stationary", "heat_phase_change"):   # their own inputs and two lines each
+            bench_heat_transfer(a, law, elastic_ms, elastic_repeats)
             continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)

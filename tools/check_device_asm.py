@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
-"""Build-time checks of the device code of libdxmat's six translation units (csrc/{dxmat,ramberg_osgood,param_fields,hyperelastic,
+"""Build-time checks of the device code of libdxmat's first six translation units (csrc/{dxmat,ramberg_osgood,param_fields,hyperelastic,
 hosford,orthotropic}.hip), on the cross-compiler alone:
 
 1. the resources of every kernel, read from -Rpass-analysis=kernel-resource-usage: no scratch and no spilled VGPR anywhere, and
    the kernels with per-point parameter fields within the bounds of the uniform J2 kernels (at most 128 VGPRs, the same static LDS,
    exactly 32 instantiations);
+   With --all-units the same for the units added since (small_strain_clean, single_crystal, heat_transfer), whose kernels need not
+   keep to the bounds of the J2 kernels;
 2. (--parent REV) the device assembly of every unit is byte for byte what the sources of git revision REV give (but for the
    compilation-unit id, which hashes the source file's path); the parent's resource figures are printed beside the tree's.
 
@@ -27,6 +29,8 @@ CSRC = os.path.join(ROOT, "dolfinx_materials_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-S", "--cuda-device-only"]
 UNITS = ("dxmat", "ramberg_osgood", "param_fields", "hyperelastic", "hosford", "orthotropic")
+# the units added since (--all-units): compared with the parent's where the parent has them
+LATER_UNITS = ("small_strain_clean", "single_crystal", "heat_transfer")
 MAX_VGPRS = 128
 J2_STATIC_LDS = 30848     # small_strain.hpp: 4 waves x (64 x 6 + 64 x 9) doubles + the 4 x 4 status words
 
@@ -75,23 +79,27 @@ def sha(path):
     return hashlib.sha256(re.sub(rb"__hip_cuid_[0-9a-f]+", b"__hip_cuid_", open(path, "rb").read())).hexdigest()
 
 
-def build_units(csrc, tmp, tag):
+def build_units(csrc, tmp, tag, units=UNITS):
     """unit -> (sha256 of its device assembly, resource table), the six units compiled side by side"""
     def one(unit):
         out = os.path.join(tmp, f"{unit}_{tag}.s")
         remarks = device_asm(csrc, unit, out, remarks=True)
         return unit, (sha(out), resource_table(remarks))
     with ThreadPoolExecutor(max_workers=len(UNITS)) as pool:
-        return dict(pool.map(one, UNITS))
+        return dict(pool.map(one, units))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default=None, help="git revision whose device assembly must be reproduced")
     ap.add_argument("--write-digests", default=None, help="with --parent: write the parent's digests to this JSON file")
+    ap.add_argument("--all-units", action="store_true", help="also the units added after the first six: " + ", ".join(LATER_UNITS))
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         new = build_units(CSRC, tmp, "tree")
+        later_new, later_old = {}, {}
+        if a.all_units:
+            later_new = build_units(CSRC, tmp, "tree", LATER_UNITS)
         old = None
         if a.parent:
             src = os.path.join(tmp, "parent")
@@ -99,6 +107,9 @@ def main():
             tar = subprocess.run(["git", "archive", a.parent, "dolfinx_materials_amd/csrc", "include"], cwd=ROOT, capture_output=True, check=True)
             subprocess.run(["tar", "-x", "-C", src], input=tar.stdout, check=True)
             old = build_units(os.path.join(src, "dolfinx_materials_amd", "csrc"), tmp, "parent")
+            if a.all_units:
+                there = tuple(u for u in LATER_UNITS if os.path.exists(os.path.join(src, "dolfinx_materials_amd", "csrc", u + ".hip")))
+                later_old = build_units(os.path.join(src, "dolfinx_materials_amd", "csrc"), tmp, "parent", there)
 
     fmt = lambda r: (f"VGPRs {r['vgprs']:3d}  AGPRs {r['agprs']}  SGPRs {r['sgprs']:3d}  scratch {r['scratch']}  spilled VGPRs {r['vgpr_spill']}  "   # noqa: E731
                      f"spilled SGPRs {r['sgpr_spill']:2d}  LDS {r['lds']:5d}  waves/SIMD {r['occupancy']}")
@@ -112,6 +123,22 @@ def main():
             print(f"{name}\n    {fmt(r)}" + ("" if was is None else "   parent: same" if was == r else f"\n    parent: {fmt(was)}"))
             if r["scratch"] or r["vgpr_spill"]:
                 spills.append(name)
+    # the later units: resources, and the parent's assembly where the parent has the unit (a line format of their own: the lines of
+    # the first six are counted by tests)
+    later_same = True
+    for unit in LATER_UNITS if a.all_units else ():
+        table = later_new[unit][1]
+        print(f"== {unit}: {len(table)} kernels")
+        for name in sorted(table):
+            print(f"{name}\n    {fmt(table[name])}")
+            if table[name]["scratch"] or table[name]["vgpr_spill"]:
+                spills.append(name)
+        if unit in later_old:
+            same = later_new[unit][0] == later_old[unit][0]
+            later_same = later_same and same
+            print(f"later unit {unit}_gfx950.s  tree {later_new[unit][0]}  parent {later_old[unit][0]}  {'identical' if same else 'DIFFERENT'}")
+        elif a.parent:
+            print(f"later unit {unit}_gfx950.s  tree {later_new[unit][0]}  parent: not there")
     fields = {k: v for k, v in new["param_fields"][1].items() if "small_strain_field_kernel" in k}
     out = {"field_kernels": len(fields), "broken_bounds": broken_bounds(fields), "scratch_or_spilled_vgprs": spills}
     if old:
@@ -121,9 +148,11 @@ def main():
             out["assembly"][unit + "_gfx950.s"] = {"sha256": now, "parent_sha256": was, "identical": now == was}
             print(f"{unit}_gfx950.s  tree {now}  parent {was}  {'identical' if now == was else 'DIFFERENT'}")
         if a.write_digests:
-            json.dump({k: v["parent_sha256"] for k, v in out["assembly"].items()}, open(a.write_digests, "w"), indent=1)
+            digests = {k: v["parent_sha256"] for k, v in out["assembly"].items()}
+            digests.update({u + "_gfx950.s": v[0] for u, v in later_old.items()})
+            json.dump(digests, open(a.write_digests, "w"), indent=1)
     print(json.dumps(out))
-    ok = len(fields) == 32 and not out["broken_bounds"] and not spills and all(v["identical"] for v in out.get("assembly", {}).values())
+    ok = len(fields) == 32 and not out["broken_bounds"] and not spills and all(v["identical"] for v in out.get("assembly", {}).values()) and later_same
     return 0 if ok else 1
 
 
