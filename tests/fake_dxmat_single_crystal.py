@@ -34,6 +34,7 @@ class FakeDxmatSingleCrystal(FakeDxmat):
         n = int(npoints)
         h.state = [{k: np.zeros((n, d)) for k, d in self.FIELDS} for _ in range(2)]
         h.frame = None
+        h.maxit, h.rtol = 25, 1e-14
         self._handles[self._next] = h
         return self._next
 
@@ -41,6 +42,14 @@ class FakeDxmatSingleCrystal(FakeDxmat):
         if layout != 0:
             return self._fail(-1, "the single-crystal tangent is not symmetric (interaction hardening): only DXM_TANGENT_FULL is available")
         self._h(h).epoch += 1
+        return 0
+
+    def dxm_set_newton(self, h, maxit, rtol):
+        if maxit < 1 or not rtol > 0.0:
+            return self._fail(-1, f"invalid Newton controls maxit={maxit} rtol={rtol:g}")
+        m = self._h(h)
+        m.maxit, m.rtol = int(maxit), float(rtol)
+        m.epoch += 1
         return 0
 
     def dxm_kernel_name(self, h):
@@ -130,7 +139,7 @@ class FakeDxmatSingleCrystal(FakeDxmat):
 
     def _step(self, m, grad, dt):
         m.io_valid[1] = 0
-        r = sc.update(grad, m.state[0], np.array(m.params), dt, R=m.frame)
+        r = sc.update(grad, m.state[0], np.array(m.params), dt, R=m.frame, rtol=getattr(m, "rtol", 1e-14), maxit=getattr(m, "maxit", 25))
         m.state[1] = sc.next_state(r)
         m.s1_alias, m.launched = False, True
         bad = int((r["status"] != 0).sum())
@@ -154,6 +163,20 @@ class FakeDxmatSingleCrystal(FakeDxmat):
         if _addr(isv):
             self.dxm_isv_host(h, S1, isv)
         return self._finish(m, g, r, stats)
+
+    def dxm_integrate_device(self, h, grad, dt, flux, ct, stream):
+        """the device-pointer form, with ordinary memory standing for the device's: no transfer, no state download"""
+        m = self._h(h)
+        if rc := self._take_dt(dt):
+            return rc
+        if m.n == 0:
+            return 0
+        r = self._step(m, _rows(grad, m.n, 6), dt)
+        if _addr(flux):
+            _rows(flux, m.n, 6)[...] = r["sig"]
+        if _addr(ct):
+            _rows(ct, m.n, 36)[...] = r["Ct"]
+        return 0
 
     def dxm_integrate_rows(self, h, grad, dt, flux_base, ct_base, rows, stats):
         m = self._h(h)
