@@ -66,6 +66,23 @@ def cp_bar_inv_from_be_bar(F9, be_bar6):
     return tensor_to_mandel(0.5 * (G + np.swapaxes(G, -1, -2))), tensor_to_mandel(be)
 
 
+def hencky_strain(F9):
+    """Hencky strain ``E = 1/2 log(F^T F)`` of every row of ``F9`` (N, 9), Mandel (N, 6): what the hidden plastic strain of
+    logarithmic-strain plasticity is rebuilt from, ``Ep_n = E(F_n) - ElasticStrain_n``.
+
+    Rows that are not a deformation gradient (``det F <= 0`` or not finite, e.g. the all-zero initial value of a dolfinx quadrature
+    Function handed over by ``QuadratureMap.initialize_state``) count as ``F = I``: zero strain."""
+    F = nsym_to_tensor(np.asarray(F9, dtype=np.float64).reshape(-1, 9))
+    with np.errstate(invalid="ignore", over="ignore"):
+        bad = ~(np.isfinite(F).all(axis=(1, 2)) & (np.linalg.det(np.where(np.isfinite(F), F, 0.0)) > 0.0))
+    if bad.any():
+        F = F.copy()
+        F[bad] = np.eye(3)
+    c, V = np.linalg.eigh(np.swapaxes(F, -1, -2) @ F)
+    E = (V * (0.5 * np.log(c))[:, None, :]) @ np.swapaxes(V, -1, -2)
+    return tensor_to_mandel(0.5 * (E + np.swapaxes(E, -1, -2)))
+
+
 #: (i, j) of the 21 entries of the symmetric-packed 6x6 tangent (upper triangle, row-major)
 SYM_IDX = tuple((i, j) for i in range(6) for j in range(i, 6))
 

@@ -36,6 +36,7 @@
 #include "orthotropic.hpp"
 #include "single_crystal.hpp"
 #include "heat_transfer.hpp"
+#include "log_strain.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -337,6 +338,20 @@ static int build_heat_phase_change(const double* p, LawParams&) {
   return 0;
 }
 
+// [E, nu, s0, H0] (LogarithmicStrainPlasticity.mfront; the file writes E and nu in, the material properties are s0 and H0)
+static int build_log_strain(const double* p, LawParams& q) {
+  static const char* const names[4] = {"E", "nu", "s0", "H0"};
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "logarithmic-strain plasticity: %s must be finite, got %g", names[k], p[k]);
+  if (int rc = elastic_constants(p, q)) return rc;
+  if (!(p[2] > 0.0)) return fail(-1, "logarithmic-strain plasticity: s0 must be > 0, got %g", p[2]);
+  if (!(p[3] >= 0.0)) return fail(-1, "logarithmic-strain plasticity: the hardening slope H0 must be >= 0, got %g", p[3]);
+  q.sig0 = p[2];
+  q.h1 = p[3];
+  yield_tolerance(q);
+  return 0;
+}
+
 // ---- launchers (defined in the launch section, where the handle is complete) ----
 template <int LAW> static void launch_small_strain(const LaunchArgs& a);
 static void launch_fefp_voce(const LaunchArgs& a);
@@ -348,6 +363,7 @@ static void launch_orthotropic(const LaunchArgs& a);
 static void launch_single_crystal(const LaunchArgs& a);
 static void launch_heat_stationary(const LaunchArgs& a);
 static void launch_heat_phase_change(const LaunchArgs& a);
+static void launch_log_strain(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -658,11 +674,42 @@ constexpr LawDesc law_heat_phase_change() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13 and 15 are not assigned and stay empty rows (law_known)
+// Logarithmic-strain J2: F in (72 B), PK1 (72) + dP/dF (648) out; reads p and the hidden logarithmic plastic strain (56), writes
+// them and the elastic strain (104)
+constexpr LawDesc law_log_strain_j2() {
+  LawDesc d{};
+  d.id = DXM_LAW_LOG_STRAIN_J2;
+  d.n_grad = d.n_flux = 9;
+  d.n_params = d.n_params_custom = 4;
+  d.n_isv_fields = 2;
+  d.n_fields = 3;   // field 2 is hidden state: what the update is driven by (log_strain.hpp)
+  state_field(d, 0, "ElasticStrain", 6, LS_SLOT_EEL);
+  state_field(d, 1, "EquivalentPlasticStrain", 1, LS_SLOT_P);
+  state_field(d, 2, "PlasticStrain", 6, LS_SLOT_EP);
+  d.n_slots = LS_NSLOTS;
+  d.alg_bytes = 952;
+  d.kernel = "log_strain_kernel";
+  d.no_fields = "the logarithmic-strain plasticity kernel takes its constants per handle";
+  d.build = build_log_strain;
+  d.stock_only = "logarithmic-strain plasticity takes linear hardening only: it is served by the stock libdxmat, not by a custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(log_strain_kernel_fn);
+  d.blocks_per_cu = LS_BLOCKS_PER_CU;   // log_strain.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.set_refusal = "the logarithmic-strain plasticity kernel writes the full 81-entry dP/dF only: no packed tangent record (sym / coef / pack4) "
+                  "exists for this law";
+  d.launch_refusal = "the logarithmic-strain plasticity kernel writes the full 81-entry dP/dF only: no packed tangent record exists for this law";
+  d.no_fused = "the logarithmic-strain plasticity kernel has no fused displacement-gradient form: set option fused_gradient to 0 (F is "
+               "then evaluated by the gradient kernel) or pass F as an array";
+  d.no_frame = kNoFrame;
+  d.launch = DXM_STOCK_ONLY(launch_log_strain);   // log_strain.hip: F from the (N, 9) array, the full tangent
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15 and 18 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
-    law_heat_stationary(), law_heat_phase_change(),
+    law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(),
 };
 
 constexpr bool rows_in_place() {
@@ -671,8 +718,9 @@ constexpr bool rows_in_place() {
   return true;
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
-static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel,
-              "ids 6, 8, 9, 11, 13 and 15 are not assigned");
+static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
+                  !kLaws[18].kernel,
+              "ids 6, 8, 9, 11, 13, 15 and 18 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -1512,6 +1560,12 @@ static void launch_hosford(const LaunchArgs& a) {
   dxm_material* m = a.m;
   hosford_launch(a.tl, a.grid, a.st, m->prm, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
                  m->d_stats + a.stats_off);
+}
+
+static void launch_log_strain(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  log_strain_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
+                    m->d_stats + a.stats_off);
 }
 
 static void launch_orthotropic(const LaunchArgs& a) {

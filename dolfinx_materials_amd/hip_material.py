@@ -110,6 +110,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_OGDEN:
             raise ValueError("the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for this law")
+        if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_LOG_STRAIN_J2:
+            raise ValueError("the logarithmic-strain plasticity kernel writes the full 81-entry dP/dF only: no packed tangent record "
+                             f"(tangent_layout={tangent_layout!r}) exists for this law")
         if tangent_layout in ("coef", "pack4") and getattr(behavior, "law", None) == _lib.LAW_HOSFORD_LINEAR:
             raise ValueError("the Hosford tangent is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no "
                              f"coefficients (tangent_layout={tangent_layout!r}); use 'full' or 'sym'")
@@ -311,8 +314,8 @@ class HIPMaterial:
     @property
     def _has_hidden_plastic_strain(self):
         """Hosford: the kernel is handed the total strain, so its state is the plastic strain (hidden field 2), rebuilt from
-        (Strain_n, ElasticStrain_n) when either is set."""
-        return self.behavior.law == _lib.LAW_HOSFORD_LINEAR
+        (Strain_n, ElasticStrain_n) when either is set.  Logarithmic-strain plasticity: the same with the Hencky strain of F_n."""
+        return self.behavior.law in (_lib.LAW_HOSFORD_LINEAR, _lib.LAW_LOG_STRAIN_J2)
 
     @property
     def variables(self):
@@ -393,8 +396,8 @@ class HIPMaterial:
         if self.behavior.law not in (_lib.LAW_J2_LINEAR, _lib.LAW_J2_VOCE) or getattr(self.behavior, "custom_hardening", None) is not None:
             raise NotImplementedError(
                 f"material property {key!r} varies from point to point: per-point property fields exist for the small-strain J2 laws "
-                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp, Ogden, Hosford, orthotropic elasticity or "
-                "custom hardening laws)")
+                "with linear or Voce hardening only (not the elastic law, Ramberg-Osgood, FeFp, Ogden, Hosford, orthotropic elasticity, "
+                "logarithmic-strain plasticity or custom hardening laws)")
         return list(self.behavior.flat_properties()).index(key)
 
     def _upload_field(self, key, arr, restore=None):
@@ -707,7 +710,13 @@ class HIPMaterial:
             # eps_p,n = eps_n - eps_el,n: what the next update forms its trial elastic strain from
             eel = _as_c(state["ElasticStrain"], (self._n, 6)) if "ElasticStrain" in state else self._isv_dict(S0)["ElasticStrain"]
             self._retire_final_views(materializing=True)
-            self._set_state(2, _as_c(np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 6) - eel))
+            if self.behavior.law == _lib.LAW_LOG_STRAIN_J2:
+                from .conventions import hencky_strain
+
+                total = hencky_strain(np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 9))
+            else:
+                total = np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 6)
+            self._set_state(2, _as_c(total - eel))
 
     def _set_state(self, field, a):
         for h, lo, hi, ptrs in self._blocks(a):

@@ -351,6 +351,57 @@ class HosfordIsotropicHardening(SmallStrainBehavior):
                 "yield_stress.H": self.yield_stress.H, "a": self.a}
 
 
+class LogarithmicStrainPlasticity(FiniteStrainBehavior):
+    """Finite-strain J2 plasticity in logarithmic strains with linear isotropic hardening (the reference's
+    ``demos/mfront/finite_strain_elastoplasticity/LogarithmicStrainPlasticity.mfront``): the Hencky strain ``E = 1/2 log(F^T F)``
+    goes through the small-strain radial return (Hooke, Mises, ``R(p) = s0 + H0 p``) and the stress ``T`` is mapped back to the first
+    Piola-Kirchhoff stress by the derivatives of the tensor logarithm.  ``s0 > 0``, ``H0 >= 0``; ``E`` and ``nu`` default to the
+    values the behaviour file writes in (210e9, 0.3).  Internal state variables ``ElasticStrain`` (6) and
+    ``EquivalentPlasticStrain`` (1), MFront's names.
+
+    ``JAXMaterial(LogarithmicStrainPlasticity.from_mfront_properties({"YieldStrength": 250e6, "HardeningSlope": 1e6}))`` stands
+    where the demo uses ``MFrontMaterial(lib, "LogarithmicStrainPlasticity", material_properties=...)``: gradient
+    ``DeformationGradient`` (9), flux ``FirstPiolaKirchhoffStress`` (9), tangent block ``(9, 9)``.  Full tangent only; uniform
+    properties only; the displacement forms need option ``fused_gradient`` off."""
+
+    law = _lib.LAW_LOG_STRAIN_J2
+    gradient_name = "DeformationGradient"
+    flux_name = "FirstPiolaKirchhoffStress"
+
+    def __init__(self, s0: float, H0: float, E: float = 210e9, nu: float = 0.3):
+        self.s0 = float(s0)
+        self.H0 = float(H0)
+        self.E = float(E)
+        self.nu = float(nu)
+        if not (self.E > 0.0 and -1.0 < self.nu < 0.5 and self.s0 > 0.0 and self.H0 >= 0.0
+                and all(map(_isfinite, (self.E, self.nu, self.s0, self.H0)))):
+            raise ValueError("logarithmic-strain plasticity: E > 0, -1 < nu < 0.5, s0 > 0 and H0 >= 0 (all finite); "
+                             f"got E={E}, nu={nu}, s0={s0}, H0={H0}")
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict):
+        """The ``material_properties`` of the demo: ``HardeningSlope`` and ``YieldStrength`` (the demo's key; ``YieldStress``, the
+        glossary name, is taken too).  ``E`` and ``nu`` are written into the behaviour file and are no material properties."""
+        props = dict(props)
+        extra = set(props) - {"HardeningSlope", "YieldStrength", "YieldStress"}
+        if extra:
+            raise ValueError(f"logarithmic-strain plasticity material properties: unknown {sorted(extra)} (the behaviour has YieldStrength, "
+                             "HardeningSlope)")
+        if "YieldStrength" in props and "YieldStress" in props:
+            raise ValueError("logarithmic-strain plasticity material properties: YieldStrength and YieldStress name the same property, pass one")
+        missing = [k for k, ok in (("YieldStrength", "YieldStrength" in props or "YieldStress" in props),
+                                   ("HardeningSlope", "HardeningSlope" in props)) if not ok]
+        if missing:
+            raise ValueError(f"logarithmic-strain plasticity material properties: missing {missing}")
+        return cls(s0=float(props.get("YieldStrength", props.get("YieldStress"))), H0=float(props["HardeningSlope"]))
+
+    def params(self):
+        return [self.E, self.nu, self.s0, self.H0]
+
+    def flat_properties(self):
+        return {"E": self.E, "nu": self.nu, "s0": self.s0, "H0": self.H0}
+
+
 class OrthotropicElasticity(SmallStrainBehavior):
     """Small-strain orthotropic elasticity in a material frame (the orthotropic form of MFront's ``StandardElasticity`` brick, as
     ``tests/mfront/MericCailletaudSingleCrystalViscoPlasticity.mfront:18-28`` sets it up): nine constants ``E1, E2, E3, nu12,

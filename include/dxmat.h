@@ -162,7 +162,21 @@ enum {
    * Restrictions and dxm_stats as for DXM_LAW_HEAT_STATIONARY (n_nan also counts a non-finite Enthalpy).
    * params = [Tm, ks, cs, kl, cl, dhsl, Tsmooth], finite, Tsmooth > 0 */
   DXM_LAW_HEAT_PHASE_CHANGE = 17,
-  DXM_LAW_COUNT = 18
+  /* finite-strain logarithmic-strain J2 plasticity with linear hardening (the reference's
+   * demos/mfront/finite_strain_elastoplasticity/LogarithmicStrainPlasticity.mfront, restated from its equations): gradient F (9),
+   * flux PK1 (9), full 81-entry dP/dF.  The Hencky strain E = 1/2 log(F^T F) goes through the small-strain radial return of
+   * DXM_LAW_J2_LINEAR (Hooke, Mises, R(p) = s0 + H0 p) and its stress T is mapped back to PK1 by the derivatives of the tensor
+   * logarithm (DESIGN.md section "Logarithmic-strain J2 plasticity"); closed form, no local iteration.
+   * Internal state variables ElasticStrain (6; written by every update) and EquivalentPlasticStrain (1), MFront vector
+   * convention; the gradient handed in is the TOTAL F, so the update is driven by a hidden state field 2, the logarithmic
+   * plastic strain (6): dxm_set_state / dxm_get_state address it, a state set through field 0 alone does not change the next
+   * update.  Points with det F <= 0 or a non-finite F give NaN outputs and count in dxm_stats.n_nan; n_plastic counts the points
+   * that yield; n_not_converged and max_local_iters are 0.
+   * Only DXM_TANGENT_FULL; no material frame, no per-point parameter fields, no fused displacement gradient (option
+   * fused_gradient 0), not served by a custom-hardening build.
+   * params = [E, nu, s0, H0] with E > 0, -1 < nu < 0.5, s0 > 0, H0 >= 0, all finite */
+  DXM_LAW_LOG_STRAIN_J2 = 19,   /* id 18 is not assigned */
+  DXM_LAW_COUNT = 20
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

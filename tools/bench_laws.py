@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -268,8 +268,8 @@ def main():
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
-                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws):
-        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal or heat-transfer law")
+                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "log_strain" in a.laws):
+        ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal, heat-transfer or logarithmic-strain law")
     import torch
 
     import dolfinx_materials_amd.materials as jm
@@ -300,6 +300,12 @@ def main():
             rng = np.random.default_rng(2025)
             eye = np.array([1.0, 1, 1, 0, 0, 0, 0, 0, 0])
             beh, hist = jm.OgdenHyperelasticity(), [eye + 0.2 * (rng.random((n, 9)) - 0.5) for _ in range(2)]
+        elif law == "log_strain":
+            # the demo's material properties; F = I + 2e-3 U(-1/2, 1/2), the family of the law's parity tests (half of the points
+            # yield in either increment; every tile costs the same: the update is a closed form)
+            rng = np.random.default_rng(2026)
+            eye = np.array([1.0, 1, 1, 0, 0, 0, 0, 0, 0])
+            beh, hist = jm.LogarithmicStrainPlasticity(250e6, 1e6), [eye + 2e-3 * (rng.random((n, 9)) - 0.5) for _ in range(2)]
         elif law == "hosford":
             # the J2-linear parameters with the behaviour file's exponent a = 10, uniform (zero) state, the headline increments
             beh, hist = jm.HosfordIsotropicHardening(el, jm.LinearHardening(SIG0_LIN, H_LIN), a=10.0), j2_history(n)[1:3]
@@ -315,7 +321,7 @@ def main():
         else:
             path = fefp_path(n)
             beh, hist = jm.FeFpJ2Plasticity(el, jm.VoceHardening(SIG0_F, SIGU_F, B_F)), [path[9], path[18]]
-        sym = a.sym and law not in ("fefp", "ogden")
+        sym = a.sym and law not in ("fefp", "ogden", "log_strain")
         m = JAXMaterial(beh, tangent_layout="sym" if sym else "full")
         m.set_data_manager(n)
         ng, nf = m._info.n_grad, m._info.n_flux
@@ -367,14 +373,14 @@ def main():
             elif j2_linear_ms:
                 r["ratio_to_j2_linear"] = round(float(np.median(r["kernel_ms_repeats"])) / j2_linear_ms, 3)
                 r["byte_ratio_to_j2_linear"] = round(544 / 496, 3)
-        if law in ("fefp", "ogden"):   # same-process comparison of the two finite-strain kernels: two more timings each, for the spread
+        if law in ("fefp", "ogden", "log_strain"):   # same-process comparison of the two finite-strain kernels: two more timings each, for the spread
             r["kernel"] = m.kernel_name
             r["kernel_ms_repeats"] = [round(ms, 4), round(timed(), 4), round(timed(), 4)]
             if law == "fefp":
                 fefp_ms = float(np.median(r["kernel_ms_repeats"]))
             elif fefp_ms:
                 r["ratio_to_fefp"] = round(float(np.median(r["kernel_ms_repeats"])) / fefp_ms, 3)
-                r["byte_ratio_to_fefp"] = round(840 / 976, 3)
+                r["byte_ratio_to_fefp"] = round(ab / 976, 3)
         if law == "ramberg_osgood":
             r["kernel"] = m.kernel_name
             if sweep:
