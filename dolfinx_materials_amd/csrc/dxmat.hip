@@ -37,6 +37,7 @@
 #include "single_crystal.hpp"
 #include "heat_transfer.hpp"
 #include "log_strain.hpp"
+#include "fs_single_crystal.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -352,6 +353,27 @@ static int build_log_strain(const double* p, LawParams& q) {
   return 0;
 }
 
+// [E, nu, G, n, K, tau0, Q, b, d, C, h_self, h_coplanar, h_Hirth, h_collinear, h_glissile, h_Lomer]: the cubic stiffness is the
+// orthotropic law's with E1 = E2 = E3 = E, nu12 = nu23 = nu13 = nu, G12 = G23 = G13 = G, in the same twelve doubles; the rest is
+// read from the handle's parameters by the launcher
+static int build_fs_single_crystal(const double* p, LawParams& q) {
+  static const char* const names[16] = {"E", "nu", "G", "n", "K", "tau0", "Q", "b", "d", "C", "h_self", "h_coplanar", "h_Hirth", "h_collinear",
+                                        "h_glissile", "h_Lomer"};
+  for (int k = 0; k < 16; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "finite-strain single-crystal viscoplasticity: %s must be finite, got %g", names[k], p[k]);
+  if (!(p[0] > 0.0)) return fail(-1, "finite-strain single-crystal viscoplasticity: E must be > 0, got %g", p[0]);
+  if (!(p[1] > -1.0 && p[1] < 0.5)) return fail(-1, "finite-strain single-crystal viscoplasticity: nu must lie in (-1, 0.5), got %g", p[1]);
+  if (!(p[2] > 0.0)) return fail(-1, "finite-strain single-crystal viscoplasticity: G must be > 0, got %g", p[2]);
+  if (!(p[3] >= 1.0)) return fail(-1, "finite-strain single-crystal viscoplasticity: the Norton exponent n must be >= 1, got %g", p[3]);
+  if (!(p[4] > 0.0)) return fail(-1, "finite-strain single-crystal viscoplasticity: K must be > 0, got %g", p[4]);
+  if (!(p[5] >= 0.0)) return fail(-1, "finite-strain single-crystal viscoplasticity: tau0 must be >= 0, got %g", p[5]);
+  if (!(p[7] >= 0.0)) return fail(-1, "finite-strain single-crystal viscoplasticity: b must be >= 0, got %g", p[7]);
+  if (!(p[8] >= 0.0)) return fail(-1, "finite-strain single-crystal viscoplasticity: d must be >= 0, got %g", p[8]);
+  if (!(p[9] >= 0.0)) return fail(-1, "finite-strain single-crystal viscoplasticity: C must be >= 0, got %g", p[9]);
+  const double cubic[9] = {p[0], p[0], p[0], p[1], p[1], p[1], p[2], p[2], p[2]};
+  return build_orthotropic(cubic, q);
+}
+
 // ---- launchers (defined in the launch section, where the handle is complete) ----
 template <int LAW> static void launch_small_strain(const LaunchArgs& a);
 static void launch_fefp_voce(const LaunchArgs& a);
@@ -364,6 +386,7 @@ static void launch_single_crystal(const LaunchArgs& a);
 static void launch_heat_stationary(const LaunchArgs& a);
 static void launch_heat_phase_change(const LaunchArgs& a);
 static void launch_log_strain(const LaunchArgs& a);
+static void launch_fs_single_crystal(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -705,11 +728,48 @@ constexpr LawDesc law_log_strain_j2() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15 and 18 are not assigned and stay empty rows (law_known)
+// Finite-strain FCC single-crystal viscoplasticity: F in (72 B) and the four state fields read (360); PK1 (72), dP/dF (648) and the
+// four state fields (360) out: 1512 B/point, plus nine 8 B streams with a frame field.  A yielded point reads its cumulated slips
+// and back strains a second time in its Newton round (192 B, cache hits: not counted)
+constexpr LawDesc law_fs_single_crystal() {
+  LawDesc d{};
+  d.id = DXM_LAW_FS_SINGLE_CRYSTAL_FCC;
+  d.n_grad = d.n_flux = 9;
+  d.n_params = d.n_params_custom = 16;
+  d.n_isv_fields = d.n_fields = 4;
+  state_field(d, 0, "PlasticSlip", 12, FX_SLOT_G);
+  state_field(d, 1, "EquivalentViscoplasticSlip", 12, FX_SLOT_P);
+  state_field(d, 2, "BackStrain", 12, FX_SLOT_A);
+  state_field(d, 3, "PlasticPartOfTheDeformationGradient", 9, FX_SLOT_FP);
+  d.unit_fields = 1u << 3;   // the 9-vector starts with the diagonal: the three slots init_state fills
+  d.n_slots = FX_NSLOTS;
+  d.alg_bytes = 1512;
+  d.kernel = "fs_single_crystal_kernel<0";
+  d.frame_kernel[0] = "fs_single_crystal_kernel<1";
+  d.frame_kernel[1] = "fs_single_crystal_kernel<2";
+  d.no_fields = "per-point parameter fields are not served for finite-strain single-crystal viscoplasticity: its constants are formed "
+                "once per handle";
+  d.build = build_fs_single_crystal;
+  d.stock_only = "finite-strain single-crystal viscoplasticity has no isotropic hardening law to replace: it is served by the stock "
+                 "libdxmat, not by a custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(fs_single_crystal_kernel_fn);
+  d.blocks_per_cu = FX_BLOCKS_PER_CU;   // fs_single_crystal.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.set_refusal = "the finite-strain single-crystal tangent dP/dF is 81 independent numbers: only DXM_TANGENT_FULL is available, no packed "
+                  "record (sym / coef / pack4) exists for this law";
+  d.launch_refusal = "the finite-strain single-crystal tangent is 81 independent numbers: only the full block exists for this law";
+  d.no_fused = d.no_displacement = "the finite-strain single-crystal kernel takes F as an array: the displacement forms "
+                                   "(dxm_integrate_displacement*) and the fused displacement gradient are not served for this law";
+  d.launch = DXM_STOCK_ONLY(launch_fs_single_crystal);   // fs_single_crystal.hip: F from the (N, 9) array, the handle's frame, dt
+  d.rate_dependent = true;
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18 and 20 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
-    law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(),
+    law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(), {}, law_fs_single_crystal(),
 };
 
 constexpr bool rows_in_place() {
@@ -719,8 +779,8 @@ constexpr bool rows_in_place() {
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
-                  !kLaws[18].kernel,
-              "ids 6, 8, 9, 11, 13, 15 and 18 are not assigned");
+                  !kLaws[18].kernel && !kLaws[20].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18 and 20 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -1566,6 +1626,20 @@ static void launch_log_strain(const LaunchArgs& a) {
   dxm_material* m = a.m;
   log_strain_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
                     m->d_stats + a.stats_off);
+}
+
+static void launch_fs_single_crystal(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  const double* p = m->raw_params.data();   // 16 values (build_fs_single_crystal)
+  const OrthoStiffness s = ortho_load(m->prm);
+  FxParams sp{};
+  sp.c11 = s.c[0]; sp.c12 = s.c[1]; sp.g2 = s.g2[0];
+  sp.n = p[3]; sp.K = p[4]; sp.tau0 = p[5]; sp.b = p[7]; sp.d = p[8]; sp.C = p[9];
+  for (int k = 0; k < 6; ++k) sp.qh[k] = p[6] * p[10 + k];
+  sp.dt = a.dt;
+  fs_single_crystal_launch(m->frame_kind, a.grid, a.st, m->prm, sp, a.cnt, a.grad, m->frame_uniform,
+                           m->frame_streams ? m->frame_streams + a.off : nullptr, m->ld, m->state[0] + a.off, m->state[1] + a.off, m->ld,
+                           a.flux, a.ct, m->d_stats + a.stats_off);
 }
 
 static void launch_orthotropic(const LaunchArgs& a) {

@@ -122,6 +122,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_SINGLE_CRYSTAL_FCC:
             raise ValueError("the single-crystal tangent is not symmetric (interaction hardening): no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for this law; use 'full'")
+        if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_FS_SINGLE_CRYSTAL_FCC:
+            raise ValueError("the finite-strain single-crystal tangent dP/dF is 81 independent numbers: no packed tangent record "
+                             f"(tangent_layout={tangent_layout!r}) exists for this law; use 'full'")
         if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_HEAT_STATIONARY, _lib.LAW_HEAT_PHASE_CHANGE):
             raise ValueError("the heat-transfer tangent is several blocks (flux / gradient, flux / temperature, enthalpy / temperature), not "
                              f"a symmetric 6x6: no packed tangent record (tangent_layout={tangent_layout!r}) exists for these laws; use 'full'")
@@ -180,7 +183,7 @@ class HIPMaterial:
     def frame_fused(self):
         """Whether the law rotates into a material frame inside its kernel (orthotropic elasticity, single-crystal viscoplasticity): ``rotation_matrix`` can then
         be set, and ``rotate_gradients / rotate_fluxes / rotate_tangent_operator`` leave the arrays alone."""
-        return self.behavior.law in (_lib.LAW_ORTHOTROPIC_ELASTIC, _lib.LAW_SINGLE_CRYSTAL_FCC)
+        return self.behavior.law in (_lib.LAW_ORTHOTROPIC_ELASTIC, _lib.LAW_SINGLE_CRYSTAL_FCC, _lib.LAW_FS_SINGLE_CRYSTAL_FCC)
 
     @property
     def rotation_matrix(self):
@@ -694,6 +697,9 @@ class HIPMaterial:
                 self._serial0 += 1
             elif key == "be_bar" and self._has_be_bar:
                 continue  # handled below together with F
+            elif key == "PlasticPartOfTheDeformationGradient" and self.behavior.law == _lib.LAW_FS_SINGLE_CRYSTAL_FCC:
+                self._retire_final_views(materializing=True)
+                self._set_state(isv_names.index(key), _fp_rows(a))
             else:
                 self._retire_final_views(materializing=True)   # dxm_set_state gives s1 its own storage back: its device copies go
                 self._set_state(isv_names.index(key), a)
@@ -1338,3 +1344,21 @@ class HIPMaterial:
         rc = self._chk(self._lib.dxm_get_stats(self._require(), C.byref(st)))
         self.last_stats = st.as_dict()
         return rc, self.last_stats
+
+
+def _fp_rows(a):
+    """The plastic part of the deformation gradient as the kernel takes it: a row whose nine entries are all exactly zero (the
+    zero Functions the reference's ``initialize_state`` hands over) becomes the identity; a singular row that is not all zero is
+    refused."""
+    a = np.array(a, dtype=np.float64, order="C")
+    zero = ~a.any(axis=1)
+    a[zero, :3] = 1.0
+    m = np.empty((a.shape[0], 3, 3))
+    for t, (i, j) in enumerate(zip((0, 1, 2, 0, 1, 0, 2, 1, 2), (0, 1, 2, 1, 0, 2, 0, 2, 1))):
+        m[:, i, j] = a[:, t]
+    det = np.linalg.det(m)
+    bad = ~(np.isfinite(det) & (det != 0.0))
+    if bad.any():
+        raise ValueError(f"PlasticPartOfTheDeformationGradient: row {int(np.nonzero(bad)[0][0])} is singular and not all zero "
+                         f"(determinant {det[bad][0]!r}); {int(bad.sum())} such rows")
+    return a

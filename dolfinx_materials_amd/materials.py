@@ -545,6 +545,119 @@ class MericCailletaudSingleCrystalViscoPlasticity(OrthotropicElasticity):
                 **{f"interaction.{i}": v for i, v in enumerate(self.interaction)}}
 
 
+class FCCMericCailletaudFiniteStrainSingleCrystalViscoPlasticity(FiniteStrainBehavior):
+    """Finite-strain FCC single-crystal viscoplasticity (the reference's
+    ``mfront_materials/FCCMericCailletaudFiniteStrainSingleCrystalViscoPlasticity.mfront``): multiplicative ``F = Fe Fp``, cubic
+    elasticity of ``E, nu, G`` between the Green-Lagrange strain of ``Fe`` and its second Piola-Kirchhoff stress, the twelve
+    ``{111}<01-1>`` systems, Norton flow, interaction hardening and Armstrong-Frederick back strain of
+    :class:`MericCailletaudSingleCrystalViscoPlasticity` driven by the Mandel stress on the non-symmetrised ``m_i x n_i``.  The
+    file's interaction matrix is self-hardening only, which is the default here.  Rate-dependent: the time increment is
+    ``material.dt`` (or the ``dt`` of the call).
+
+    Gradient ``DeformationGradient`` (9), flux ``FirstPiolaKirchhoffStress`` (9), tangent block ``(9, 9)``.  Internal state
+    variables, all in the material frame: ``PlasticSlip`` (12), ``EquivalentViscoplasticSlip`` (12), ``BackStrain`` (12),
+    ``PlasticPartOfTheDeformationGradient`` (9, the identity at the start).  MFront's other variables are functions of ``F`` and
+    this state: :meth:`derived_state` returns them under MFront's names.  The systems are numbered as for the small-strain law,
+    which is this library's order, not necessarily MFront's.
+
+    ``rotation_matrix`` and ``set_frame`` as for :class:`OrthotropicElasticity` (rows = material axes).  Tangent layout ``"full"``
+    only; uniform properties only; ``F`` is passed as an array (no displacement forms)."""
+
+    law = _lib.LAW_FS_SINGLE_CRYSTAL_FCC
+    gradient_name = "DeformationGradient"
+    flux_name = "FirstPiolaKirchhoffStress"
+    #: the ten material properties of the behaviour file, in the order of the parameter vector
+    NAMES = ("E", "nu", "G", "n", "K", "tau0", "Q", "b", "d", "C")
+    #: the file's interaction matrix, [self, coplanar, Hirth, collinear, glissile, Lomer]
+    INTERACTION = (1.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+    def __init__(self, E, nu, G, n, K, Q, b, tau0, d, C, interaction=INTERACTION):
+        for name, v in zip(("E", "nu", "G", "n", "K", "Q", "b", "tau0", "d", "C"), (E, nu, G, n, K, Q, b, tau0, d, C)):
+            object.__setattr__(self, name, float(v))
+        h = tuple(float(v) for v in interaction)
+        if len(h) != 6:
+            raise ValueError(f"finite-strain single-crystal viscoplasticity: the interaction matrix takes six coefficients, got {len(h)}")
+        object.__setattr__(self, "interaction", h)
+        self.validate()
+
+    def validate(self):
+        """The rules the library applies in ``dxm_create`` / ``dxm_set_params``, with the offending value in the message."""
+        for k in self.NAMES:
+            if not _isfinite(getattr(self, k)):
+                raise ValueError(f"finite-strain single-crystal viscoplasticity: {k} must be finite, got {getattr(self, k)}")
+        for k, v in zip(("h_self", "h_coplanar", "h_Hirth", "h_collinear", "h_glissile", "h_Lomer"), self.interaction):
+            if not _isfinite(v):
+                raise ValueError(f"finite-strain single-crystal viscoplasticity: {k} must be finite, got {v}")
+        for k in ("E", "G", "K"):
+            if not getattr(self, k) > 0.0:
+                raise ValueError(f"finite-strain single-crystal viscoplasticity: {k} must be > 0, got {getattr(self, k)}")
+        if not -1.0 < self.nu < 0.5:
+            raise ValueError(f"finite-strain single-crystal viscoplasticity: nu must lie in (-1, 0.5), got {self.nu}")
+        if not self.n >= 1.0:
+            raise ValueError(f"finite-strain single-crystal viscoplasticity: the Norton exponent n must be >= 1, got {self.n}")
+        for k in ("tau0", "b", "d", "C"):
+            if not getattr(self, k) >= 0.0:
+                raise ValueError(f"finite-strain single-crystal viscoplasticity: {k} must be >= 0, got {getattr(self, k)}")
+
+    @classmethod
+    def from_mfront_properties(cls, props: dict):
+        """``material_properties`` keyed by the file's names, all ten: it gives no defaults.  ``interaction`` may be added."""
+        missing, extra = set(cls.NAMES) - set(props), set(props) - set(cls.NAMES) - {"interaction"}
+        if missing or extra:
+            raise ValueError(f"finite-strain single-crystal material properties: missing {sorted(missing)}, unknown {sorted(extra)}")
+        return cls(**{k: float(props[k]) for k in cls.NAMES}, interaction=props.get("interaction", cls.INTERACTION))
+
+    def __setattr__(self, name, value):
+        object.__setattr__(self, name, float(value) if name in self.NAMES else value)
+
+    def params(self):
+        return [getattr(self, k) for k in self.NAMES] + list(self.interaction)
+
+    def flat_properties(self):
+        return {**{k: getattr(self, k) for k in self.NAMES}, **{f"interaction.{i}": v for i, v in enumerate(self.interaction)}}
+
+    def derived_state(self, F, state, rotation=None):
+        """MFront's variables that are functions of ``F`` and the state, on the host: ``ElasticStrain`` (N, 6) -- the
+        Green-Lagrange strain of ``Fe``, tensor components [11, 22, 33, 12, 13, 23] --, ``ElasticPartOfTheDeformationGradient``
+        (N, 9) and ``ResolvedShearStress`` (N, 12), all in the material frame.  ``F`` (N, 9); ``state`` maps
+        ``PlasticPartOfTheDeformationGradient`` to (N, 9); ``rotation``: None, (3, 3) or (N, 3, 3), rows = material axes."""
+        import numpy as np
+
+        TI, TJ = (0, 1, 2, 0, 1, 0, 2, 1, 2), (0, 1, 2, 1, 0, 2, 0, 2, 1)   # the order of the 9-vectors
+
+        F = np.asarray(F, dtype=np.float64).reshape(-1, 9)
+        N = F.shape[0]
+        Fp = np.asarray(state["PlasticPartOfTheDeformationGradient"], dtype=np.float64).reshape(N, 9)
+
+        def mat(v):
+            m = np.empty((N, 3, 3))
+            for t in range(9):
+                m[:, TI[t], TJ[t]] = v[:, t]
+            return m
+
+        Fm = mat(F)
+        if rotation is not None:
+            R = np.broadcast_to(np.asarray(rotation, dtype=np.float64).reshape(-1, 3, 3), (N, 3, 3))
+            Fm = R @ Fm @ np.swapaxes(R, 1, 2)
+        Fe = Fm @ np.linalg.inv(mat(Fp))
+        Eel = 0.5 * (np.swapaxes(Fe, 1, 2) @ Fe - np.eye(3))
+        # the cubic stiffness: the normal block is the inverse of the compliance block
+        S3 = np.full((3, 3), -self.nu / self.E)
+        np.fill_diagonal(S3, 1.0 / self.E)
+        A = np.linalg.inv(S3)
+        S = 2.0 * self.G * Eel
+        tr = Eel[:, 0, 0] + Eel[:, 1, 1] + Eel[:, 2, 2]
+        for i in range(3):
+            S[:, i, i] = (A[0, 0] - A[0, 1]) * Eel[:, i, i] + A[0, 1] * tr
+        M = (np.swapaxes(Fe, 1, 2) @ Fe) @ S
+        planes = ((1, 1, 1), (-1, 1, 1), (1, -1, 1), (1, 1, -1))
+        dirs = ((0, 1, -1), (1, 0, -1), (1, -1, 0), (0, 1, 1), (1, 0, 1), (1, 1, 0))
+        mu = np.array([np.outer(d, p) / np.sqrt(6.0) for p in planes for d in dirs if np.dot(p, d) == 0])
+        return {"ElasticStrain": np.stack([Eel[:, 0, 0], Eel[:, 1, 1], Eel[:, 2, 2], Eel[:, 0, 1], Eel[:, 0, 2], Eel[:, 1, 2]], axis=1),
+                "ElasticPartOfTheDeformationGradient": np.stack([Fe[:, TI[t], TJ[t]] for t in range(9)], axis=1),
+                "ResolvedShearStress": np.einsum("nkl,ikl->ni", M, mu)}
+
+
 class HeatTransferBehavior(Behavior):
     """Base of the heat-transfer laws: gradient ``TemperatureGradient`` (3), flux ``HeatFlux`` (3) and one external state variable,
     ``Temperature``, the value at the end of the step (``HIPMaterial.update_external_state_variable``).  The gradient is 3 wide

@@ -176,7 +176,29 @@ enum {
    * fused_gradient 0), not served by a custom-hardening build.
    * params = [E, nu, s0, H0] with E > 0, -1 < nu < 0.5, s0 > 0, H0 >= 0, all finite */
   DXM_LAW_LOG_STRAIN_J2 = 19,   /* id 18 is not assigned */
-  DXM_LAW_COUNT = 20
+  /* finite-strain FCC single-crystal viscoplasticity (the reference's FCCMericCailletaudFiniteStrainSingleCrystalViscoPlasticity
+   * behaviour, restated from its equations; DESIGN.md section "Finite-strain single-crystal viscoplasticity" lists them).
+   * Gradient F (9), flux PK1 (9), tangent dP/dF (81 independent numbers), 9-vectors as for DXM_LAW_OGDEN.  Multiplicative
+   * F = Fe Fp, cubic stiffness of E, nu, G, St-Venant-Kirchhoff elasticity in the intermediate configuration, the twelve
+   * {111}<01-1> systems of DXM_LAW_SINGLE_CRYSTAL_FCC in the same order with mu_i = m_i x n_i (not symmetrised), Norton flow,
+   * interaction hardening and Armstrong-Frederick back strain as there; dFp^-1 = (I - sum dg_i mu_i) / det^(1/3).
+   * FRAME CONVENTION of DXM_LAW_ORTHOTROPIC_ELASTIC (dxm_set_frame*): F_m = R F R^T, P = R^T P_m R; gradient, flux and tangent
+   * are global, the state lives in the material frame.
+   * RATE-DEPENDENT like DXM_LAW_SINGLE_CRYSTAL_FCC: dt finite and >= 0, else the call fails; dt = 0 is the elastic response.
+   * State, all visible, all carried: PlasticSlip (12), EquivalentViscoplasticSlip (12), BackStrain (12),
+   * PlasticPartOfTheDeformationGradient (9, the identity after dxm_create).  MFront's other variables (ElasticStrain, the elastic
+   * part of F, ResolvedShearStress) are functions of F and this state.  MFront's entry names, its numbering of the systems and its
+   * det^(1/3) normalisation are not pinned (MFront is absent).
+   * DXM_TANGENT_FULL only.  No per-point parameter fields, no fused displacement gradient, no displacement forms, not served
+   * by a custom-hardening build.
+   * dxm_stats: n_plastic counts points with any f_i > 0 at the trial state; n_not_converged those that reach the iteration cap of
+   * dxm_set_newton (whose rtol is the absolute bound on the slip residuals): such a point writes its elastic trial response
+   * (St-Venant-Kirchhoff about the old Fp) and keeps the state bits it read; max_local_iters counts step halvings too (a step is
+   * halved while the largest slip residual grows or is not finite).
+   * params = [E, nu, G, n, K, tau0, Q, b, d, C, h_self, h_coplanar, h_Hirth, h_collinear, h_glissile, h_Lomer]: all finite,
+   * E, G, K > 0, -1 < nu < 0.5, n >= 1, tau0, b, d, C >= 0 */
+  DXM_LAW_FS_SINGLE_CRYSTAL_FCC = 21,   /* id 20 is not assigned */
+  DXM_LAW_COUNT = 22
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -201,6 +201,77 @@ def bench_single_crystal(a, j2_linear_ms):
             torch.cuda.empty_cache()
 
 
+def bench_fs_single_crystal(a):
+    """nine lines of the finite-strain single-crystal law (id 21): frame state x yielded fraction, on the points of its 50-digit
+    fixture (first parameter set, dt = 0.1; tests/fs_single_crystal_cases.py) repeated over the batch -- a yielded point carries the
+    state the fixture recorded for it, and a history belongs to its frame: the lines without a frame draw from the fixture's
+    frameless class, the uniform lines from its generic class under that class's one frame, the field lines from all three
+    classes.  Run `--laws single_crystal fs_single_crystal` to have law 14's lines of the same process beside them."""
+    import torch
+
+    import dolfinx_materials_amd.materials as jm
+    from dolfinx_materials_amd.jaxmat import JAXMaterial
+    import fs_single_crystal_cases as cs
+    from helpers import to_device
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+    names = {"PlasticSlip": "g", "EquivalentViscoplasticSlip": "p", "BackStrain": "a", "PlasticPartOfTheDeformationGradient": "Fp"}
+    props = dict(zip(("E", "nu", "G", "n", "K", "tau0", "Q", "b", "d", "C"), cs.PRM[:10]))
+    i = np.arange(n)
+    G = cs.GOLD
+    for frame in ("noframe", "uniform", "field"):
+        cls = {"noframe": (0,), "uniform": (2,), "field": (0, 1, 2)}[frame]
+        sel = (G["pset"] == 0) & (G["dt"] == cs.DT) & np.isin(G["has_frame"], cls)
+        pool = {yy: {"F": G["F"][sel & (G["yielded"] == yy)], "R": G["R"][sel & (G["yielded"] == yy)],
+                     **{k: G[k + "0"][sel & (G["yielded"] == yy)] for k in cs.STATE}} for yy in (True, False)}
+        ny, ne = len(pool[True]["F"]), len(pool[False]["F"])
+        for fraction in (0.0, 0.5, 1.0):
+            y = {0.0: np.zeros(n, dtype=bool), 0.5: i % 2 == 0, 1.0: np.ones(n, dtype=bool)}[fraction]
+            pick = lambda k: np.ascontiguousarray(np.where(y.reshape((n,) + (1,) * (pool[True][k].ndim - 1)),   # noqa: E731
+                                                           pool[True][k][i % ny], pool[False][k][i % ne]))
+            F = pick("F")
+            state = {q: pick(k) for q, k in names.items()}
+            m = JAXMaterial(jm.FCCMericCailletaudFiniteStrainSingleCrystalViscoPlasticity.from_mfront_properties(props))
+            m.set_data_manager(n)
+            m.dt = cs.DT
+            m.set_newton(cs.MAXIT, 1e-14)
+            if frame == "uniform":
+                m.set_frame(pool[True]["R"][0])
+            elif frame == "field":
+                m.set_frame(pick("R"))
+            m.set_initial_state_dict(state)
+            g = to_device(F)
+            del F, state
+            flux = torch.empty((n, 9), dtype=torch.float64, device=g.device)
+            ct = torch.empty((n, 81), dtype=torch.float64, device=g.device)
+
+            def timed():
+                for _ in range(a.warmup):
+                    m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)   # every launch reads the same s0: no advance
+                torch.cuda.synchronize()
+                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+                for e0, e1 in ev:
+                    e0.record()
+                    m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+                    e1.record()
+                torch.cuda.synchronize()
+                return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+            t = [timed(), timed(), timed()]
+            ms = float(np.median(t))
+            rc, stats = m.stats()
+            ab = m.algorithmic_bytes_per_point
+            r = {"law": f"fs_single_crystal+{frame}+yielded{int(100 * fraction)}", "points": n, "dt": cs.DT, "kernel": m.kernel_name,
+                 "kernel_ms_repeats": [round(x, 4) for x in t], "kernel_ms": round(ms, 4), "Mpoints_per_s": round(n / ms / 1e3, 1),
+                 "algorithmic_bytes_per_point": ab, "GBs": round(ab * n / ms / 1e6, 1), "frac_of_8TBs": round(ab * n / ms / 1e6 / 8000, 4),
+                 "plastic_fraction": round(stats["n_plastic"] / n, 4), "plastic_fraction_asked": round(float(y.mean()), 4),
+                 "max_local_iters": stats["max_local_iters"], "not_converged": stats["n_not_converged"], "nan": stats["n_nan"], "rc": rc}
+            print(json.dumps(r), flush=True)
+            del m, g, flux, ct
+            torch.cuda.empty_cache()
+
+
 def bench_heat_transfer(a, law, elastic_ms, elastic_repeats):
     """two lines: uniform temperature, one temperature per point (module docstring)"""
     import torch
@@ -268,7 +339,7 @@ def main():
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
-                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "log_strain" in a.laws):
+                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws):
         ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal, heat-transfer or logarithmic-strain law")
     import torch
 
@@ -287,6 +358,9 @@ def main():
     for law in a.laws:
         if law == "single_crystal":   # its own inputs, state and nine lines
             bench_single_crystal(a, j2_linear_ms)
+            continue
+        if law == "fs_single_crystal":   # its own inputs, state and nine lines
+            bench_fs_single_crystal(a)
             continue
         if law in ("heat_stationary", "heat_phase_change"):   # their own inputs and two lines each
             bench_heat_transfer(a, law, elastic_ms, elastic_repeats)
