@@ -15,3 +15,4 @@ class PerformanceWarning(UserWarning):
 
 from .hip_material import HIPMaterial, DataManager  # noqa: E402,F401
 from . import materials  # noqa: E402,F401
+from . import plane_stress  # noqa: E402,F401

@@ -124,3 +124,14 @@ def tangent_from_pack4(stress, pack):
     n = stress * pack[:, 3:4]
     n[:, :3] = (stress[:, :3] - third[:, None]) * pack[:, 3:4]
     return tangent_from_coefficients(np.concatenate([pack[:, :3], n], axis=1))
+
+
+def plane_stress_stiffness(E, nu):
+    """The plane-stress stiffness on ``[xx, yy, sqrt(2) xy]`` (Kelvin-Mandel), formed as the reference forms it
+    (``demos/cvxpy/cvxpy_materials.py:16-18``): ``E / (1 - nu^2) [[1, nu, 0], [nu, 1, 0], [0, 0, 1 - nu]]``."""
+    return (E / (1 - nu**2)) * np.array([[1.0, nu, 0.0], [nu, 1.0, 0.0], [0.0, 0.0, (1.0 - nu)]])
+
+
+def plane_stress_compliance(E, nu):
+    """Its inverse in closed form: ``1 / E [[1, -nu, 0], [-nu, 1, 0], [0, 0, 1 + nu]]``."""
+    return np.array([[1.0, -nu, 0.0], [-nu, 1.0, 0.0], [0.0, 0.0, 1.0 + nu]]) / E

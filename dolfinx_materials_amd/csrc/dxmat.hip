@@ -38,6 +38,7 @@
 #include "heat_transfer.hpp"
 #include "log_strain.hpp"
 #include "fs_single_crystal.hpp"
+#include "plane_stress.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -374,6 +375,57 @@ static int build_fs_single_crystal(const double* p, LawParams& q) {
   return build_orthotropic(cubic, q);
 }
 
+// [E, nu, sig0, q, tangent] (the reference's demos/cvxpy/cvxpy_materials.py:89-93 with q = 1); what the kernel reads is formed by
+// the launcher (plane_stress.hpp: PsParams).  nu < 1 suffices in plane stress: C is positive definite for -1 < nu < 1
+static int build_ps_quadratic(const double* p, LawParams& q) {
+  static const char* const names[5] = {"E", "nu", "sig0", "q", "tangent"};
+  for (int k = 0; k < 5; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "plane-stress quadratic yield set: %s must be finite, got %g", names[k], p[k]);
+  if (!(p[0] > 0.0)) return fail(-1, "plane-stress quadratic yield set: E must be > 0, got %g", p[0]);
+  if (!(p[1] > -1.0 && p[1] < 1.0)) return fail(-1, "plane-stress quadratic yield set: nu must lie in (-1, 1), got %g", p[1]);
+  if (!(p[2] > 0.0)) return fail(-1, "plane-stress quadratic yield set: sig0 must be > 0, got %g", p[2]);
+  if (!(p[3] > 0.0)) return fail(-1, "plane-stress quadratic yield set: the shear weight q must be > 0, got %g", p[3]);
+  if (!(p[4] == 0.0 || p[4] == 1.0))
+    return fail(-1, "plane-stress quadratic yield set: tangent must be 0 (the elastic C) or 1 (the algorithmic tangent), got %g", p[4]);
+  q.sig0 = p[2];
+  q.tol = q.rtol * p[2];   // on sqrt(s^T Q s) - sig0
+  return 0;
+}
+
+// [E, nu, M, n1_0, n2_0, d_0, ... ] padded to PS_MAX_PLANES rows (the rows past M are not read): half-planes n . (sI, sII) <= d in
+// the unordered plane of the principal stresses (cvxpy_materials.py:54-86 for the reference's two)
+static int build_ps_polygon(const double* p, LawParams&) {
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "plane-stress polygonal yield set: %s must be finite, got %g", k == 0 ? "E" : (k == 1 ? "nu" : "M"), p[k]);
+  if (!(p[0] > 0.0)) return fail(-1, "plane-stress polygonal yield set: E must be > 0, got %g", p[0]);
+  if (!(p[1] > -1.0 && p[1] < 1.0)) return fail(-1, "plane-stress polygonal yield set: nu must lie in (-1, 1), got %g", p[1]);
+  const int M = (int)p[2];
+  if (!(p[2] == (double)M) || M < 1 || M > PS_MAX_PLANES)
+    return fail(-1, "plane-stress polygonal yield set: the number of half-planes M must be an integer in [1, %d], got %g", PS_MAX_PLANES, p[2]);
+  for (int k = 0; k < M; ++k) {
+    const double* r = p + 3 + 3 * k;
+    if (!std::isfinite(r[0]) || !std::isfinite(r[1]) || !std::isfinite(r[2]))
+      return fail(-1, "plane-stress polygonal yield set: half-plane %d (%g, %g, %g) must be finite", k, r[0], r[1], r[2]);
+    if (!(r[2] > 0.0))
+      return fail(-1, "plane-stress polygonal yield set: half-plane %d has d = %g: d must be > 0, the origin lies strictly inside the set", k, r[2]);
+    if (r[0] == 0.0 && r[1] == 0.0) return fail(-1, "plane-stress polygonal yield set: half-plane %d has a zero normal", k);
+  }
+  // closed under the exchange of the two principal stresses: the mirror (n2, n1, d) of every row is a row, exactly.  Without it the
+  // projection of an ordered trial can leave the set
+  for (int k = 0; k < M; ++k) {
+    const double* r = p + 3 + 3 * k;
+    bool found = false;
+    for (int j = 0; j < M; ++j) {
+      const double* o = p + 3 + 3 * j;
+      found = found || (o[0] == r[1] && o[1] == r[0] && o[2] == r[2]);
+    }
+    if (!found)
+      return fail(-1, "plane-stress polygonal yield set: the half-planes are not symmetric under the exchange of the principal stresses: "
+                      "the mirror (%g, %g, %g) of half-plane %d is not in the list", r[1], r[0], r[2], k);
+  }
+  return 0;
+}
+
 // ---- launchers (defined in the launch section, where the handle is complete) ----
 template <int LAW> static void launch_small_strain(const LaunchArgs& a);
 static void launch_fefp_voce(const LaunchArgs& a);
@@ -387,6 +439,8 @@ static void launch_heat_stationary(const LaunchArgs& a);
 static void launch_heat_phase_change(const LaunchArgs& a);
 static void launch_log_strain(const LaunchArgs& a);
 static void launch_fs_single_crystal(const LaunchArgs& a);
+static void launch_ps_quadratic(const LaunchArgs& a);
+static void launch_ps_polygon(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -765,11 +819,67 @@ constexpr LawDesc law_fs_single_crystal() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18 and 20 are not assigned and stay empty rows (law_known)
+// The two plane-stress return mappings (plane_stress.hip): strain in (24 B) and the hidden plastic strain read (24); stress (24),
+// the 3x3 tangent (72) and the plastic strain (24) out: 168 B/point.  Strain and stress are 3 wide: gradient_kind below takes every
+// law that is not 9 wide for a 6-wide strain, so the refusals of the fused and displacement forms are what keeps a mesh gradient
+// away from these rows
+constexpr LawDesc plane_stress_law(int id, int n_params, const char* kernel) {
+  LawDesc d{};
+  d.id = id;
+  d.n_grad = d.n_flux = 3;
+  d.n_params = d.n_params_custom = n_params;
+  d.n_isv_fields = 0;
+  d.n_fields = 1;   // field 0 is hidden state: what the update is driven by (plane_stress.hpp)
+  state_field(d, 0, "PlasticStrain", 3, 0);
+  d.n_slots = PS_NSLOTS;
+  d.alg_bytes = 168;
+  d.kernel = kernel;
+  d.blocks_per_cu = PS_BLOCKS_PER_CU;   // plane_stress.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  return d;
+}
+
+constexpr LawDesc law_ps_quadratic() {
+  LawDesc d = plane_stress_law(DXM_LAW_PS_QUADRATIC, 5, "plane_stress_kernel<0");
+  d.build = build_ps_quadratic;
+  d.residency_kernel = DXM_STOCK_ONLY(plane_stress_quadratic_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_ps_quadratic);
+  d.no_fields = "per-point parameter fields are not served for the plane-stress quadratic yield set: its constants are formed once per handle";
+  d.stock_only = "the plane-stress quadratic yield set is perfectly plastic, it has no hardening law: it is served by the stock libdxmat, "
+                 "not by a custom-hardening build";
+  d.set_refusal = d.launch_refusal = "the plane-stress tangent is a 3x3 block of 9 entries, not a symmetric 6x6: only DXM_TANGENT_FULL is "
+                                     "available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fused = d.no_displacement = "the plane-stress quadratic yield set takes a 3-wide strain [xx, yy, sqrt(2) xy]: the mesh gradient "
+                                   "kernels evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
+                                   "fused displacement gradient are not served; pass the strain as an array";
+  d.no_frame = "the plane-stress quadratic yield set is isotropic: a material frame changes nothing in its update";
+  return d;
+}
+
+constexpr LawDesc law_ps_polygon() {
+  LawDesc d = plane_stress_law(DXM_LAW_PS_POLYGON, 3 + 3 * PS_MAX_PLANES, "plane_stress_kernel<1");
+  d.build = build_ps_polygon;
+  d.residency_kernel = DXM_STOCK_ONLY(plane_stress_polygon_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_ps_polygon);
+  d.no_fields = "per-point parameter fields are not served for the plane-stress polygonal yield set: its half-planes and vertices are "
+                "formed once per handle";
+  d.stock_only = "the plane-stress polygonal yield set is perfectly plastic, it has no hardening law: it is served by the stock libdxmat, "
+                 "not by a custom-hardening build";
+  d.set_refusal = d.launch_refusal = "the plane-stress tangent is a 3x3 block of 9 entries, not a symmetric 6x6: only DXM_TANGENT_FULL is "
+                                     "available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fused = d.no_displacement = "the plane-stress polygonal yield set takes a 3-wide strain [xx, yy, sqrt(2) xy]: the mesh gradient "
+                                   "kernels evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
+                                   "fused displacement gradient are not served; pass the strain as an array";
+  d.no_frame = "the plane-stress polygonal yield set is a function of the principal stresses: a material frame changes nothing in its update";
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20 and 22 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
-    law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(), {}, law_fs_single_crystal(),
+    law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(), {}, law_fs_single_crystal(), {},
+    law_ps_quadratic(), law_ps_polygon(),
 };
 
 constexpr bool rows_in_place() {
@@ -779,8 +889,8 @@ constexpr bool rows_in_place() {
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
-                  !kLaws[18].kernel && !kLaws[20].kernel,
-              "ids 6, 8, 9, 11, 13, 15, 18 and 20 are not assigned");
+                  !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18, 20 and 22 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -1694,6 +1804,75 @@ static void launch_heat_phase_change(const LaunchArgs& a) {
   hp.p[HT_HL3] = cc / 2;
   heat_transfer_launch(HT_PHASE_CHANGE, a.grid, a.st, hp, a.cnt, a.grad, m->ext_uniform[0], m->ext_kind[0] ? m->ext_field[0] + a.off : nullptr,
                        m->state[1] + a.off, a.flux, a.ct, m->d_stats + a.stats_off);
+}
+
+// the constants both plane-stress kernels read: the stiffness as cvxpy_materials.py:16-18 forms it
+static void ps_elastic_constants(PsParams& q, double E, double nu) {
+#pragma clang fp contract(off)
+  const double c0 = E / (1.0 - nu * nu);
+  q.p[PS_C11] = c0;
+  q.p[PS_C12] = c0 * nu;
+  q.p[PS_C33] = c0 * (1.0 - nu);
+  q.p[PS_E] = E;
+  q.p[PS_NU] = nu;
+  q.p[PS_CA] = E / (1.0 - nu);
+  q.p[PS_CB] = E / (1.0 + nu);
+}
+
+static void launch_ps_quadratic(const LaunchArgs& a) {
+#pragma clang fp contract(off)
+  dxm_material* m = a.m;
+  const double* p = m->raw_params.data();   // [E, nu, sig0, q, tangent] (build_ps_quadratic)
+  PsParams q{};
+  ps_elastic_constants(q, p[0], p[1]);
+  q.p[PS_QC] = p[3];
+  q.p[PS_SIG0] = p[2];
+  q.p[PS_TOL] = m->prm.tol;
+  q.p[PS_KMAX] = fmax(fmax(0.5 * q.p[PS_CA], 1.5 * q.p[PS_CB]), p[3] * q.p[PS_CB]);
+  q.p[PS_SIG0SQ] = p[2] * p[2];
+  q.maxit = m->prm.maxit;
+  plane_stress_launch(PS_QUADRATIC, p[4] != 0.0, a.grid, a.st, q, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
+                      m->d_stats + a.stats_off);
+}
+
+static void launch_ps_polygon(const LaunchArgs& a) {
+#pragma clang fp contract(off)
+  dxm_material* m = a.m;
+  const double* p = m->raw_params.data();   // [E, nu, M, (n1, n2, d) x 4] (build_ps_polygon)
+  PsParams q{};
+  ps_elastic_constants(q, p[0], p[1]);
+  const int M = (int)p[2];
+  q.planes = M;
+  constexpr double eps = 2.220446049250313e-16;
+  for (int k = 0; k < M; ++k) {
+    const double* r = p + 3 + 3 * k;
+    double* pl = q.p + PS_PLANE + k * PS_PLANE_REC;
+    pl[PL_N1] = r[0]; pl[PL_N2] = r[1]; pl[PL_D] = r[2];
+    // w = M^-1 n with M^-1 = [[C11, C12], [C12, C11]], the stiffness of the principal values
+    pl[PL_W1] = q.p[PS_C11] * r[0] + q.p[PS_C12] * r[1];
+    pl[PL_W2] = q.p[PS_C12] * r[0] + q.p[PS_C11] * r[1];
+    pl[PL_NW] = r[0] * pl[PL_W1] + r[1] * pl[PL_W2];
+    pl[PL_SLACK] = (8.0 * eps) * r[2];
+  }
+  // the vertices: intersections of two non-parallel rows at which every other row holds (to 64 eps d: three rows through one point)
+  int nv = 0;
+  for (int i = 0; i < M; ++i)
+    for (int j = i + 1; j < M; ++j) {
+      const double* ri = p + 3 + 3 * i;
+      const double* rj = p + 3 + 3 * j;
+      const double det = ri[0] * rj[1] - ri[1] * rj[0];
+      if (det == 0.0) continue;
+      const double x = (ri[2] * rj[1] - rj[2] * ri[1]) / det, y = (ri[0] * rj[2] - rj[0] * ri[2]) / det;
+      bool adm = std::isfinite(x) && std::isfinite(y);
+      for (int k = 0; k < M; ++k) {
+        const double* rk = p + 3 + 3 * k;
+        if (k != i && k != j) adm = adm && ((rk[0] * x + rk[1] * y) - rk[2] <= (64.0 * eps) * rk[2]);
+      }
+      if (adm) { q.p[PS_VERTEX + 2 * nv] = x; q.p[PS_VERTEX + 2 * nv + 1] = y; ++nv; }
+    }
+  q.vertices = nv;
+  plane_stress_launch(PS_POLYGON, 0, a.grid, a.st, q, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
+                      m->d_stats + a.stats_off);
 }
 #endif
 

@@ -128,6 +128,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_HEAT_STATIONARY, _lib.LAW_HEAT_PHASE_CHANGE):
             raise ValueError("the heat-transfer tangent is several blocks (flux / gradient, flux / temperature, enthalpy / temperature), not "
                              f"a symmetric 6x6: no packed tangent record (tangent_layout={tangent_layout!r}) exists for these laws; use 'full'")
+        if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_PS_QUADRATIC, _lib.LAW_PS_POLYGON):
+            raise ValueError("the plane-stress tangent is a 3x3 block of 9 entries, not a symmetric 6x6: no packed tangent record "
+                             f"(tangent_layout={tangent_layout!r}) exists for these laws; use 'full'")
         if not isinstance(jit, (bool, type(None))):
             raise TypeError("the second argument of JAXMaterial / HIPMaterial is `jit` (jaxmat.py:144); pass the GPU index as device=")
         self.jit = bool(jit)
@@ -319,6 +322,12 @@ class HIPMaterial:
         """Hosford: the kernel is handed the total strain, so its state is the plastic strain (hidden field 2), rebuilt from
         (Strain_n, ElasticStrain_n) when either is set.  Logarithmic-strain plasticity: the same with the Hencky strain of F_n."""
         return self.behavior.law in (_lib.LAW_HOSFORD_LINEAR, _lib.LAW_LOG_STRAIN_J2)
+
+    @property
+    def _has_plane_stress_state(self):
+        """The plane-stress return mappings: the kernel is handed the total strain and its state is the plastic strain (hidden
+        field 0, ``eps - C^-1 sigma``), rebuilt from (Strain_n, Stress_n) when either is set."""
+        return self.behavior.law in (_lib.LAW_PS_QUADRATIC, _lib.LAW_PS_POLYGON)
 
     @property
     def variables(self):
@@ -723,6 +732,17 @@ class HIPMaterial:
             else:
                 total = np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 6)
             self._set_state(2, _as_c(total - eel))
+
+        if self._has_plane_stress_state and (self._fname in state or self._gname in state):
+            # eps_p,n = eps_n - C^-1 sigma_n: the next trial stress is then sigma_n + C (eps - eps_n), the reference's (a prestress
+            # with a zero strain included)
+            from .conventions import plane_stress_compliance
+
+            S = plane_stress_compliance(self.behavior.E, self.behavior.nu)
+            eps_n = np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 3)
+            sig_n = np.asarray(self._flux[0], dtype=np.float64).reshape(self._n, 3)
+            self._retire_final_views(materializing=True)
+            self._set_state(0, _as_c(eps_n - sig_n @ S.T))
 
     def _set_state(self, field, a):
         for h, lo, hi, ptrs in self._blocks(a):

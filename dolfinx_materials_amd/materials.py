@@ -750,5 +750,85 @@ class HeatTransferPhaseChange(HeatTransferBehavior):
         return cls(**{**cls.MFRONT_DEFAULTS, **props})
 
 
+class PlaneStressBehavior(Behavior):
+    """Base of the plane-stress return mappings (the reference's ``demos/cvxpy/cvxpy_materials.py``): gradient ``Strain`` (3), flux
+    ``Stress`` (3), both ``[xx, yy, sqrt(2) xy]``; perfectly plastic; no internal state variable (the state of the reference is the
+    strain and the stress of the last accepted increment, which the material keeps as the gradient and the flux of ``s0``)."""
+
+    gradient_name = "Strain"
+    flux_name = "Stress"
+    ngrad = 3
+    nflux = 3
+
+    def _check_elastic(self):
+        if not (_isfinite(self.E) and _isfinite(self.nu) and self.E > 0.0 and -1.0 < self.nu < 1.0):
+            raise ValueError(f"{type(self).__name__}: E must be > 0 and -1 < nu < 1 (both finite); got E={self.E}, nu={self.nu}")
+
+
+class PlaneStressQuadraticYield(PlaneStressBehavior):
+    """Closest-point projection, in the elastic energy norm, of the trial stress onto ``{s^T Q s <= sig0^2}`` with
+    ``Q = [[1, -1/2, 0], [-1/2, 1, 0], [0, 0, q]]``.  ``q = 1`` is the matrix of the reference's ``PlaneStressvonMises``
+    (``cvxpy_materials.py:89-93``) -- NOT von Mises in Kelvin-Mandel components, where the third component is ``sqrt(2) s_xy``;
+    ``q = 3/2`` is von Mises.  ``tangent`` 0 hands back the elastic ``C`` like the reference, 1 the algorithmic tangent of the
+    yielded points."""
+
+    law = _lib.LAW_PS_QUADRATIC
+
+    def __init__(self, E, nu, sig0, q=1.0, tangent=0):
+        self.E, self.nu, self.sig0, self.q = float(E), float(nu), float(sig0), float(q)
+        self.tangent = int(tangent)
+        self._check_elastic()
+        if not (_isfinite(self.sig0) and self.sig0 > 0.0):
+            raise ValueError(f"{type(self).__name__}: sig0 must be finite and > 0, got {sig0}")
+        if not (_isfinite(self.q) and self.q > 0.0):
+            raise ValueError(f"{type(self).__name__}: the shear weight q must be finite and > 0, got {q}")
+        if tangent not in (0, 1):
+            raise ValueError(f"{type(self).__name__}: tangent must be 0 (elastic) or 1 (algorithmic), got {tangent!r}")
+
+    def params(self):
+        return [self.E, self.nu, self.sig0, self.q, float(self.tangent)]
+
+    def flat_properties(self):
+        return {"E": self.E, "nu": self.nu, "sig0": self.sig0, "q": self.q}
+
+
+class PlaneStressPolygonYield(PlaneStressBehavior):
+    """Closest-point projection onto ``{n_k . (s_I, s_II) <= d_k}``: at most four half-planes ``(n1, n2, d)`` in the unordered plane
+    of the two principal stresses, ``d > 0``, no zero normal, and the list closed under the exchange of the principal stresses (the
+    mirror ``(n2, n1, d)`` of every row is a row).  The tangent handed back is the elastic ``C``."""
+
+    law = _lib.LAW_PS_POLYGON
+    MAX_PLANES = 4
+
+    def __init__(self, E, nu, planes):
+        self.E, self.nu = float(E), float(nu)
+        self._check_elastic()
+        try:
+            rows = [tuple(float(v) for v in r) for r in planes]
+        except TypeError:
+            raise ValueError(f"{type(self).__name__}: planes must be a list of (n1, n2, d) rows, got {planes!r}") from None
+        if not 1 <= len(rows) <= self.MAX_PLANES or any(len(r) != 3 for r in rows):
+            raise ValueError(f"{type(self).__name__}: between 1 and {self.MAX_PLANES} half-planes (n1, n2, d), got {planes!r}")
+        for k, (n1, n2, d) in enumerate(rows):
+            if not all(map(_isfinite, (n1, n2, d))):
+                raise ValueError(f"{type(self).__name__}: half-plane {k} {rows[k]} must be finite")
+            if not d > 0.0:
+                raise ValueError(f"{type(self).__name__}: half-plane {k} has d = {d}: d must be > 0, the origin lies strictly inside the set")
+            if n1 == 0.0 and n2 == 0.0:
+                raise ValueError(f"{type(self).__name__}: half-plane {k} has a zero normal")
+        for k, (n1, n2, d) in enumerate(rows):
+            if (n2, n1, d) not in rows:
+                raise ValueError(f"{type(self).__name__}: the half-planes are not symmetric under the exchange of the principal stresses: "
+                                 f"the mirror {(n2, n1, d)} of half-plane {k} is not in the list")
+        self.planes = rows
+
+    def params(self):
+        flat = [v for r in self.planes for v in r]
+        return [self.E, self.nu, float(len(self.planes))] + flat + [0.0] * (3 * self.MAX_PLANES - len(flat))
+
+    def flat_properties(self):
+        return {"E": self.E, "nu": self.nu}
+
+
 def _isfinite(x):
     return x == x and abs(x) != float("inf")

@@ -198,7 +198,40 @@ enum {
    * params = [E, nu, G, n, K, tau0, Q, b, d, C, h_self, h_coplanar, h_Hirth, h_collinear, h_glissile, h_Lomer]: all finite,
    * E, G, K > 0, -1 < nu < 0.5, n >= 1, tau0, b, d, C >= 0 */
   DXM_LAW_FS_SINGLE_CRYSTAL_FCC = 21,   /* id 20 is not assigned */
-  DXM_LAW_COUNT = 22
+  /* plane-stress return mapping onto a quadratic yield set, perfectly plastic (the reference's PlaneStressvonMises,
+   * demos/cvxpy/cvxpy_materials.py:89-93, with its update :38-51, without the conic program).  Gradient Strain (3) and flux
+   * Stress (3) are [xx, yy, sqrt(2) xy] (Kelvin-Mandel); C = E/(1-nu^2) [[1, nu, 0], [nu, 1, 0], [0, 0, 1-nu]] (:16-18).
+   *   s_tr = C (eps - epsp_n),   s = argmin 1/2 (t - s_tr)^T C^-1 (t - s_tr) over K = {t^T Q t <= sig0^2},
+   *   Q = [[1, -1/2, 0], [-1/2, 1, 0], [0, 0, q]].
+   * q = 1 is the reference's matrix, which is NOT von Mises in Mandel components (the weight of its third component is its own);
+   * q = 3/2 is von Mises.  The projection is a scalar monotone Newton on one multiplier (DESIGN.md section "Plane-stress return
+   * mapping"), ended on the residual sqrt(s^T Q s) - sig0 <= rtol sig0 of dxm_set_newton.
+   * No user-visible internal state (the reference's state is Strain and Stress, the gradient and the flux of s0).  ONE HIDDEN
+   * state field 0, PlasticStrain (3) = eps - C^-1 s: dxm_set_state / dxm_get_state address it; a yielded point writes it, an
+   * elastic point writes back the bits it read.  A caller that sets a Strain / Stress state sets epsp_n = eps_n - C^-1 s_n.
+   * tangent = 0 writes C at every point (the reference's); tangent = 1 writes the algorithmic tangent of a yielded point,
+   * A - (A n)(A n)^T / (n^T A n) with A = (C^-1 + l Q)^-1 and n = Q s, and C at an elastic one.  9 entries, row-major.
+   * DXM_TANGENT_FULL only; no material frame, no per-point parameter fields, none of the displacement forms, no fused
+   * displacement gradient (the mesh gradient kernels evaluate 6-wide strains or F), not served by a custom-hardening build.
+   * dxm_stats: n_plastic counts the projected points; max_local_iters is the largest number of Newton steps a point took before
+   * its residual met the bound; n_not_converged counts the points that reached the cap of dxm_set_newton (they write their last
+   * iterate); n_nan counts points with a non-finite stress, state or (tangent = 1) tangent entry.
+   * algorithmic_bytes_per_point = 168: strain 24 + state 24 in, stress 24 + tangent 72 + state 24 out.
+   * params = [E, nu, sig0, q, tangent], all finite, E > 0, -1 < nu < 1, sig0 > 0, q > 0, tangent 0 or 1 */
+  DXM_LAW_PS_QUADRATIC = 23,   /* id 22 is not assigned */
+  /* plane-stress return mapping onto a polygonal yield set in the plane of the two principal stresses, perfectly plastic (the
+   * reference's Rankine, cvxpy_materials.py:54-65, and L1Rankine, :68-86).  Conventions, update, hidden state and restrictions as
+   * for DXM_LAW_PS_QUADRATIC.  K = {n_k . (sI, sII) <= d_k, k < M}, M <= 4, in the UNORDERED principal-stress plane: d_k > 0 (the
+   * origin strictly inside), no zero normal, and the list closed under the exchange of the principal stresses (the mirror
+   * (n2, n1, d) of every row is a row, exactly), else dxm_create refuses.  Trial and answer are coaxial: the answer is the
+   * nearest, in the energy norm, of the projections onto the rows' lines that keep the other rows and of the set's vertices.
+   * Rankine(ft, fc): (1,0,ft), (0,1,ft), (-1,0,fc), (0,-1,fc).  L1Rankine, a = (1/ft-1/fc)/2, b = (1/ft+1/fc)/2: (1,1,ft),
+   * (-1,-1,fc), (a+b,a-b,1), (a-b,a+b,1).  The tangent written is C (no consistent tangent for this law).
+   * dxm_stats: n_plastic counts the projected points; there is no local iteration: max_local_iters = n_not_converged = 0; n_nan as
+   * for DXM_LAW_PS_QUADRATIC.
+   * params = [E, nu, M, n1_0, n2_0, d_0, ..., n1_3, n2_3, d_3]: always 15 numbers, the rows past M are not read */
+  DXM_LAW_PS_POLYGON = 24,
+  DXM_LAW_COUNT = 25
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -28,6 +28,12 @@ temperature gradients.  Two lines each: a uniform temperature (the phase-change 
 point (the phase-change law: spread over the three branches), each with three timings and, when the elastic kernel ran in the same
 process (run `--laws elastic heat_stationary heat_phase_change`), its time next to the elastic kernel's scaled by the byte ratio
 120 (128) / 384 or 136 (144) / 384.
+
+ps_vonmises, ps_rankine, ps_l1rankine: the plane-stress return mappings with the cvxpy demo's parameters (E = 70e3, nu = 0.2, sig0 = 30,
+fc = 30, ft = 10).  Two lines each: a wholly elastic batch and a wholly yielded one (trials at 1.01 ... 100 times the surface; the
+quadratic law's Newton takes a point-dependent number of steps), each with three timings and, when the elastic kernel ran in the same
+process (run `--laws elastic heat_stationary ps_vonmises ps_rankine ps_l1rankine`), its time next to the elastic kernel's scaled by
+168 / 384.
 
 --param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
 (dxm_set_param_field; 1 = sig0, 2 = lambda and mu from an E field, 3 = both, 4 / 5 = H | sigu, b as well), in the same process and on
@@ -325,6 +331,57 @@ def bench_heat_transfer(a, law, elastic_ms, elastic_repeats):
     torch.cuda.empty_cache()
 
 
+def bench_plane_stress(a, law, elastic_ms, elastic_repeats):
+    """ps_vonmises, ps_rankine, ps_l1rankine (the demo's E = 70e3, nu = 0.2, sig0 = 30, fc = 30, ft = 10): two lines each, a wholly
+    elastic batch (trials at 0.05 ... 0.95 of the surface) and a wholly yielded one (1.01 ... 100 times), from a zero plastic strain;
+    168 B/point, next to the elastic kernel of the same process scaled by the byte ratio"""
+    import torch
+
+    import plane_stress_ref as ps
+    from dolfinx_materials_amd.plane_stress import L1Rankine, PlaneStressvonMises, Rankine
+    from helpers import to_device
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+    m = {"ps_vonmises": lambda: PlaneStressvonMises(70e3, 0.2, 30.0), "ps_rankine": lambda: Rankine(70e3, 0.2, ft=10.0, fc=30.0),
+         "ps_l1rankine": lambda: L1Rankine(70e3, 0.2, ft=10.0, fc=30.0)}[law]()
+    m.set_data_manager(n)
+    flux = torch.empty((n, 3), dtype=torch.float64, device="cuda:0")
+    ct = torch.empty((n, 9), dtype=torch.float64, device="cuda:0")
+    for tag, lo, hi in (("elastic", 0.05, 0.95), ("yielded", 1.01, 100.0)):
+        g = to_device(ps.random_trials(m.behavior.law, m.behavior.params(), n, seed=2027, lo=lo, hi=hi))
+
+        def timed():
+            for _ in range(a.warmup):
+                m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+            torch.cuda.synchronize()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+            for e0, e1 in ev:
+                e0.record()
+                m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+                e1.record()
+            torch.cuda.synchronize()
+            return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+        t = [timed(), timed(), timed()]
+        ms = float(np.median(t))
+        rc, stats = m.stats()
+        ab = m.algorithmic_bytes_per_point
+        r = {"law": f"{law}+{tag}", "points": n, "kernel": m.kernel_name, "kernel_ms_repeats": [round(x, 4) for x in t], "kernel_ms": round(ms, 4),
+             "Mpoints_per_s": round(n / ms / 1e3, 1), "algorithmic_bytes_per_point": ab, "GBs": round(ab * n / ms / 1e6, 1),
+             "frac_of_8TBs": round(ab * n / ms / 1e6 / 8000, 4), "plastic_fraction": round(stats["n_plastic"] / n, 4),
+             "max_local_iters": stats["max_local_iters"], "not_converged": stats["n_not_converged"], "nan": stats["n_nan"], "rc": rc}
+        if elastic_ms:
+            r["ratio_to_elastic"] = round(ms / elastic_ms, 3)
+            r["elastic_scaled_ms"] = round(elastic_ms * ab / 384, 4)
+            r["ratio_to_yardstick"] = round(ms / (elastic_ms * ab / 384), 3)
+            r["elastic_ms_repeats"] = elastic_repeats
+        print(json.dumps(r), flush=True)
+        del g
+    del m, flux, ct
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -339,7 +396,8 @@ def main():
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
-                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws):
+                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws or
+                         any(law.startswith("ps_") for law in a.laws)):
         ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal, heat-transfer or logarithmic-strain law")
     import torch
 
@@ -364,6 +422,9 @@ def main():
             continue
         if law in ("heat_stationary", "heat_phase_change"):   # their own inputs and two lines each
             bench_heat_transfer(a, law, elastic_ms, elastic_repeats)
+            continue
+        if law in ("ps_vonmises", "ps_rankine", "ps_l1rankine"):   # their own inputs and two lines each
+            bench_plane_stress(a, law, elastic_ms, elastic_repeats)
             continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
