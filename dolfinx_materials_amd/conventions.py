@@ -135,3 +135,36 @@ def plane_stress_stiffness(E, nu):
 def plane_stress_compliance(E, nu):
     """Its inverse in closed form: ``1 / E [[1, -nu, 0], [-nu, 1, 0], [0, 0, 1 + nu]]``."""
     return np.array([[1.0, -nu, 0.0], [-nu, 1.0, 0.0], [0.0, 0.0, 1.0 + nu]]) / E
+
+
+#: positions, in the 6-wide Mandel vector, of the four components [xx, yy, zz, sqrt(2) xy] of a plane-strain state
+PLANE_STRAIN_IDX = (0, 1, 2, 3)
+
+
+def embed_plane_strain(v4):
+    """(..., 4) ``[xx, yy, zz, sqrt(2) xy]`` (the 4-vector ``utils.py:146-150`` builds from a 2x2 tensor under the reference's
+    ``hypothesis="plane_strain"``) -> (..., 6) Mandel with zero out-of-plane shears."""
+    v4 = np.asarray(v4, dtype=np.float64)
+    if v4.shape[-1] != 4:
+        raise ValueError(f"a plane-strain vector has 4 components [xx, yy, zz, sqrt(2) xy], got shape {v4.shape}")
+    out = np.zeros(v4.shape[:-1] + (6,))
+    out[..., list(PLANE_STRAIN_IDX)] = v4
+    return out
+
+
+def restrict_plane_strain(v6):
+    """(..., 6) Mandel -> (..., 4) ``[xx, yy, zz, sqrt(2) xy]``: the components a plane-strain state has (the other two are
+    zero in such a state and are dropped, whatever they hold)."""
+    v6 = np.asarray(v6, dtype=np.float64)
+    if v6.shape[-1] != 6:
+        raise ValueError(f"a Mandel vector has 6 components, got shape {v6.shape}")
+    return np.ascontiguousarray(v6[..., list(PLANE_STRAIN_IDX)])
+
+
+def restrict_plane_strain_tangent(C66):
+    """(..., 6, 6) -> (..., 4, 4): rows and columns ``[0, 1, 2, 3]`` of a 6-wide tangent block, the block of a plane-strain law."""
+    C66 = np.asarray(C66, dtype=np.float64)
+    if C66.shape[-2:] != (6, 6):
+        raise ValueError(f"a 6-wide tangent block is (..., 6, 6), got shape {C66.shape}")
+    idx = list(PLANE_STRAIN_IDX)
+    return np.ascontiguousarray(C66[..., idx, :][..., :, idx])

@@ -39,6 +39,7 @@
 #include "log_strain.hpp"
 #include "fs_single_crystal.hpp"
 #include "plane_stress.hpp"
+#include "plane_strain.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -441,6 +442,7 @@ static void launch_log_strain(const LaunchArgs& a);
 static void launch_fs_single_crystal(const LaunchArgs& a);
 static void launch_ps_quadratic(const LaunchArgs& a);
 static void launch_ps_polygon(const LaunchArgs& a);
+template <int LAW> static void launch_plane_strain(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -874,12 +876,73 @@ constexpr LawDesc law_ps_polygon() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20 and 22 are not assigned and stay empty rows (law_known)
+// The plane-strain forms of laws 0 / 1 / 2 (plane_strain.hip): strain in (32 B), stress (32) and the 4x4 tangent (128) out: 192
+// B/point; the J2 laws read and write p and the 4-wide plastic strain (40 + 40): 272.  Strain and stress are 4 wide: gradient_kind
+// takes every law that is not 9 wide for a 6-wide strain, so the refusals of the fused and displacement forms are what keeps a mesh
+// gradient away from these rows.  Grid: 128 workgroups per CU for the elastic and the linear-hardening law, 256 for Voce, from two
+// sweeps at 1e7 points (plane_strain.hpp, profiles/r21_plane_strain.md); every other size is UNMEASURED for these kernels
+constexpr LawDesc plane_strain_law(int id, int n_params, int alg_bytes, const char* kernel) {
+  LawDesc d{};
+  d.id = id;
+  d.n_grad = d.n_flux = PE_DIM;
+  d.n_params = d.n_params_custom = n_params;
+  d.alg_bytes = alg_bytes;
+  d.kernel = kernel;
+  d.blocks_per_cu = PE_BLOCKS_PER_CU;   // plane_strain.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.set_refusal = d.launch_refusal = "the plane-strain tangent is a 4x4 block of 16 entries, not a symmetric 6x6: only DXM_TANGENT_FULL is "
+                                     "available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fields = "per-point parameter fields are not served under the plane-strain hypothesis: the field kernels are the 6-wide "
+                "DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE (embed the strain as [xx, yy, zz, xy, 0, 0] to use them)";
+  d.no_fused = d.no_displacement = "the plane-strain laws take a 4-wide strain [xx, yy, zz, sqrt(2) xy]: the mesh gradient kernels "
+                                   "evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
+                                   "fused displacement gradient are not served; pass the strain as an array";
+  d.no_frame = kNoFrame;
+  d.stock_only = "the plane-strain laws take the stock hardening laws only (linear, Voce): they are served by the stock libdxmat, not by "
+                 "a custom-hardening build";
+  return d;
+}
+
+constexpr void pe_j2_state(LawDesc& d) {
+  d.n_isv_fields = d.n_fields = 2;
+  state_field(d, 0, "p", 1, 0);
+  state_field(d, 1, "epsp", PE_DIM, 1);
+  d.n_slots = PE_NSLOTS;
+}
+
+constexpr LawDesc law_pe_elastic() {
+  LawDesc d = plane_strain_law(DXM_LAW_PE_ELASTIC_ISO, 2, 192, "plane_strain_kernel<0");
+  d.build = build_elastic;
+  d.residency_kernel = DXM_STOCK_ONLY(plane_strain_elastic_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_plane_strain<PE_ELASTIC>);
+  return d;
+}
+
+constexpr LawDesc law_pe_j2_linear() {
+  LawDesc d = plane_strain_law(DXM_LAW_PE_J2_LINEAR, 4, 272, "plane_strain_kernel<1");
+  pe_j2_state(d);
+  d.build = build_linear_hardening;
+  d.residency_kernel = DXM_STOCK_ONLY(plane_strain_j2_linear_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_plane_strain<PE_J2_LINEAR>);
+  return d;
+}
+
+constexpr LawDesc law_pe_j2_voce() {
+  LawDesc d = plane_strain_law(DXM_LAW_PE_J2_VOCE, 5, 272, "plane_strain_kernel<2");
+  pe_j2_state(d);
+  d.build = build_voce_hardening;
+  d.residency_kernel = DXM_STOCK_ONLY(plane_strain_j2_voce_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_plane_strain<PE_J2_VOCE>);
+  d.blocks_per_cu = PE_BLOCKS_PER_CU_VOCE;   // plane_strain.hpp
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22 and 25 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
     law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(), {}, law_fs_single_crystal(), {},
-    law_ps_quadratic(), law_ps_polygon(),
+    law_ps_quadratic(), law_ps_polygon(), {}, law_pe_elastic(), law_pe_j2_linear(), law_pe_j2_voce(),
 };
 
 constexpr bool rows_in_place() {
@@ -889,8 +952,8 @@ constexpr bool rows_in_place() {
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
-                  !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel,
-              "ids 6, 8, 9, 11, 13, 15, 18, 20 and 22 are not assigned");
+                  !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22 and 25 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -1873,6 +1936,13 @@ static void launch_ps_polygon(const LaunchArgs& a) {
   q.vertices = nv;
   plane_stress_launch(PS_POLYGON, 0, a.grid, a.st, q, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
                       m->d_stats + a.stats_off);
+}
+// the record of the handle's law is the 6-wide law's (build_elastic / build_linear_hardening / build_voce_hardening)
+template <int LAW> static void launch_plane_strain(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  const bool state = LAW != PE_ELASTIC;
+  plane_strain_launch(LAW, a.grid, a.st, m->prm, a.cnt, a.grad, state ? m->state[0] + a.off : nullptr, state ? m->state[1] + a.off : nullptr,
+                      m->ld, a.flux, a.ct, m->d_stats + a.stats_off);
 }
 #endif
 

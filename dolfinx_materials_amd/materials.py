@@ -175,13 +175,38 @@ def _hardening_properties(y):
     return {f"yield_stress.{k}": v for k, v in vars(y).items()}
 
 
+#: the modelling hypotheses served, the reference's strings (``dolfinx_materials/mfront.py:33-37``)
+HYPOTHESES = ("3d", "plane_strain")
+
+
+def _check_hypothesis(hypothesis):
+    if hypothesis == "axisymmetric":
+        raise NotImplementedError('hypothesis="axisymmetric" is not served yet (a follow-up: its 4-wide strain [rr, zz, tt, sqrt(2) rz] '
+                                  'needs a gradient of its own); "3d" and "plane_strain" are')
+    if hypothesis not in HYPOTHESES:
+        raise ValueError(f"hypothesis must be one of {list(HYPOTHESES)}, got {hypothesis!r}")
+    return hypothesis
+
+
+def _set_hypothesis(behavior, hypothesis):
+    """``"plane_strain"``: strain, stress and plastic strain are the 4-vectors ``[xx, yy, zz, sqrt(2) xy]`` of a 2x2 tensor
+    (``utils.py:146-150``), the tangent block is ``(4, 4)``."""
+    behavior.hypothesis = _check_hypothesis(hypothesis)
+    if hypothesis == "plane_strain":
+        behavior.ngrad = behavior.nflux = 4
+
+
 class ElasticBehavior(SmallStrainBehavior):
-    """Linear isotropic elasticity as a small-strain behaviour."""
+    """Linear isotropic elasticity as a small-strain behaviour; ``hypothesis="plane_strain"``: in the four components
+    ``[xx, yy, zz, sqrt(2) xy]``."""
 
     law = _lib.LAW_ELASTIC_ISO
 
-    def __init__(self, elasticity: LinearElasticIsotropic):
+    def __init__(self, elasticity: LinearElasticIsotropic, hypothesis: str = "3d"):
         self.elasticity = elasticity
+        _set_hypothesis(self, hypothesis)
+        if hypothesis == "plane_strain":
+            self.law = _lib.LAW_PE_ELASTIC_ISO
 
     def params(self):
         return [self.elasticity.E, self.elasticity.nu]
@@ -191,14 +216,23 @@ class ElasticBehavior(SmallStrainBehavior):
 
 
 class vonMisesIsotropicHardening(SmallStrainBehavior):
-    """Small-strain J2 plasticity with isotropic hardening (``plane_elastoplasticity.py:67-71``)."""
+    """Small-strain J2 plasticity with isotropic hardening (``plane_elastoplasticity.py:67-71``).  ``hypothesis="plane_strain"``
+    (what the reference's ``MFrontMaterial(..., hypothesis="plane_strain")`` asks for): strain, stress and ``epsp`` are the
+    4-vectors ``[xx, yy, zz, sqrt(2) xy]``, the tangent block is ``(4, 4)``; stock hardening laws only."""
 
-    def __init__(self, elasticity: LinearElasticIsotropic, yield_stress):
+    def __init__(self, elasticity: LinearElasticIsotropic, yield_stress, hypothesis: str = "3d"):
         self.elasticity = elasticity
+        _set_hypothesis(self, hypothesis)
+        if hypothesis == "plane_strain" and not isinstance(yield_stress, (LinearHardening, VoceHardening)):
+            raise TypeError('hypothesis="plane_strain" is served with the stock hardening laws only: yield_stress must be a '
+                            "materials.LinearHardening or materials.VoceHardening, not a CustomHardening or a traced callable "
+                            f"(got {type(yield_stress).__name__}); use the \"3d\" hypothesis with an embedded strain for those")
         self.yield_stress = _check_hardening(yield_stress)
-        self.law = (
-            _lib.LAW_J2_LINEAR if isinstance(self.yield_stress, LinearHardening) else _lib.LAW_J2_VOCE
-        )
+        linear = isinstance(self.yield_stress, LinearHardening)
+        if hypothesis == "plane_strain":
+            self.law = _lib.LAW_PE_J2_LINEAR if linear else _lib.LAW_PE_J2_VOCE
+        else:
+            self.law = _lib.LAW_J2_LINEAR if linear else _lib.LAW_J2_VOCE
         self.custom_hardening = self.yield_stress if isinstance(self.yield_stress, CustomHardening) else None
 
     def params(self):

@@ -231,7 +231,22 @@ enum {
    * for DXM_LAW_PS_QUADRATIC.
    * params = [E, nu, M, n1_0, n2_0, d_0, ..., n1_3, n2_3, d_3]: always 15 numbers, the rows past M are not read */
   DXM_LAW_PS_POLYGON = 24,
-  DXM_LAW_COUNT = 25
+  /* The plane-strain hypothesis of DXM_LAW_ELASTIC_ISO / DXM_LAW_J2_LINEAR / DXM_LAW_J2_VOCE (the reference's
+   * MFrontMaterial(..., hypothesis="plane_strain"), dolfinx_materials/mfront.py:33-37): the same three updates in the four
+   * components a plane-strain state has.  Gradient Strain (4) and flux Stress (4) are [xx, yy, zz, sqrt(2) xy]
+   * (utils.py:146-150 for a 2x2 tensor); eps_zz is read like any other component (a plane-strain caller passes 0) and sig_zz is
+   * returned.  The tangent is the 4x4 block d Stress / d Strain, 16 entries, row-major: the rows and columns [0, 1, 2, 3] of the
+   * 6-wide law's block (whose out-of-plane rest is zero for such a state).  DXM_TANGENT_FULL only.
+   * State of the two J2 laws: field 0 p (1), field 1 epsp (4, the same order), 5 SoA slots; the elastic law has none.
+   * Parameters, validation, dxm_set_newton and dxm_stats as for the 6-wide law of the same name.
+   * No per-point parameter fields, no material frame, no external state variable, none of the displacement forms and no fused
+   * displacement gradient (the mesh gradient kernels evaluate 6-wide strains or F), not served by a custom-hardening build.
+   * algorithmic_bytes_per_point = 192 (strain 32 in, stress 32 + tangent 128 out) / 272 (+ state 40 in, 40 out) / 272.
+   * params = [E, nu] / [E, nu, sig0, H] / [E, nu, sig0, sigu, b] */
+  DXM_LAW_PE_ELASTIC_ISO = 26,   /* id 25 is not assigned */
+  DXM_LAW_PE_J2_LINEAR = 27,
+  DXM_LAW_PE_J2_VOCE = 28,
+  DXM_LAW_COUNT = 29
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -34,6 +34,9 @@ fc = 30, ft = 10).  Two lines each: a wholly elastic batch and a wholly yielded 
 quadratic law's Newton takes a point-dependent number of steps), each with three timings and, when the elastic kernel ran in the same
 process (run `--laws elastic heat_stationary ps_vonmises ps_rankine ps_l1rankine`), its time next to the elastic kernel's scaled by
 168 / 384.
+
+plane_strain: the three laws of the plane-strain hypothesis (ids 26 / 27 / 28, 4-wide) each next to its 6-wide law (0 / 1 / 2) of the
+same process on the same strains, embedded; one line per law and batch (bench_plane_strain).
 
 --param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
 (dxm_set_param_field; 1 = sig0, 2 = lambda and mu from an E field, 3 = both, 4 / 5 = H | sigu, b as well), in the same process and on
@@ -382,6 +385,87 @@ def bench_plane_stress(a, law, elastic_ms, elastic_repeats):
     torch.cuda.empty_cache()
 
 
+def bench_plane_strain(a):
+    """--laws plane_strain: laws 26 / 27 / 28 next to laws 0 / 1 / 2 of the same process on the same strains, embedded.  One JSON line
+    per law and batch: kernel ms of both (median of three medians), fraction of 8 TB/s at the counted bytes (192 / 272 against 384 /
+    496), and the ratio of the 4-wide time to the 6-wide time scaled by the byte ratio.  The elastic law: one batch; the J2 laws: an
+    elastic batch (|eps| up to 0.9 sig0 / E), a mixed one (up to 3 sig0 / E) and a fully yielded one (deviatoric, 2 ... 4 sig0 / E),
+    each from the virgin state.  --blocks-per-cu: the 4-wide kernels at each of these grid sizes as well."""
+    import torch
+
+    import dolfinx_materials_amd.materials as jm
+    from dolfinx_materials_amd.conventions import embed_plane_strain
+    from dolfinx_materials_amd.jaxmat import JAXMaterial
+    from helpers import B_V, E, H_LIN, NU, SIG0_LIN, SIG0_V, SIGU_V, to_device
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+    el = jm.LinearElasticIsotropic(E=E, nu=NU)
+
+    def strains(kind, sig0, seed=2028):
+        rng = np.random.default_rng(seed)
+        d = rng.standard_normal((n, 4))
+        if kind == "yielded":
+            d[:, :3] -= d[:, :3].mean(axis=1, keepdims=True)
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        lo, hi = {"elastic": (0.0, 0.9), "mixed": (0.0, 3.0), "yielded": (2.0, 4.0)}[kind]
+        return d * rng.uniform(lo, hi, n)[:, None] * (sig0 / E)
+
+    def timed(m, g, flux, ct):
+        for _ in range(a.warmup):
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+        for e0, e1 in ev:
+            e0.record()
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+            e1.record()
+        torch.cuda.synchronize()
+        return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+    laws = (("elastic", lambda h: jm.ElasticBehavior(el, hypothesis=h), SIG0_LIN, ("mixed",)),
+            ("j2_linear", lambda h: jm.vonMisesIsotropicHardening(el, jm.LinearHardening(SIG0_LIN, H_LIN), hypothesis=h), SIG0_LIN, ("elastic", "mixed", "yielded")),
+            ("j2_voce", lambda h: jm.vonMisesIsotropicHardening(el, jm.VoceHardening(SIG0_V, SIGU_V, B_V), hypothesis=h), SIG0_V, ("elastic", "mixed", "yielded")))
+    for name, make, sig0, batches in laws:
+        m4, m6 = JAXMaterial(make("plane_strain")), JAXMaterial(make("3d"))
+        m4.set_data_manager(n)
+        m6.set_data_manager(n)
+        f4, c4 = torch.empty((n, 4), dtype=torch.float64, device="cuda:0"), torch.empty((n, 16), dtype=torch.float64, device="cuda:0")
+        f6, c6 = torch.empty((n, 6), dtype=torch.float64, device="cuda:0"), torch.empty((n, 36), dtype=torch.float64, device="cuda:0")
+        for tag in batches:
+            e4 = strains(tag, sig0)
+            g4, g6 = to_device(e4), to_device(embed_plane_strain(e4))
+            del e4
+            t4, t6 = [], []
+            for _ in range(3):          # interleaved: both kernels see the same drift of the machine
+                t6.append(timed(m6, g6, f6, c6))
+                t4.append(timed(m4, g4, f4, c4))
+            _, s4 = m4.stats()
+            _, s6 = m6.stats()
+            ms4, ms6 = float(np.median(t4)), float(np.median(t6))
+            b4, b6 = m4.algorithmic_bytes_per_point, m6.algorithmic_bytes_per_point
+            r = {"law": f"plane_strain:{name}+{tag}", "points": n, "kernel": m4.kernel_name, "kernel_ms_repeats": [round(x, 4) for x in t4],
+                 "kernel_ms": round(ms4, 4), "algorithmic_bytes_per_point": b4, "frac_of_8TBs": round(b4 * n / ms4 / 1e6 / 8000, 4),
+                 "six_wide_kernel": m6.kernel_name, "six_wide_ms_repeats": [round(x, 4) for x in t6], "six_wide_ms": round(ms6, 4),
+                 "six_wide_bytes_per_point": b6, "six_wide_frac_of_8TBs": round(b6 * n / ms6 / 1e6 / 8000, 4),
+                 "ratio_to_six_wide": round(ms4 / ms6, 3), "byte_ratio": round(b4 / b6, 3), "ratio_to_byte_scaled_six_wide": round(ms4 / (ms6 * b4 / b6), 3),
+                 "plastic_fraction": round(s4["n_plastic"] / n, 4), "same_plastic_count": s4["n_plastic"] == s6["n_plastic"],
+                 "max_local_iters": s4["max_local_iters"], "not_converged": s4["n_not_converged"], "nan": s4["n_nan"]}
+            if a.blocks_per_cu:
+                sweep = {}
+                for b in a.blocks_per_cu:
+                    m4.set_option("blocks_per_cu", b)
+                    sweep[b] = round(timed(m4, g4, f4, c4), 4)
+                m4.set_option("blocks_per_cu", 256 if name == "j2_voce" else 128)      # the shipped grid again (plane_strain.hpp)
+                r["kernel_ms_by_blocks_per_cu"] = sweep
+            print(json.dumps(r), flush=True)
+            del g4, g6
+        m4.close()
+        m6.close()
+        del m4, m6, f4, c4, f6, c6
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -391,13 +475,13 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0, help="also time the plain-C oracle on this many points")
     ap.add_argument("--sym", action="store_true", help="symmetric-packed tangent (small-strain laws)")
     ap.add_argument("--blocks-per-cu", type=int, nargs="+", default=None,
-                    help="ramberg_osgood: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
+                    help="ramberg_osgood, plane_strain: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
                          "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws or
-                         any(law.startswith("ps_") for law in a.laws)):
+                         any(law.startswith("ps_") for law in a.laws) or "plane_strain" in a.laws):
         ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal, heat-transfer or logarithmic-strain law")
     import torch
 
@@ -425,6 +509,9 @@ def main():
             continue
         if law in ("ps_vonmises", "ps_rankine", "ps_l1rankine"):   # their own inputs and two lines each
             bench_plane_stress(a, law, elastic_ms, elastic_repeats)
+            continue
+        if law == "plane_strain":   # laws 26 / 27 / 28 beside laws 0 / 1 / 2 of this process: seven lines
+            bench_plane_strain(a)
             continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
