@@ -168,3 +168,11 @@ def restrict_plane_strain_tangent(C66):
         raise ValueError(f"a 6-wide tangent block is (..., 6, 6), got shape {C66.shape}")
     idx = list(PLANE_STRAIN_IDX)
     return np.ascontiguousarray(C66[..., idx, :][..., :, idx])
+
+
+def plane_stress_axial_strain(E, nu, stress, epsp):
+    """The out-of-plane strain of a plane-stress state from the outputs of plane-stress J2 plasticity (``[xx, yy, sqrt(2) xy]``):
+    ``eps_zz = -nu / E (s_xx + s_yy) - (epsp_xx + epsp_yy)`` -- the elastic part from ``sig_zz = 0``, the plastic part from the
+    trace-free flow.  The field the reference's ``_plane_stress_elastoplasticity.py`` carries as an unknown of the global problem."""
+    stress, epsp = np.asarray(stress, dtype=np.float64).reshape(-1, 3), np.asarray(epsp, dtype=np.float64).reshape(-1, 3)
+    return -nu / E * (stress[:, 0] + stress[:, 1]) - (epsp[:, 0] + epsp[:, 1])

@@ -40,6 +40,7 @@
 #include "fs_single_crystal.hpp"
 #include "plane_stress.hpp"
 #include "plane_strain.hpp"
+#include "plane_stress_j2.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -443,6 +444,7 @@ static void launch_fs_single_crystal(const LaunchArgs& a);
 static void launch_ps_quadratic(const LaunchArgs& a);
 static void launch_ps_polygon(const LaunchArgs& a);
 template <int LAW> static void launch_plane_strain(const LaunchArgs& a);
+template <int HARD> static void launch_plane_stress_j2(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -937,12 +939,61 @@ constexpr LawDesc law_pe_j2_voce() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22 and 25 are not assigned and stay empty rows (law_known)
+// Plane-stress J2 plasticity with linear or Voce hardening (plane_stress_j2.hip): laws 1 / 2 under sig_zz = 0 in the three components
+// [xx, yy, sqrt(2) xy] of laws 23 / 24.  Strain in (24 B), p and the in-plane plastic strain read (32); stress (24), the 3x3 tangent
+// (72) and the state (32) out: 184 B/point.  The parameters are those of laws 1 / 2 and go through their build functions.  Strain and
+// stress are 3 wide: gradient_kind takes every law that is not 9 wide for a 6-wide strain, so the refusals of the fused and
+// displacement forms are what keeps a mesh gradient away from these rows.  No external state variable is declared (n_ext = 0):
+// dxm_set_external_state* answers with the library's sentence for every law without one
+constexpr LawDesc plane_stress_j2_law(int id, int n_params, const char* kernel) {
+  LawDesc d{};
+  d.id = id;
+  d.n_grad = d.n_flux = 3;
+  d.n_params = d.n_params_custom = n_params;
+  d.n_isv_fields = d.n_fields = 2;
+  state_field(d, 0, "p", 1, 0);
+  state_field(d, 1, "epsp", 3, 1);
+  d.n_slots = PSJ_NSLOTS;
+  d.alg_bytes = 184;
+  d.kernel = kernel;
+  d.blocks_per_cu = PSJ_BLOCKS_PER_CU;   // plane_stress_j2.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.set_refusal = d.launch_refusal = "the plane-stress tangent is a 3x3 block of 9 entries, not a symmetric 6x6: only DXM_TANGENT_FULL is "
+                                     "available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fields = "per-point parameter fields are not served for plane-stress J2 plasticity: the field kernels are the 6-wide "
+                "DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE, and the plane-stress constants are formed once per handle";
+  d.no_fused = d.no_displacement = "plane-stress J2 plasticity takes a 3-wide strain [xx, yy, sqrt(2) xy]: the mesh gradient kernels "
+                                   "evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
+                                   "fused displacement gradient are not served; pass the strain as an array";
+  d.no_frame = kNoFrame;
+  d.stock_only = "plane-stress J2 plasticity takes the stock hardening laws only (linear, Voce): it is served by the stock libdxmat, not "
+                 "by a custom-hardening build";
+  return d;
+}
+
+constexpr LawDesc law_ps_j2_linear() {
+  LawDesc d = plane_stress_j2_law(DXM_LAW_PS_J2_LINEAR, 4, "plane_stress_j2_kernel<1");
+  d.build = build_linear_hardening;
+  d.residency_kernel = DXM_STOCK_ONLY(plane_stress_j2_linear_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_plane_stress_j2<PSJ_LINEAR>);
+  return d;
+}
+
+constexpr LawDesc law_ps_j2_voce() {
+  LawDesc d = plane_stress_j2_law(DXM_LAW_PS_J2_VOCE, 5, "plane_stress_j2_kernel<2");
+  d.build = build_voce_hardening;
+  d.residency_kernel = DXM_STOCK_ONLY(plane_stress_j2_voce_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_plane_stress_j2<PSJ_VOCE>);
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25 and 29 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
     law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(), {}, law_fs_single_crystal(), {},
-    law_ps_quadratic(), law_ps_polygon(), {}, law_pe_elastic(), law_pe_j2_linear(), law_pe_j2_voce(),
+    law_ps_quadratic(), law_ps_polygon(), {}, law_pe_elastic(), law_pe_j2_linear(), law_pe_j2_voce(), {},
+    law_ps_j2_linear(), law_ps_j2_voce(),
 };
 
 constexpr bool rows_in_place() {
@@ -952,8 +1003,8 @@ constexpr bool rows_in_place() {
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
-                  !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel,
-              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22 and 25 are not assigned");
+                  !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel && !kLaws[29].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25 and 29 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -1943,6 +1994,26 @@ template <int LAW> static void launch_plane_strain(const LaunchArgs& a) {
   const bool state = LAW != PE_ELASTIC;
   plane_strain_launch(LAW, a.grid, a.st, m->prm, a.cnt, a.grad, state ? m->state[0] + a.off : nullptr, state ? m->state[1] + a.off : nullptr,
                       m->ld, a.flux, a.ct, m->d_stats + a.stats_off);
+}
+// the record of the handle's law is the 6-wide law's (build_linear_hardening / build_voce_hardening); the plane-stress constants are
+// formed here from E and nu, each entry a few individually rounded operations (plane_stress_j2.hpp: PsJ2Params)
+template <int HARD> static void launch_plane_stress_j2(const LaunchArgs& a) {
+#pragma clang fp contract(off)
+  dxm_material* m = a.m;
+  const double E = m->raw_params[0], nu = m->raw_params[1];
+  PsJ2Params q{};
+  q.law = m->prm;
+  const double c0 = E / (1.0 - nu * nu);
+  q.c11 = c0;
+  q.c12 = c0 * nu;
+  q.c33 = c0 * (1.0 - nu);
+  q.CA = E / (1.0 - nu);
+  q.CB = E / (1.0 + nu);
+  q.ka = q.CA / 3.0;
+  q.kmax = fmax(q.ka, q.CB);
+  q.kmin = fmin(q.ka, q.CB);
+  plane_stress_j2_launch(HARD, a.grid, a.st, q, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
+                         m->d_stats + a.stats_off);
 }
 #endif
 

@@ -131,6 +131,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_PS_QUADRATIC, _lib.LAW_PS_POLYGON):
             raise ValueError("the plane-stress tangent is a 3x3 block of 9 entries, not a symmetric 6x6: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for these laws; use 'full'")
+        if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_PS_J2_LINEAR, _lib.LAW_PS_J2_VOCE):
+            raise ValueError("the plane-stress tangent is a 3x3 block of 9 entries, not a symmetric 6x6: no packed tangent record "
+                             f"(tangent_layout={tangent_layout!r}) exists for plane-stress J2 plasticity; use 'full'")
         if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_PE_ELASTIC_ISO, _lib.LAW_PE_J2_LINEAR, _lib.LAW_PE_J2_VOCE):
             raise ValueError("the plane-strain tangent is a 4x4 block of 16 entries, not a symmetric 6x6: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists under hypothesis=\"plane_strain\"; use 'full'")

@@ -864,5 +864,38 @@ class PlaneStressPolygonYield(PlaneStressBehavior):
         return {"E": self.E, "nu": self.nu}
 
 
+class PlaneStressJ2(PlaneStressBehavior):
+    """Small-strain J2 plasticity with isotropic hardening under plane stress (``sig_zz = sig_xz = sig_yz = 0``): the law of
+    :class:`vonMisesIsotropicHardening` on ``[xx, yy, sqrt(2) xy]``, what the reference's
+    ``demos/jax/elastoplasticity/_plane_stress_elastoplasticity.py`` obtains with ``eps_zz`` as an extra unknown.  Internal state
+    variables ``p`` (1) and ``epsp`` (3, in-plane; ``epsp_zz = -(epsp_xx + epsp_yy)``); the tangent is the consistent 3x3 block.
+    Stock hardening laws only."""
+
+    def __init__(self, elasticity: LinearElasticIsotropic, yield_stress):
+        if not isinstance(yield_stress, (LinearHardening, VoceHardening)):
+            raise TypeError("plane-stress J2 plasticity is served with the stock hardening laws only: yield_stress must be a "
+                            "materials.LinearHardening or materials.VoceHardening, not a CustomHardening or a traced callable "
+                            f"(got {type(yield_stress).__name__})")
+        self.elasticity = elasticity
+        self.yield_stress = yield_stress
+        self.law = _lib.LAW_PS_J2_LINEAR if isinstance(yield_stress, LinearHardening) else _lib.LAW_PS_J2_VOCE
+
+    @property
+    def E(self):
+        return self.elasticity.E
+
+    @property
+    def nu(self):
+        return self.elasticity.nu
+
+    def params(self):
+        return _hardening_params(self.elasticity, self.yield_stress)
+
+    def flat_properties(self):
+        out = {"elasticity.E": self.elasticity.E, "elasticity.nu": self.elasticity.nu}
+        out.update(_hardening_properties(self.yield_stress))
+        return out
+
+
 def _isfinite(x):
     return x == x and abs(x) != float("inf")

@@ -7,7 +7,11 @@
     material.set_data_manager(N); sig, isv, Ct = material.integrate(eps); material.data_manager.update()
 
 Strain and stress are ``[xx, yy, sqrt(2) xy]``; ``gradients == {"Strain": 3}``, ``fluxes == {"Stress": 3}``, no internal state variable;
-the state dictionaries carry ``Strain`` and ``Stress`` like the reference's.  ``PlaneStressHosford`` is not served."""
+the state dictionaries carry ``Strain`` and ``Stress`` like the reference's.  ``PlaneStressHosford`` is not served.
+
+:class:`PlaneStressvonMisesHardening` is von Mises plasticity with linear or Voce hardening in the same three components
+(``csrc/plane_stress_j2.hip``), the law of ``demos/jax/elastoplasticity/_plane_stress_elastoplasticity.py`` without its extra
+unknown ``eps_zz``; its internal state variables are ``p`` (1) and ``epsp`` (3)."""
 from . import materials as _m
 from .hip_material import HIPMaterial
 
@@ -42,6 +46,21 @@ class PlaneStressvonMises(_PlaneStressMaterial):
     @property
     def sig0(self):
         return self.behavior.sig0
+
+
+class PlaneStressvonMisesHardening(_PlaneStressMaterial):
+    """von Mises plasticity with isotropic hardening in plane stress (``csrc/plane_stress_j2.hip``): the law of the reference's
+    ``demos/jax/elastoplasticity/_plane_stress_elastoplasticity.py`` without its extra unknown ``eps_zz``.  ``yield_stress`` is a
+    ``materials.LinearHardening`` or ``materials.VoceHardening``.  ``gradients == {"Strain": 3}``, ``fluxes == {"Stress": 3}``,
+    ``internal_state_variables == {"p": 1, "epsp": 3}``; the tangent is the consistent one.  The out-of-plane strain is
+    ``conventions.plane_stress_axial_strain(E, nu, stress, epsp)``."""
+
+    def __init__(self, E, nu, yield_stress, **kwargs):
+        super().__init__(_m.PlaneStressJ2(_m.LinearElasticIsotropic(E=E, nu=nu), yield_stress), **kwargs)
+
+    @property
+    def yield_stress(self):
+        return self.behavior.yield_stress
 
 
 class PlaneStressPolygon(_PlaneStressMaterial):

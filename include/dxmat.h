@@ -246,7 +246,29 @@ enum {
   DXM_LAW_PE_ELASTIC_ISO = 26,   /* id 25 is not assigned */
   DXM_LAW_PE_J2_LINEAR = 27,
   DXM_LAW_PE_J2_VOCE = 28,
-  DXM_LAW_COUNT = 29
+  /* (the table ended here, with DXM_LAW_COUNT = 29, before ids 30 and 31)
+   * Plane-stress J2 plasticity with isotropic hardening: the backward-Euler update of DXM_LAW_J2_LINEAR / DXM_LAW_J2_VOCE (Hooke,
+   * von Mises, associated flow, R(p) linear or Voce) under sig_zz = sig_xz = sig_yz = 0, what the reference's
+   * demos/jax/elastoplasticity/_plane_stress_elastoplasticity.py obtains with eps_zz as an extra unknown of the global problem.
+   * Gradient Strain (3) and flux Stress (3) are [xx, yy, sqrt(2) xy], the convention of DXM_LAW_PS_QUADRATIC.
+   * State: field 0 p (1), field 1 epsp (3, the in-plane plastic strain in the same components), 4 SoA slots; epsp_zz =
+   * -(epsp_xx + epsp_yy) is implied and not stored; eps_zz = -nu/E (s_xx + s_yy) - (epsp_xx + epsp_yy) follows from the outputs.
+   * The update is one scalar equation in the multiplier dg of epsp - epsp_n = dg P s, g(dg) = seq(dg) - R(p_n + 2/3 dg seq(dg)) = 0,
+   * solved by a bracketed Newton (DESIGN.md section "Plane-stress J2 plasticity") and ended on |g| <= max(rtol max(|sig0|, 2e-8 mu),
+   * rtol seq_trial) of dxm_set_newton; both hardening laws iterate.
+   * The tangent is one 3x3 block, 9 entries, row-major, exactly symmetric: the consistent (algorithmic) tangent at a yielded point,
+   * the plane-stress C = E/(1-nu^2) [[1, nu, 0], [nu, 1, 0], [0, 0, 1-nu]] at an elastic one.  DXM_TANGENT_FULL only.
+   * No per-point parameter fields, no material frame, no external state variable, none of the displacement forms and no fused
+   * displacement gradient (the mesh gradient kernels evaluate 6-wide strains or F), not served by a custom-hardening build.
+   * dxm_stats: n_plastic counts the yielded points; max_local_iters is the largest number of Newton steps a point took before its
+   * residual met the bound; n_not_converged counts the points that reached the cap of dxm_set_newton (they write their last
+   * iterate); n_nan counts points with a non-finite stress, state or tangent entry (a non-finite strain takes the elastic path and
+   * keeps its state bits).
+   * algorithmic_bytes_per_point = 184: strain 24 + state 32 in, stress 24 + tangent 72 + state 32 out.
+   * params = [E, nu, sig0, H] / [E, nu, sig0, sigu, b], validated as for DXM_LAW_J2_LINEAR / DXM_LAW_J2_VOCE */
+  DXM_LAW_PS_J2_LINEAR = 30,   /* id 29 is not assigned */
+  DXM_LAW_PS_J2_VOCE = 31,
+  DXM_LAW_COUNT = 32
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -37,6 +37,11 @@ process (run `--laws elastic heat_stationary ps_vonmises ps_rankine ps_l1rankine
 
 plane_strain: the three laws of the plane-strain hypothesis (ids 26 / 27 / 28, 4-wide) each next to its 6-wide law (0 / 1 / 2) of the
 same process on the same strains, embedded; one line per law and batch (bench_plane_strain).
+
+ps_j2: plane-stress J2 plasticity with linear and Voce hardening (ids 30 / 31, 184 B/point) on elastic, mixed and fully yielded batches,
+each next to two yardsticks of the same process on the same strains: law 23 (q = 3/2, consistent tangent, the same sig0; 168 B/point)
+and law 27 / 28 (plane strain, the strain embedded as [xx, yy, 0, sqrt(2) xy]; 272 B/point), both scaled to 184 B (bench_plane_stress_j2).
+--blocks-per-cu: the new kernels at each of these grid sizes as well.
 
 --param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
 (dxm_set_param_field; 1 = sig0, 2 = lambda and mu from an E field, 3 = both, 4 / 5 = H | sigu, b as well), in the same process and on
@@ -466,6 +471,84 @@ def bench_plane_strain(a):
         torch.cuda.empty_cache()
 
 
+def bench_plane_stress_j2(a):
+    """--laws ps_j2: laws 30 / 31 next to law 23 (q = 3/2, consistent tangent) and to law 27 / 28 of the same process on the same
+    strains.  One JSON line per law and batch: kernel ms of the three (median of three medians, interleaved), the fraction of 8 TB/s at
+    the counted bytes, and the ratio of the new kernel's time to each yardstick scaled by the byte ratio (184 / 168, 184 / 272).
+    Batches from the virgin state, trials log-uniform in 0.05 ... 0.95 (elastic), 0.2 ... 8 (mixed) and 1.01 ... 100 (yielded) times the
+    initial yield surface.  --blocks-per-cu: the new kernel at each of these grid sizes as well."""
+    import torch
+
+    import dolfinx_materials_amd.materials as jm
+    import plane_stress_j2_ref as pj
+    from dolfinx_materials_amd.jaxmat import JAXMaterial
+    from dolfinx_materials_amd.plane_stress import PlaneStressvonMises, PlaneStressvonMisesHardening
+    from helpers import to_device
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+
+    def timed(m, g, flux, ct):
+        for _ in range(a.warmup):
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+        for e0, e1 in ev:
+            e0.record()
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+            e1.record()
+        torch.cuda.synchronize()
+        return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+    el = jm.LinearElasticIsotropic(E=pj.E, nu=pj.NU)
+    for name, hard in (("linear", jm.LinearHardening(250.0, 5e3)), ("voce", jm.VoceHardening(350.0, 500.0, 1e3))):
+        mj = PlaneStressvonMisesHardening(pj.E, pj.NU, hard)
+        m23 = PlaneStressvonMises(pj.E, pj.NU, hard.sig0, shear_weight=1.5, tangent="consistent")
+        m27 = JAXMaterial(jm.vonMisesIsotropicHardening(el, hard, hypothesis="plane_strain"))
+        for m in (mj, m23, m27):
+            m.set_data_manager(n)
+        prm = mj.behavior.params()
+        f3, c3 = torch.empty((n, 3), dtype=torch.float64, device="cuda:0"), torch.empty((n, 9), dtype=torch.float64, device="cuda:0")
+        f4, c4 = torch.empty((n, 4), dtype=torch.float64, device="cuda:0"), torch.empty((n, 16), dtype=torch.float64, device="cuda:0")
+        for tag, lo, hi in (("elastic", 0.05, 0.95), ("mixed", 0.2, 8.0), ("yielded", 1.01, 100.0)):
+            e3 = pj.random_trials(prm, n, seed=2029, lo=lo, hi=hi)
+            e4 = np.zeros((n, 4))
+            e4[:, :2], e4[:, 3] = e3[:, :2], e3[:, 2]
+            g3, g4 = to_device(e3), to_device(e4)
+            del e3, e4
+            tj, t23, t27 = [], [], []
+            for _ in range(3):          # interleaved: the three kernels see the same drift of the machine
+                t23.append(timed(m23, g3, f3, c3))
+                t27.append(timed(m27, g4, f4, c4))
+                tj.append(timed(mj, g3, f3, c3))
+            _, sj = mj.stats()
+            _, s23 = m23.stats()
+            ms, ms23, ms27 = float(np.median(tj)), float(np.median(t23)), float(np.median(t27))
+            ab = mj.algorithmic_bytes_per_point
+            r = {"law": f"ps_j2:{name}+{tag}", "points": n, "kernel": mj.kernel_name, "kernel_ms_repeats": [round(x, 4) for x in tj],
+                 "kernel_ms": round(ms, 4), "algorithmic_bytes_per_point": ab, "frac_of_8TBs": round(ab * n / ms / 1e6 / 8000, 4),
+                 "law23_ms_repeats": [round(x, 4) for x in t23], "law23_ms": round(ms23, 4), "law23_scaled_ms": round(ms23 * ab / 168, 4),
+                 "ratio_to_scaled_law23": round(ms / (ms23 * ab / 168), 3),
+                 "plane_strain_kernel": m27.kernel_name, "plane_strain_ms_repeats": [round(x, 4) for x in t27], "plane_strain_ms": round(ms27, 4),
+                 "plane_strain_scaled_ms": round(ms27 * ab / 272, 4), "ratio_to_scaled_plane_strain": round(ms / (ms27 * ab / 272), 3),
+                 "plastic_fraction": round(sj["n_plastic"] / n, 4), "law23_plastic_fraction": round(s23["n_plastic"] / n, 4),
+                 "max_local_iters": sj["max_local_iters"], "law23_max_local_iters": s23["max_local_iters"],
+                 "not_converged": sj["n_not_converged"], "nan": sj["n_nan"]}
+            if a.blocks_per_cu:
+                sweep = {}
+                for b in a.blocks_per_cu:
+                    mj.set_option("blocks_per_cu", b)
+                    sweep[b] = round(timed(mj, g3, f3, c3), 4)
+                mj.set_option("blocks_per_cu", 32)      # the shipped grid again (plane_stress_j2.hpp)
+                r["kernel_ms_by_blocks_per_cu"] = sweep
+            print(json.dumps(r), flush=True)
+            del g3, g4
+        for m in (mj, m23, m27):
+            m.close()
+        del mj, m23, m27, f3, c3, f4, c4
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -475,13 +558,13 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0, help="also time the plain-C oracle on this many points")
     ap.add_argument("--sym", action="store_true", help="symmetric-packed tangent (small-strain laws)")
     ap.add_argument("--blocks-per-cu", type=int, nargs="+", default=None,
-                    help="ramberg_osgood, plane_strain: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
+                    help="ramberg_osgood, plane_strain, ps_j2: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
                          "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws or
-                         any(law.startswith("ps_") for law in a.laws) or "plane_strain" in a.laws):
+                         any(law.startswith("ps_") for law in a.laws) or "plane_strain" in a.laws):   # (ps_j2 among them)
         ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal, heat-transfer or logarithmic-strain law")
     import torch
 
@@ -512,6 +595,9 @@ def main():
             continue
         if law == "plane_strain":   # laws 26 / 27 / 28 beside laws 0 / 1 / 2 of this process: seven lines
             bench_plane_strain(a)
+            continue
+        if law == "ps_j2":   # laws 30 / 31 beside law 23 and laws 27 / 28 of this process: six lines
+            bench_plane_stress_j2(a)
             continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
