@@ -9,14 +9,21 @@
 // seq^2 = 3/2 s^T P s = 1/2 sa^2 + 3/2 sb^2 + 3/2 sc^2.  With the multiplier dg of  eps_p - eps_p,n = dg P s  (dg = 3/2 dp / seq):
 //   t = C (eps - eps_p,n),   s_i = t_i / (1 + dg k_i),  k = (CA/3, CB, CB),   p = p_n + 2/3 dg seq(dg)
 //   g(dg) = seq(dg) - R(p_n + 2/3 dg seq(dg)) = 0
-// g is decreasing, and convex for H >= 0 and for Voce: one root.  Even linear hardening has no closed form, so both laws iterate:
+// For hardening parameters (H >= 0; Voce with sigu >= sig0) g is decreasing and convex: one root.  Softening parameters (H < 0,
+// sigu < sig0), which the build functions accept, lose both: only g(0) > 0 >= g(hi) below holds for them, and the bracket finds a
+// root between.  Even linear hardening has no closed form, so both laws iterate:
 //   start: the larger of two lower bounds of the root.  With kmax = max k_i, seq(dg) >= seq_tr / (1 + dg kmax) and seq(dg) <= seq_tr;
 //     R concave gives R(p) <= R_n + R'_n (p - p_n), so g >= seq_tr / (1 + dg kmax) - R_n - c dg with c = 2/3 max(R'_n, 0) seq_tr, whose
 //     root is 2 f / (B + sqrt(B^2 + 4 c kmax f)), B = c + R_n kmax, f = seq_tr - R_n (H = 0: the start of plane_stress.hip); Voce also
 //     has R <= max(sigu, R_n) = cap: dg >= (seq_tr / cap - 1) / kmax.
-//   safeguard: the root is bracketed in [lo, hi], lo = 0 (g(0) = f > 0), hi = (seq_tr / R_n - 1) / kmin (seq(hi) <= R_n <= R); every
-//     iterate moves the end of its sign; a Newton step that leaves (lo, hi) is replaced by the midpoint.  From a lower bound of a
-//     convex decreasing g Newton is monotone and the safeguard idle.
+//   safeguard: a root is bracketed in [lo, hi], lo = 0 (g(0) = f > 0), hi = (seq_tr / floor - 1) / kmin with floor a positive lower
+//     bound of R over the step: seq(hi) <= seq_tr / (1 + hi kmin) = floor <= R, so g(hi) <= 0.  Hardening: floor = R_n.  Voce:
+//     floor = min(R_n, sigu) (R runs monotonically from R_n towards sigu).  Linear, H < 0: p - p_n = 2/3 dg seq(dg) and
+//     dg s_i = t_i dg / (1 + dg k_i) < t_i / k_i, so p - p_n < 2/3 sqrt(1/2 (ta/ka)^2 + 3/2 ((tb/CB)^2 + (tc/CB)^2)) = dp_max and
+//     floor = R_n + H dp_max.  A floor that is not positive gives no bracket: the point is counted in n_not_converged at its first
+//     residual and writes the start (the 6-wide body does the same for rho <= 0).  Every iterate moves the end of its sign; a
+//     Newton step that leaves (lo, hi) is replaced by the midpoint.  From a lower bound of a convex decreasing g Newton is
+//     monotone and the safeguard idle; under softening it works.
 //   end: |g| <= max(tol, rtol seq_tr), the tolerance of the 6-wide laws (dxm_set_newton); the step computed from that last residual
 //     is still taken, unsafeguarded.  A point at the cap is counted and writes its last iterate.
 // eps_p = eps - C^-1 s at a yielded point.  Tangent, with A = diag(C_i / (1 + dg k_i)), n = 3/2 P s, theta = 1 - 2/3 R' dg:
@@ -122,7 +129,19 @@ plane_stress_j2_kernel(const PsJ2Params prm, const int64_t n, const double* __re
         }
         if (!(dg >= 0.0 && dg <= 1.7976931348623157e308)) dg = 0.0;
       }
-      double lo = 0.0, hi = (seqt / Rn - 1.0) / prm.kmin;
+      // the lower bound of R over the step (header): R_n itself unless the parameters soften
+      // and without a positive bound there is no bracket: that point is counted at its first residual and writes the start
+      double floor_R = Rn;
+      int cap = prm.law.maxit;
+      if constexpr (HARD == PSJ_VOCE) {
+        floor_R = __builtin_fmin(Rn, prm.law.h1);
+        if (!(floor_R > 0.0)) cap = 0;
+      } else if (prm.law.h1 < 0.0) {   // one scalar compare on the kernel's parameters: an H >= 0 launch executes none of this
+        const double ua = ta / ka, ub = tb / CB, uc = tc / CB;
+        floor_R = Rn + prm.law.h1 * (TWO3 * __builtin_sqrt(0.5 * (ua * ua) + 1.5 * (ub * ub + uc * uc)));
+        if (!(floor_R > 0.0)) cap = 0;
+      }
+      double lo = 0.0, hi = (seqt / floor_R - 1.0) / prm.kmin;
       double da, db, S, seq, pp;
       int it = 0;
       for (;;) {
@@ -134,7 +153,7 @@ plane_stress_j2_kernel(const PsJ2Params prm, const int64_t n, const double* __re
         pp = p_n + (TWO3 * dg) * seq;
         const double g = seq - hardening_R<HARD>(prm.law, pp);
         const bool conv = __builtin_fabs(g) <= tolp;
-        if (!conv && it >= prm.law.maxit) { ++c_notconv; break; }
+        if (!conv && it >= cap) { ++c_notconv; break; }
         // seq' = -(sum q_i k_i d_i) / seq,  p' = 2/3 (seq + dg seq'),  g' = seq' - R' p'
         const double dseq = -((qa * (ka * da) + (qb + qc) * (CB * db)) / seq);
         const double gp = dseq - (TWO3 * hardening_dR<HARD>(prm.law, pp)) * (seq + dg * dseq);

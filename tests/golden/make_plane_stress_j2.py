@@ -55,8 +55,12 @@ def radial_return(law, prm, eps6, epsp6, p_n):
     if law == LINEAR:
         dp = f / (mp.mpf(prm[3]) + 3 * mu)
     else:
-        r = lambda x: seq - 3 * mu * x - R(p_n + x)    # noqa: E731  decreasing, r(0) = f > 0, r(f / (3 mu)) <= 0 for a hardening R
-        dp = mp.findroot(r, (mp.mpf(0), f / (3 * mu)), solver="illinois", tol=mp.mpf(10) ** -47, maxsteps=400, verify=False)
+        r = lambda x: seq - 3 * mu * x - R(p_n + x)    # noqa: E731  r(0) = f > 0, r(f / (3 mu)) <= 0 for a hardening R
+        hi = f / (3 * mu)
+        while r(hi) > 0:                               # a softening R: the root lies beyond, the end moves out until r is negative
+            hi *= 2
+        assert r(mp.mpf(0)) > 0 >= r(hi)
+        dp = mp.findroot(r, (mp.mpf(0), hi), solver="illinois", tol=mp.mpf(10) ** -47, maxsteps=400, verify=False)
         assert abs(r(dp)) <= mp.mpf(10) ** -44 * seq
     n = [mp.mpf(3) / 2 * s / seq for s in se]
     e = [e[k] - dp * n[k] for k in range(6)]

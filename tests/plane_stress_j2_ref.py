@@ -85,7 +85,15 @@ def update(law, eps, epsp_n, p_n, prm, maxit=MAXIT, rtol=RTOL):
                 cap = np.maximum(prm[3], rn)
                 dg = np.maximum(dg, (sq / cap - 1.0) / kmax)
             dg = np.where((dg >= 0.0) & (dg <= DBL_MAX), dg, 0.0)
-            lo, hi = np.zeros(i.size), (sq / rn - 1.0) / kmin
+            # the lower bound of R over the step; no positive bound: no bracket, the point is counted at its first residual
+            floor = rn
+            if law == J2_VOCE:
+                floor = np.minimum(rn, prm[3])
+            elif prm[3] < 0.0:
+                ua, ub, uc = ta_ / ka, tb_ / CB, tc_ / CB
+                floor = rn + prm[3] * (TWO3 * np.sqrt(0.5 * (ua * ua) + 1.5 * (ub * ub + uc * uc)))
+            cap = np.where(floor > 0.0, maxit, 0)
+            lo, hi = np.zeros(i.size), (sq / floor - 1.0) / kmin
             m = i.size
             da, db, S, seq, pp = np.ones(m), np.ones(m), np.zeros(m), np.zeros(m), pn.copy()
             xa, xb, xc = ta_.copy(), tb_.copy(), tc_.copy()
@@ -102,7 +110,7 @@ def update(law, eps, epsp_n, p_n, prm, maxit=MAXIT, rtol=RTOL):
                 pp_ = pn[j] + (TWO3 * g_) * sq_
                 g = sq_ - R(pp_)
                 conv = np.abs(g) <= tolp[j]
-                stop = ~conv & (it[j] >= maxit)
+                stop = ~conv & (it[j] >= cap[j])
                 dseq = -((qa * (ka * a_) + (qb + qc) * (CB * b_)) / sq_)
                 gp = dseq - (TWO3 * dR(pp_)) * (sq_ + g_ * dseq)
                 dgn = g_ - g / gp

@@ -18,7 +18,7 @@ import check_device_asm as chk  # noqa: E402
 needs_hipcc = pytest.mark.skipif(shutil.which(chk.HIPCC) is None, reason="needs the HIP compiler")
 # per wave the 64 x 3 strain / stress staging and the 64 x 6 tangent records; per workgroup the stats words
 LDS_BYTES = 4 * 64 * (3 + 6) * 8 + 4 * 4 * 8
-VGPRS = {"1": 114, "2": 141}      # linear, Voce: what DESIGN.md records
+VGPRS = {"1": 112, "2": 141}      # linear, Voce: what DESIGN.md records
 
 
 @needs_hipcc
