@@ -26,6 +26,7 @@ LAW_FS_SINGLE_CRYSTAL_FCC = 21   # (20 is not assigned)
 LAW_PS_QUADRATIC, LAW_PS_POLYGON = 23, 24   # (22 is not assigned)
 LAW_PE_ELASTIC_ISO, LAW_PE_J2_LINEAR, LAW_PE_J2_VOCE = 26, 27, 28   # plane strain (25 is not assigned)
 LAW_PS_J2_LINEAR, LAW_PS_J2_VOCE = 30, 31   # plane-stress J2 with hardening (29 is not assigned)
+LAW_PS_HOSFORD = 33   # plane-stress Hosford (32 is not assigned)
 DXM_MAX_EXTERNAL_STATE, DXM_MAX_TANGENT_BLOCKS = 2, 4
 S0, S1 = 0, 1
 

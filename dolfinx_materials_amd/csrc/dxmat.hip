@@ -41,6 +41,7 @@
 #include "plane_stress.hpp"
 #include "plane_strain.hpp"
 #include "plane_stress_j2.hpp"
+#include "plane_stress_hosford.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -428,6 +429,28 @@ static int build_ps_polygon(const double* p, LawParams&) {
   return 0;
 }
 
+// [E, nu, sig0, a, tangent] (the reference's demos/cvxpy/cvxpy_materials.py:96-110); what the kernel reads is formed by the launcher
+// (plane_stress_hosford.hpp: PshParams).  The exponent's range is PSH_A_MIN .. PSH_A_MAX there
+static int build_ps_hosford(const double* p, LawParams& q) {
+  static const char* const names[5] = {"E", "nu", "sig0", "a", "tangent"};
+  for (int k = 0; k < 5; ++k)
+    if (!std::isfinite(p[k])) return fail(-1, "plane-stress Hosford plasticity: %s must be finite, got %g", names[k], p[k]);
+  if (!(p[0] > 0.0)) return fail(-1, "plane-stress Hosford plasticity: E must be > 0, got %g", p[0]);
+  if (!(p[1] > -1.0 && p[1] < 1.0)) return fail(-1, "plane-stress Hosford plasticity: nu must lie in (-1, 1), got %g", p[1]);
+  if (!(p[2] > 0.0)) return fail(-1, "plane-stress Hosford plasticity: sig0 must be > 0, got %g", p[2]);
+  if (!(p[3] >= PSH_A_MIN))
+    return fail(-1, "plane-stress Hosford plasticity: the exponent a must be >= 2 (below 2 the Hessian of the yield function is unbounded "
+                    "on the axes), got %g", p[3]);
+  if (!(p[3] <= PSH_A_MAX))
+    return fail(-1, "plane-stress Hosford plasticity: the exponent a must be <= 100 (the largest exponent at which the accuracy was "
+                    "measured), got %g", p[3]);
+  if (!(p[4] == 0.0 || p[4] == 1.0))
+    return fail(-1, "plane-stress Hosford plasticity: tangent must be 0 (the elastic C) or 1 (the algorithmic tangent), got %g", p[4]);
+  q.sig0 = p[2];
+  q.tol = fmax(q.rtol, 0x1p-49);   // on the last step of the angle, in radians
+  return 0;
+}
+
 // ---- launchers (defined in the launch section, where the handle is complete) ----
 template <int LAW> static void launch_small_strain(const LaunchArgs& a);
 static void launch_fefp_voce(const LaunchArgs& a);
@@ -445,6 +468,7 @@ static void launch_ps_quadratic(const LaunchArgs& a);
 static void launch_ps_polygon(const LaunchArgs& a);
 template <int LAW> static void launch_plane_strain(const LaunchArgs& a);
 template <int HARD> static void launch_plane_stress_j2(const LaunchArgs& a);
+static void launch_ps_hosford(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -987,13 +1011,43 @@ constexpr LawDesc law_ps_j2_voce() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25 and 29 are not assigned and stay empty rows (law_known)
+// Plane-stress Hosford plasticity (plane_stress_hosford.hip): the streams of laws 23 / 24, 168 B/point, and their hidden 3-wide
+// plastic strain.  No external state variable is declared (n_ext = 0): dxm_set_external_state* answers with the library's sentence
+constexpr LawDesc law_ps_hosford() {
+  LawDesc d{};
+  d.id = DXM_LAW_PS_HOSFORD;
+  d.n_grad = d.n_flux = 3;
+  d.n_params = d.n_params_custom = 5;
+  d.n_isv_fields = 0;
+  d.n_fields = 1;   // field 0 is hidden state: what the update is driven by (plane_stress_hosford.hpp)
+  state_field(d, 0, "PlasticStrain", 3, 0);
+  d.n_slots = PSH_NSLOTS;
+  d.alg_bytes = 168;
+  d.kernel = "plane_stress_hosford_kernel<0";
+  d.blocks_per_cu = PSH_BLOCKS_PER_CU;   // plane_stress_hosford.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.build = build_ps_hosford;
+  d.residency_kernel = DXM_STOCK_ONLY(plane_stress_hosford_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_ps_hosford);
+  d.no_fields = "per-point parameter fields are not served for plane-stress Hosford plasticity: its constants are formed once per handle";
+  d.stock_only = "plane-stress Hosford plasticity is perfectly plastic, it has no hardening law: it is served by the stock libdxmat, not by "
+                 "a custom-hardening build";
+  d.set_refusal = d.launch_refusal = "the plane-stress Hosford tangent is a 3x3 block of 9 entries, not a symmetric 6x6: only "
+                                     "DXM_TANGENT_FULL is available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fused = d.no_displacement = "plane-stress Hosford plasticity takes a 3-wide strain [xx, yy, sqrt(2) xy]: the mesh gradient kernels "
+                                   "evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the fused "
+                                   "displacement gradient are not served; pass the strain as an array";
+  d.no_frame = "plane-stress Hosford plasticity is a function of the principal stresses: a material frame changes nothing in its update";
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29 and 32 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
     law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(), {}, law_fs_single_crystal(), {},
     law_ps_quadratic(), law_ps_polygon(), {}, law_pe_elastic(), law_pe_j2_linear(), law_pe_j2_voce(), {},
-    law_ps_j2_linear(), law_ps_j2_voce(),
+    law_ps_j2_linear(), law_ps_j2_voce(), {}, law_ps_hosford(),
 };
 
 constexpr bool rows_in_place() {
@@ -1003,8 +1057,9 @@ constexpr bool rows_in_place() {
 }
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
-                  !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel && !kLaws[29].kernel,
-              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25 and 29 are not assigned");
+                  !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel && !kLaws[29].kernel &&
+                  !kLaws[32].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29 and 32 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -2014,6 +2069,35 @@ template <int HARD> static void launch_plane_stress_j2(const LaunchArgs& a) {
   q.kmin = fmin(q.ka, q.CB);
   plane_stress_j2_launch(HARD, a.grid, a.st, q, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
                          m->d_stats + a.stats_off);
+}
+// what the kernel reads (plane_stress_hosford.hpp: PshParams): each entry a parameter or a few individually rounded operations
+static void launch_ps_hosford(const LaunchArgs& a) {
+#pragma clang fp contract(off)
+  dxm_material* m = a.m;
+  const double* p = m->raw_params.data();   // [E, nu, sig0, a, tangent] (build_ps_hosford)
+  const double E = p[0], nu = p[1];
+  PshParams q{};
+  const double c0 = E / (1.0 - nu * nu);
+  q.p[PSH_C11] = c0;
+  q.p[PSH_C12] = c0 * nu;
+  q.p[PSH_C33] = c0 * (1.0 - nu);
+  q.p[PSH_E] = E;
+  q.p[PSH_NU] = nu;
+  q.p[PSH_SQA] = sqrt(E / (1.0 - nu));
+  q.p[PSH_SQB] = sqrt(E / (1.0 + nu));
+  q.p[PSH_SIG0] = p[2];
+  q.p[PSH_A] = p[3];
+  q.p[PSH_AM1] = p[3] - 1.0;
+  q.p[PSH_AM2] = p[3] - 2.0;
+  q.p[PSH_INVA] = 1.0 / p[3];
+  q.p[PSH_TOL] = m->prm.tol;
+  q.p[PSH_CB] = E / (1.0 + nu);
+  constexpr double eps4 = 4.0 * 2.220446049250313e-16;
+  q.p[PSH_KLO] = pow(0.5, q.p[PSH_INVA]) * (1.0 - eps4);
+  q.p[PSH_KHI] = pow(1.5, q.p[PSH_INVA]) * (1.0 + eps4);
+  q.maxit = m->prm.maxit;
+  plane_stress_hosford_launch(p[4] != 0.0, a.grid, a.st, q, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
+                              m->d_stats + a.stats_off);
 }
 #endif
 

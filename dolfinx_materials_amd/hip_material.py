@@ -134,6 +134,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_PS_J2_LINEAR, _lib.LAW_PS_J2_VOCE):
             raise ValueError("the plane-stress tangent is a 3x3 block of 9 entries, not a symmetric 6x6: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for plane-stress J2 plasticity; use 'full'")
+        if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_PS_HOSFORD:
+            raise ValueError("the plane-stress tangent is a 3x3 block of 9 entries, not a symmetric 6x6: no packed tangent record "
+                             f"(tangent_layout={tangent_layout!r}) exists for plane-stress Hosford plasticity; use 'full'")
         if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_PE_ELASTIC_ISO, _lib.LAW_PE_J2_LINEAR, _lib.LAW_PE_J2_VOCE):
             raise ValueError("the plane-strain tangent is a 4x4 block of 16 entries, not a symmetric 6x6: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists under hypothesis=\"plane_strain\"; use 'full'")
@@ -333,7 +336,7 @@ class HIPMaterial:
     def _has_plane_stress_state(self):
         """The plane-stress return mappings: the kernel is handed the total strain and its state is the plastic strain (hidden
         field 0, ``eps - C^-1 sigma``), rebuilt from (Strain_n, Stress_n) when either is set."""
-        return self.behavior.law in (_lib.LAW_PS_QUADRATIC, _lib.LAW_PS_POLYGON)
+        return self.behavior.law in (_lib.LAW_PS_QUADRATIC, _lib.LAW_PS_POLYGON, _lib.LAW_PS_HOSFORD)
 
     @property
     def variables(self):

@@ -864,6 +864,39 @@ class PlaneStressPolygonYield(PlaneStressBehavior):
         return {"E": self.E, "nu": self.nu}
 
 
+class PlaneStressHosfordYield(PlaneStressBehavior):
+    """Closest-point projection, in the elastic energy norm, of the trial stress onto ``{phi(s) <= sig0}`` with the Hosford function
+    ``phi = ((|s_I|^a + |s_II|^a + |s_I - s_II|^a) / 2)^(1/a)`` of the principal stresses (the reference's ``PlaneStressHosford``,
+    ``cvxpy_materials.py:96-110``).  ``2 <= a <= 100``, not necessarily an integer; ``a = 2`` is von Mises.  ``tangent`` 0 hands
+    back the elastic ``C`` like the reference, 1 the algorithmic tangent of the yielded points."""
+
+    law = _lib.LAW_PS_HOSFORD
+    A_MIN, A_MAX = 2.0, 100.0
+
+    def __init__(self, E, nu, sig0, a, tangent=0):
+        self.E, self.nu, self.sig0, self.a = float(E), float(nu), float(sig0), float(a)
+        self.tangent = int(tangent)
+        self._check_elastic()
+        if not (_isfinite(self.sig0) and self.sig0 > 0.0):
+            raise ValueError(f"{type(self).__name__}: sig0 must be finite and > 0, got {sig0}")
+        if not _isfinite(self.a):
+            raise ValueError(f"{type(self).__name__}: the exponent a must be finite, got {a}")
+        if not self.a >= self.A_MIN:
+            raise ValueError(f"{type(self).__name__}: the exponent a must be >= 2 (below 2 the Hessian of the yield function is "
+                             f"unbounded on the axes), got {a}")
+        if not self.a <= self.A_MAX:
+            raise ValueError(f"{type(self).__name__}: the exponent a must be <= 100 (the largest exponent at which the accuracy was "
+                             f"measured), got {a}")
+        if tangent not in (0, 1):
+            raise ValueError(f"{type(self).__name__}: tangent must be 0 (elastic) or 1 (algorithmic), got {tangent!r}")
+
+    def params(self):
+        return [self.E, self.nu, self.sig0, self.a, float(self.tangent)]
+
+    def flat_properties(self):
+        return {"E": self.E, "nu": self.nu, "sig0": self.sig0, "a": self.a}
+
+
 class PlaneStressJ2(PlaneStressBehavior):
     """Small-strain J2 plasticity with isotropic hardening under plane stress (``sig_zz = sig_xz = sig_yz = 0``): the law of
     :class:`vonMisesIsotropicHardening` on ``[xx, yy, sqrt(2) xy]``, what the reference's

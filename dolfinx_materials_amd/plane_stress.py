@@ -1,13 +1,14 @@
 """The plane-stress laws of the reference's ``demos/cvxpy/cvxpy_materials.py`` under their own names and constructor signatures, as
 :class:`HIPMaterial` s: where the demo solves one conic program per Gauss point and call, these run one fused kernel over the batch
-(``csrc/plane_stress.hip``: a scalar Newton on one multiplier for the quadratic set, a closed form for the polygonal ones).
+(``csrc/plane_stress.hip``: a scalar Newton on one multiplier for the quadratic set, a closed form for the polygonal ones;
+``csrc/plane_stress_hosford.hip``: one bracketed root in a polar angle for the Hosford set, at any exponent from 2 to 100).
 
-    from dolfinx_materials_amd.plane_stress import PlaneStressvonMises, Rankine, L1Rankine
+    from dolfinx_materials_amd.plane_stress import PlaneStressvonMises, Rankine, L1Rankine, PlaneStressHosford
     material = Rankine(E=70e3, nu=0.2, fc=30.0, ft=10.0)       # demos/cvxpy/cvxpy_return_mapping.py
     material.set_data_manager(N); sig, isv, Ct = material.integrate(eps); material.data_manager.update()
 
 Strain and stress are ``[xx, yy, sqrt(2) xy]``; ``gradients == {"Strain": 3}``, ``fluxes == {"Stress": 3}``, no internal state variable;
-the state dictionaries carry ``Strain`` and ``Stress`` like the reference's.  ``PlaneStressHosford`` is not served.
+the state dictionaries carry ``Strain`` and ``Stress`` like the reference's.  ``PlaneStressHosford(E=E, nu=nu, sig0=sig0, a=10)`` is the demo's fourth law (``cvxpy_return_mapping.py:179-207``).
 
 :class:`PlaneStressvonMisesHardening` is von Mises plasticity with linear or Voce hardening in the same three components
 (``csrc/plane_stress_j2.hip``), the law of ``demos/jax/elastoplasticity/_plane_stress_elastoplasticity.py`` without its extra
@@ -46,6 +47,25 @@ class PlaneStressvonMises(_PlaneStressMaterial):
     @property
     def sig0(self):
         return self.behavior.sig0
+
+
+class PlaneStressHosford(_PlaneStressMaterial):
+    """``cvxpy_materials.py:96-110``: ``(|sigma_I|^a + |sigma_II|^a + |sigma_I - sigma_II|^a) / 2 <= sig0^a`` on the principal stresses,
+    ``2 <= a <= 100``.  ``tangent="elastic"`` hands back ``C`` as the reference does, ``"consistent"`` the algorithmic tangent of the
+    yielded points."""
+
+    def __init__(self, E, nu, sig0, a, tangent="elastic", **kwargs):
+        if tangent not in ("elastic", "consistent"):
+            raise ValueError(f"PlaneStressHosford: tangent must be 'elastic' or 'consistent', got {tangent!r}")
+        super().__init__(_m.PlaneStressHosfordYield(E, nu, sig0, a, tangent=int(tangent == "consistent")), **kwargs)
+
+    @property
+    def sig0(self):
+        return self.behavior.sig0
+
+    @property
+    def a(self):
+        return self.behavior.a
 
 
 class PlaneStressvonMisesHardening(_PlaneStressMaterial):

@@ -268,7 +268,26 @@ enum {
    * params = [E, nu, sig0, H] / [E, nu, sig0, sigu, b], validated as for DXM_LAW_J2_LINEAR / DXM_LAW_J2_VOCE */
   DXM_LAW_PS_J2_LINEAR = 30,   /* id 29 is not assigned */
   DXM_LAW_PS_J2_VOCE = 31,
-  DXM_LAW_COUNT = 32
+  /* (the table ended here, with DXM_LAW_COUNT = 32, before id 33)
+   * Plane-stress Hosford plasticity, perfectly plastic (the reference's PlaneStressHosford, demos/cvxpy/cvxpy_materials.py:96-110,
+   * without the conic program).  Conventions, update, hidden state field PlasticStrain (3) and restrictions as for
+   * DXM_LAW_PS_QUADRATIC, with the yield set
+   *   K = {phi(t) <= sig0},   phi(t) = ((|t_I|^a + |t_II|^a + |t_I - t_II|^a) / 2)^(1/a),   t_I, t_II the principal values.
+   * a = 2 is plane-stress von Mises (DXM_LAW_PS_QUADRATIC with q = 3/2).  Trial and answer are coaxial; in the scaled principal
+   * plane the projection is ONE bracketed scalar root in the polar angle th of the boundary's first-quadrant arc, solved by Newton
+   * inside the bracket [0, pi/2] with a bisection safeguard (DESIGN.md section "Plane-stress Hosford plasticity"), ended when the
+   * step just taken is at most max(rtol, 2^-49) radians (dxm_set_newton).  Every iterate lies on the yield surface by construction.
+   * tangent = 0 writes C at every point (the reference's); tangent = 1 writes the algorithmic tangent of a yielded point (exactly
+   * symmetric), and C at an elastic one.  9 entries, row-major.  DXM_TANGENT_FULL only; no material frame, no per-point parameter
+   * fields, no external state variable, none of the displacement forms, no fused displacement gradient, not served by a
+   * custom-hardening build.
+   * dxm_stats: n_plastic counts the projected points; max_local_iters is the largest number of steps of the angle a point took;
+   * n_not_converged counts the points that reached the cap of dxm_set_newton (they write their last iterate, which is admissible);
+   * n_nan counts points with a non-finite stress, state or (tangent = 1) tangent entry (a non-finite trial is not projected).
+   * algorithmic_bytes_per_point = 168: strain 24 + state 24 in, stress 24 + tangent 72 + state 24 out.
+   * params = [E, nu, sig0, a, tangent], all finite, E > 0, -1 < nu < 1, sig0 > 0, 2 <= a <= 100, tangent 0 or 1 */
+  DXM_LAW_PS_HOSFORD = 33,   /* id 32 is not assigned */
+  DXM_LAW_COUNT = 34
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2 ps_hosford]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -41,6 +41,9 @@ same process on the same strains, embedded; one line per law and batch (bench_pl
 ps_j2: plane-stress J2 plasticity with linear and Voce hardening (ids 30 / 31, 184 B/point) on elastic, mixed and fully yielded batches,
 each next to two yardsticks of the same process on the same strains: law 23 (q = 3/2, consistent tangent, the same sig0; 168 B/point)
 and law 27 / 28 (plane strain, the strain embedded as [xx, yy, 0, sqrt(2) xy]; 272 B/point), both scaled to 184 B (bench_plane_stress_j2).
+ps_hosford: plane-stress Hosford plasticity (id 33, 168 B/point) at the cvxpy demo's parameters and a = 10, both tangent modes, on wholly
+elastic, mixed and fully yielded batches, next to ps_vonmises (law 23, the same bytes) of the same process on the same strains
+(bench_plane_stress_hosford).
 --blocks-per-cu: the new kernels at each of these grid sizes as well.
 
 --param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
@@ -549,6 +552,76 @@ def bench_plane_stress_j2(a):
         torch.cuda.empty_cache()
 
 
+def bench_plane_stress_hosford(a):
+    """--laws ps_hosford: law 33 at the demo's E = 70e3, nu = 0.2, sig0 = 30 and a = 10 next to law 23 (the demo's PlaneStressvonMises,
+    the same tangent mode) of the same process on the same strains; both move 168 B/point.  One JSON line per tangent mode and batch:
+    kernel ms of both (median of three medians, interleaved), the fraction of 8 TB/s at the counted bytes, their ratio.  Batches from the
+    virgin state, trials log-uniform in 0.05 ... 0.95 (elastic), 0.2 ... 8 (mixed) and 1.01 ... 100 (yielded) times the Hosford surface.
+    --blocks-per-cu: the new kernel at each of these grid sizes as well."""
+    import torch
+
+    import plane_stress_hosford_ref as psh
+    from dolfinx_materials_amd.plane_stress import PlaneStressHosford, PlaneStressvonMises
+    from helpers import to_device
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+    E, nu, sig0, expo = 70e3, 0.2, 30.0, 10.0
+
+    def timed(m, g, flux, ct):
+        for _ in range(a.warmup):
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+        for e0, e1 in ev:
+            e0.record()
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+            e1.record()
+        torch.cuda.synchronize()
+        return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+    f3, c3 = torch.empty((n, 3), dtype=torch.float64, device="cuda:0"), torch.empty((n, 9), dtype=torch.float64, device="cuda:0")
+    for tangent in ("elastic", "consistent"):
+        mh = PlaneStressHosford(E=E, nu=nu, sig0=sig0, a=expo, tangent=tangent)
+        m23 = PlaneStressvonMises(E=E, nu=nu, sig0=sig0, tangent=tangent)
+        for m in (mh, m23):
+            m.set_data_manager(n)
+        for tag, lo, hi in (("elastic", 0.05, 0.95), ("mixed", 0.2, 8.0), ("yielded", 1.01, 100.0)):
+            rng = np.random.default_rng(2033)
+            v = rng.normal(size=(n, 3))
+            v *= (sig0 / psh.phi(v, expo) * np.exp(rng.uniform(np.log(lo), np.log(hi), n)))[:, None]
+            g3 = to_device(v @ psh.compliance(E, nu).T)
+            del v
+            th, t23 = [], []
+            for _ in range(3):          # interleaved: both kernels see the same drift of the machine
+                t23.append(timed(m23, g3, f3, c3))
+                th.append(timed(mh, g3, f3, c3))
+            _, sh = mh.stats()
+            _, s23 = m23.stats()
+            ms, ms23 = float(np.median(th)), float(np.median(t23))
+            ab = mh.algorithmic_bytes_per_point
+            r = {"law": f"ps_hosford:a10+{tangent}+{tag}", "points": n, "kernel": mh.kernel_name, "kernel_ms_repeats": [round(x, 4) for x in th],
+                 "kernel_ms": round(ms, 4), "algorithmic_bytes_per_point": ab, "frac_of_8TBs": round(ab * n / ms / 1e6 / 8000, 4),
+                 "ps_vonmises_ms_repeats": [round(x, 4) for x in t23], "ps_vonmises_ms": round(ms23, 4), "ratio_to_ps_vonmises": round(ms / ms23, 3),
+                 "plastic_fraction": round(sh["n_plastic"] / n, 4), "ps_vonmises_plastic_fraction": round(s23["n_plastic"] / n, 4),
+                 "max_local_iters": sh["max_local_iters"], "ps_vonmises_max_local_iters": s23["max_local_iters"],
+                 "not_converged": sh["n_not_converged"], "nan": sh["n_nan"]}
+            if a.blocks_per_cu:
+                sweep = {}
+                for b in a.blocks_per_cu:
+                    mh.set_option("blocks_per_cu", b)
+                    sweep[b] = round(timed(mh, g3, f3, c3), 4)
+                mh.set_option("blocks_per_cu", 32)      # the shipped grid again (plane_stress_hosford.hpp)
+                r["kernel_ms_by_blocks_per_cu"] = sweep
+            print(json.dumps(r), flush=True)
+            del g3
+        for m in (mh, m23):
+            m.close()
+        del mh, m23
+    del f3, c3
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -558,7 +631,7 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0, help="also time the plain-C oracle on this many points")
     ap.add_argument("--sym", action="store_true", help="symmetric-packed tangent (small-strain laws)")
     ap.add_argument("--blocks-per-cu", type=int, nargs="+", default=None,
-                    help="ramberg_osgood, plane_strain, ps_j2: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
+                    help="ramberg_osgood, plane_strain, ps_j2, ps_hosford: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
@@ -598,6 +671,9 @@ def main():
             continue
         if law == "ps_j2":   # laws 30 / 31 beside law 23 and laws 27 / 28 of this process: six lines
             bench_plane_stress_j2(a)
+            continue
+        if law == "ps_hosford":   # law 33 beside law 23 of this process: six lines
+            bench_plane_stress_hosford(a)
             continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
