@@ -161,6 +161,10 @@ SYMBOLS = {
         _h,
         [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int],
     ),
+    "dxm_mesh_create_plane": (
+        _h,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int],
+    ),
     "dxm_mesh_destroy": (C.c_int, [_h]),
     "dxm_mesh_npoints": (C.c_int64, [_h]),
     "dxm_mesh_displacement_size": (C.c_int64, [_h]),

@@ -42,6 +42,7 @@
 #include "plane_strain.hpp"
 #include "plane_stress_j2.hpp"
 #include "plane_stress_hosford.hpp"
+#include "plane_gradient.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -181,6 +182,9 @@ struct LawDesc {
   dxm_tangent_block blocks[DXM_MAX_TANGENT_BLOCKS];
   int ct_full;                            // doubles per point of the full tangent; 0: n_flux * n_grad (ct_full_of)
   const char* no_displacement;            // null: the gradient may be evaluated from a displacement (dxm_integrate_displacement*); else the refusal
+  int plane_kind;                         // the gradient kind a two-dimensional mesh is asked for (plane_gradient.hpp: 2 the plane-strain
+                                          // 4-vector, 3 the in-plane 3-vector); there the two refusals above do not apply and the gradient
+                                          // kernel always runs on its own.  0: the law is 6 or 9 wide on every mesh
 };
 
 // doubles per point of the full tangent layout: the sum of the law's blocks
@@ -848,9 +852,9 @@ constexpr LawDesc law_fs_single_crystal() {
 }
 
 // The two plane-stress return mappings (plane_stress.hip): strain in (24 B) and the hidden plastic strain read (24); stress (24),
-// the 3x3 tangent (72) and the plastic strain (24) out: 168 B/point.  Strain and stress are 3 wide: gradient_kind below takes every
-// law that is not 9 wide for a 6-wide strain, so the refusals of the fused and displacement forms are what keeps a mesh gradient
-// away from these rows
+// the 3x3 tangent (72) and the plastic strain (24) out: 168 B/point.  Strain and stress are 3 wide: on a mesh that is not
+// two-dimensional the refusals of the fused and displacement forms are what keeps a 6-wide mesh gradient away from these rows; a
+// two-dimensional mesh is asked for plane_kind (the in-plane 3-vector of plane_gradient.hip) and the update kernel runs after it
 constexpr LawDesc plane_stress_law(int id, int n_params, const char* kernel) {
   LawDesc d{};
   d.id = id;
@@ -864,6 +868,7 @@ constexpr LawDesc plane_stress_law(int id, int n_params, const char* kernel) {
   d.kernel = kernel;
   d.blocks_per_cu = PS_BLOCKS_PER_CU;   // plane_stress.hpp
   d.set_layouts = d.launch_layouts = L_FULL;
+  d.plane_kind = GRAD_IN_PLANE3;
   return d;
 }
 
@@ -879,7 +884,7 @@ constexpr LawDesc law_ps_quadratic() {
                                      "available, no packed record (sym / coef / pack4) exists for this law";
   d.no_fused = d.no_displacement = "the plane-stress quadratic yield set takes a 3-wide strain [xx, yy, sqrt(2) xy]: the mesh gradient "
                                    "kernels evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
-                                   "fused displacement gradient are not served; pass the strain as an array";
+                                   "fused displacement gradient are not served on a mesh that is not two-dimensional; pass the strain as an array";
   d.no_frame = "the plane-stress quadratic yield set is isotropic: a material frame changes nothing in its update";
   return d;
 }
@@ -897,16 +902,17 @@ constexpr LawDesc law_ps_polygon() {
                                      "available, no packed record (sym / coef / pack4) exists for this law";
   d.no_fused = d.no_displacement = "the plane-stress polygonal yield set takes a 3-wide strain [xx, yy, sqrt(2) xy]: the mesh gradient "
                                    "kernels evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
-                                   "fused displacement gradient are not served; pass the strain as an array";
+                                   "fused displacement gradient are not served on a mesh that is not two-dimensional; pass the strain as an array";
   d.no_frame = "the plane-stress polygonal yield set is a function of the principal stresses: a material frame changes nothing in its update";
   return d;
 }
 
 // The plane-strain forms of laws 0 / 1 / 2 (plane_strain.hip): strain in (32 B), stress (32) and the 4x4 tangent (128) out: 192
-// B/point; the J2 laws read and write p and the 4-wide plastic strain (40 + 40): 272.  Strain and stress are 4 wide: gradient_kind
-// takes every law that is not 9 wide for a 6-wide strain, so the refusals of the fused and displacement forms are what keeps a mesh
-// gradient away from these rows.  Grid: 128 workgroups per CU for the elastic and the linear-hardening law, 256 for Voce, from two
-// sweeps at 1e7 points (plane_strain.hpp, profiles/r21_plane_strain.md); every other size is UNMEASURED for these kernels
+// B/point; the J2 laws read and write p and the 4-wide plastic strain (40 + 40): 272.  Strain and stress are 4 wide: on a mesh that is
+// not two-dimensional the refusals of the fused and displacement forms are what keeps a 6-wide mesh gradient away from these rows; a
+// two-dimensional mesh is asked for plane_kind (the 4-vector of plane_gradient.hip) and the update kernel runs after it.
+// Grid: 128 workgroups per CU for the elastic and the linear-hardening law, 256 for Voce, from two sweeps at 1e7 points
+// (plane_strain.hpp, profiles/r21_plane_strain.md); every other size is UNMEASURED for these kernels
 constexpr LawDesc plane_strain_law(int id, int n_params, int alg_bytes, const char* kernel) {
   LawDesc d{};
   d.id = id;
@@ -922,7 +928,8 @@ constexpr LawDesc plane_strain_law(int id, int n_params, int alg_bytes, const ch
                 "DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE (embed the strain as [xx, yy, zz, xy, 0, 0] to use them)";
   d.no_fused = d.no_displacement = "the plane-strain laws take a 4-wide strain [xx, yy, zz, sqrt(2) xy]: the mesh gradient kernels "
                                    "evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
-                                   "fused displacement gradient are not served; pass the strain as an array";
+                                   "fused displacement gradient are not served on a mesh that is not two-dimensional; pass the strain as an array";
+  d.plane_kind = GRAD_PLANE_STRAIN4;
   d.no_frame = kNoFrame;
   d.stock_only = "the plane-strain laws take the stock hardening laws only (linear, Voce): they are served by the stock libdxmat, not by "
                  "a custom-hardening build";
@@ -966,8 +973,8 @@ constexpr LawDesc law_pe_j2_voce() {
 // Plane-stress J2 plasticity with linear or Voce hardening (plane_stress_j2.hip): laws 1 / 2 under sig_zz = 0 in the three components
 // [xx, yy, sqrt(2) xy] of laws 23 / 24.  Strain in (24 B), p and the in-plane plastic strain read (32); stress (24), the 3x3 tangent
 // (72) and the state (32) out: 184 B/point.  The parameters are those of laws 1 / 2 and go through their build functions.  Strain and
-// stress are 3 wide: gradient_kind takes every law that is not 9 wide for a 6-wide strain, so the refusals of the fused and
-// displacement forms are what keeps a mesh gradient away from these rows.  No external state variable is declared (n_ext = 0):
+// stress are 3 wide: the refusals of the fused and displacement forms govern the meshes that are not two-dimensional, plane_kind the
+// two-dimensional ones (see the rows of laws 23 / 24).  No external state variable is declared (n_ext = 0):
 // dxm_set_external_state* answers with the library's sentence for every law without one
 constexpr LawDesc plane_stress_j2_law(int id, int n_params, const char* kernel) {
   LawDesc d{};
@@ -988,7 +995,8 @@ constexpr LawDesc plane_stress_j2_law(int id, int n_params, const char* kernel) 
                 "DXM_LAW_J2_LINEAR and DXM_LAW_J2_VOCE, and the plane-stress constants are formed once per handle";
   d.no_fused = d.no_displacement = "plane-stress J2 plasticity takes a 3-wide strain [xx, yy, sqrt(2) xy]: the mesh gradient kernels "
                                    "evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
-                                   "fused displacement gradient are not served; pass the strain as an array";
+                                   "fused displacement gradient are not served on a mesh that is not two-dimensional; pass the strain as an array";
+  d.plane_kind = GRAD_IN_PLANE3;
   d.no_frame = kNoFrame;
   d.stock_only = "plane-stress J2 plasticity takes the stock hardening laws only (linear, Voce): it is served by the stock libdxmat, not "
                  "by a custom-hardening build";
@@ -1036,7 +1044,8 @@ constexpr LawDesc law_ps_hosford() {
                                      "DXM_TANGENT_FULL is available, no packed record (sym / coef / pack4) exists for this law";
   d.no_fused = d.no_displacement = "plane-stress Hosford plasticity takes a 3-wide strain [xx, yy, sqrt(2) xy]: the mesh gradient kernels "
                                    "evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the fused "
-                                   "displacement gradient are not served; pass the strain as an array";
+                                   "displacement gradient are not served on a mesh that is not two-dimensional; pass the strain as an array";
+  d.plane_kind = GRAD_IN_PLANE3;
   d.no_frame = "plane-stress Hosford plasticity is a function of the principal stresses: a material frame changes nothing in its update";
   return d;
 }
@@ -1066,8 +1075,9 @@ static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws
 // parameters a law takes in THIS build: a custom-hardening build takes [E, nu, sig0, c0..c5] for the two "voce" slots
 static int n_params_of(const LawDesc& d) { return kCustomBuild ? d.n_params_custom : d.n_params; }
 
-// what the mesh gradient kernel evaluates for the law: 1 the deformation gradient F (9 components), 0 the small strain (6)
-static int gradient_kind(const LawDesc& d) { return d.n_grad == 9 ? 1 : 0; }
+// what the mesh gradient kernel evaluates for the law: 1 the deformation gradient F (9 components), 0 the small strain (6); on a
+// two-dimensional mesh the row's plane_kind where it has one
+static int gradient_kind(const LawDesc& d, bool on_2d_mesh) { return on_2d_mesh && d.plane_kind ? d.plane_kind : d.n_grad == 9 ? 1 : 0; }
 
 static int tangent_size(const dxm_material* m);
 
@@ -2660,7 +2670,16 @@ struct dxm_mesh {
   int64_t n_dofs = 0;
   int32_t* d_dofmap = nullptr;
   double* d_dphi = nullptr;
+  // two-dimensional meshes (tdim 2): what plane_gradient.hip reads.  geom_nv vertices per cell in d_conn and the reference derivatives
+  // of the geometry's shape functions at the Gauss points, (nqp, geom_nv, 2): the caller's for dxm_mesh_create_plane, the constant
+  // table of the affine triangle for dxm_mesh_create_simplex.  plane: made by dxm_mesh_create_plane (no in-kernel gradient form)
+  int geom_nv = 0;
+  double* d_gdphi = nullptr;
+  bool plane = false;
 };
+
+// triangles through dxm_mesh_create_simplex, triangles and quadrilaterals through dxm_mesh_create_plane
+static bool mesh_2d(const dxm_mesh* mesh) { return mesh->nodes_per_cell == 0 && mesh->tdim == 2; }
 
 static dxm_mesh* mesh_create(int npc, const double* coords, int64_t n_nodes, const int32_t* conn,
                              int64_t n_cells, const double* qpoints, int nqp, int device) {
@@ -2761,6 +2780,95 @@ dxm_mesh* dxm_mesh_create_simplex(int tdim, const double* coords, int64_t n_vert
   ok = ok && upload_from_host(mesh->d_conn, geom_conn, sizeof(int32_t) * nv * n_cells, nullptr) == 0;
   ok = ok && upload_from_host(mesh->d_dofmap, dofmap, sizeof(int32_t) * nd * n_cells, nullptr) == 0;
   ok = ok && upload_from_host(mesh->d_dphi, dphi, sizeof(double) * nqp * nd * tdim, nullptr) == 0;
+  if (tdim == 2) {   // kinds 2 and 3 run through plane_gradient.hip: the affine triangle's table, the same at every point
+    std::vector<double> gd((size_t)nqp * 6);
+    for (int q = 0; q < nqp; ++q) {
+      const double t[6] = {-1.0, -1.0, 1.0, 0.0, 0.0, 1.0};
+      std::copy(t, t + 6, gd.begin() + 6 * q);
+    }
+    mesh->geom_nv = 3;
+    ok = ok && hipMalloc(&mesh->d_gdphi, sizeof(double) * gd.size()) == hipSuccess;
+    ok = ok && upload_from_host(mesh->d_gdphi, gd.data(), sizeof(double) * gd.size(), nullptr) == 0;
+  }
+  if (!ok) {
+    fail(-3, "device allocation / upload of the mesh failed");
+    dxm_mesh_destroy(mesh);
+    return nullptr;
+  }
+  return mesh;
+}
+
+dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
+                                const int32_t* dofmap, int nd, int64_t n_dofs, const double* geom_dphi, const double* dphi, int nqp,
+                                int device) {
+  // every check runs on the host before a device is asked for: the kernels are never launched on indices that were not checked
+  if (nv != 3 && nv != 4) {
+    fail(-1, "a plane mesh has nv = 3 (triangles) or nv = 4 (bilinear quadrilaterals) vertices per cell, not %d", nv);
+    return nullptr;
+  }
+  if (!coords || !geom_conn || !dofmap || !geom_dphi || !dphi || n_vertices <= 0 || n_cells <= 0 || nd < nv ||
+      nd > PLANE_GRAD_MAX_ND || n_dofs <= 0 || nqp <= 0 || nqp > PLANE_GRAD_MAX_NQP) {
+    fail(-1, "invalid plane mesh arguments");
+    return nullptr;
+  }
+  for (int64_t k = 0; k < n_cells * nv; ++k)
+    if (geom_conn[k] < 0 || geom_conn[k] >= n_vertices) { fail(-1, "geometry connectivity entry %lld out of range", (long long)k); return nullptr; }
+  for (int64_t k = 0; k < n_cells * nd; ++k)
+    if (dofmap[k] < 0 || dofmap[k] >= n_dofs) { fail(-1, "dofmap entry %lld out of range", (long long)k); return nullptr; }
+  // det J at every Gauss point: zero or not finite puts Inf / NaN into the gradient, a change of sign within a cell is a cell that
+  // folds over (a bow-tie quadrilateral).  One sign per cell, not per mesh: the cells of a dolfinx mesh are numbered either way round
+  for (int64_t c = 0; c < n_cells; ++c) {
+    double sign = 0.0;
+    for (int q = 0; q < nqp; ++q) {
+      double J[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int v = 0; v < nv; ++v) {
+        const double* X = coords + 3 * (int64_t)geom_conn[c * nv + v];
+        const double* t = geom_dphi + ((int64_t)q * nv + v) * 2;
+        J[0] += X[0] * t[0]; J[1] += X[0] * t[1];
+        J[2] += X[1] * t[0]; J[3] += X[1] * t[1];
+      }
+      const double det = J[0] * J[3] - J[1] * J[2];
+      if (!(det != 0.0) || !std::isfinite(det)) {
+        fail(-1, "cell %lld is degenerate: det J is zero or not finite at Gauss point %d", (long long)c, q);
+        return nullptr;
+      }
+      if (sign == 0.0) sign = det;
+      if ((det > 0.0) != (sign > 0.0)) {
+        fail(-1, "cell %lld is folded over (a bow-tie quadrilateral?): det J changes sign at Gauss point %d", (long long)c, q);
+        return nullptr;
+      }
+    }
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
+    fail(-2, "no usable HIP device %d (libdxmat has no CPU fallback)", device);
+    return nullptr;
+  }
+  dxm_mesh* mesh = new dxm_mesh();
+  mesh->nodes_per_cell = 0;
+  mesh->plane = true;
+  mesh->device = device;
+  mesh->n_nodes = n_vertices;
+  mesh->n_cells = n_cells;
+  mesh->qp.nqp = nqp;
+  mesh->tdim = 2;
+  mesh->nd = nd;
+  mesh->geom_nv = nv;
+  mesh->n_dofs = n_dofs;
+  mesh->u_len = 2 * n_dofs;
+  DeviceGuard guard(device);
+  bool ok = guard.ok;
+  ok = ok && hipMalloc(&mesh->d_coords, sizeof(double) * 3 * n_vertices) == hipSuccess;
+  ok = ok && hipMalloc(&mesh->d_conn, sizeof(int32_t) * nv * n_cells) == hipSuccess;
+  ok = ok && hipMalloc(&mesh->d_dofmap, sizeof(int32_t) * nd * n_cells) == hipSuccess;
+  ok = ok && hipMalloc(&mesh->d_gdphi, sizeof(double) * nqp * nv * 2) == hipSuccess;
+  ok = ok && hipMalloc(&mesh->d_dphi, sizeof(double) * nqp * nd * 2) == hipSuccess;
+  ok = ok && hipMalloc(&mesh->d_u, sizeof(double) * mesh->u_len) == hipSuccess;
+  ok = ok && upload_from_host(mesh->d_coords, coords, sizeof(double) * 3 * n_vertices, nullptr) == 0;
+  ok = ok && upload_from_host(mesh->d_conn, geom_conn, sizeof(int32_t) * nv * n_cells, nullptr) == 0;
+  ok = ok && upload_from_host(mesh->d_dofmap, dofmap, sizeof(int32_t) * nd * n_cells, nullptr) == 0;
+  ok = ok && upload_from_host(mesh->d_gdphi, geom_dphi, sizeof(double) * nqp * nv * 2, nullptr) == 0;
+  ok = ok && upload_from_host(mesh->d_dphi, dphi, sizeof(double) * nqp * nd * 2, nullptr) == 0;
   if (!ok) {
     fail(-3, "device allocation / upload of the mesh failed");
     dxm_mesh_destroy(mesh);
@@ -2778,6 +2886,7 @@ int dxm_mesh_destroy(dxm_mesh* mesh) {
   if (mesh->d_u) (void)hipFree(mesh->d_u);
   if (mesh->d_dofmap) (void)hipFree(mesh->d_dofmap);
   if (mesh->d_dphi) (void)hipFree(mesh->d_dphi);
+  if (mesh->d_gdphi) (void)hipFree(mesh->d_gdphi);
   if (mesh->grad_done) (void)hipEventDestroy(mesh->grad_done);
   delete mesh;
   return 0;
@@ -2791,12 +2900,24 @@ static MeshSource mesh_source(const dxm_mesh* mesh, const double* u_dev);
 int dxm_mesh_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, double* grad_dev,
                              void* hip_stream) {
   if (!mesh || !u_dev || !grad_dev) return fail(-1, "null argument");
-  if (kind != 0 && kind != 1) return fail(-1, "gradient kind must be 0 (strain) or 1 (F)");
+  if (kind < 0 || kind > 3)
+    return fail(-1, "gradient kind must be 0 (strain), 1 (F), 2 (plane-strain 4-vector) or 3 (in-plane 3-vector)");
+  if (kind >= 2 && !mesh_2d(mesh))
+    return fail(-1, "gradient kinds 2 (plane-strain 4-vector) and 3 (in-plane 3-vector) are evaluated on two-dimensional meshes only "
+                    "(dxm_mesh_create_plane, dxm_mesh_create_simplex with tdim 2): this mesh is three-dimensional");
   DEVICE_GUARD(mesh);
   const int64_t npts = mesh->n_cells * mesh->qp.nqp;
   const int blocks = (int)((npts + 255) / 256);
   hipStream_t st = (hipStream_t)hip_stream;
-  if (mesh->nodes_per_cell == 0) {
+  if (mesh->plane || kind >= 2) {   // plane_gradient.hip: every kind on a plane mesh, kinds 2 and 3 on triangles of either constructor
+#ifdef DXM_CUSTOM_HARDENING
+    return fail(-1, "the plane gradient kernels (a mesh of dxm_mesh_create_plane; gradient kinds 2 and 3) are served by the stock "
+                    "libdxmat, not by a custom-hardening build, which is dxmat.hip alone");
+#else
+    HIP_TRY(plane_gradient_launch(kind, st, mesh->d_coords, mesh->d_conn, mesh->geom_nv, mesh->d_dofmap, mesh->nd, mesh->d_gdphi,
+                                  mesh->d_dphi, mesh->qp.nqp, mesh->n_cells, u_dev, grad_dev));
+#endif
+  } else if (mesh->nodes_per_cell == 0) {
     const MeshSource src = mesh_source(mesh, u_dev);
     if (kind == 0) hipLaunchKernelGGL(simplex_gradient_kernel<0>, dim3(blocks), dim3(256), 0, st, src, grad_dev);
     else hipLaunchKernelGGL(simplex_gradient_kernel<1>, dim3(blocks), dim3(256), 0, st, src, grad_dev);
@@ -2825,8 +2946,10 @@ int dxm_mesh_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, doub
   return 0;
 }
 
-// kind of in-kernel gradient evaluation this mesh allows: 1 hex8 x 8 points, 2 tet4, 3 Lagrange simplex, 0 none
+// kind of in-kernel gradient evaluation this mesh allows: 1 hex8 x 8 points, 2 tet4, 3 Lagrange simplex, 0 none (a plane mesh: its
+// gradient kernel runs on its own)
 static int fused_kind(const dxm_mesh* mesh) {
+  if (mesh->plane) return 0;
   if (mesh->nodes_per_cell == 8) return mesh->qp.nqp == 8 ? 1 : 0;
   if (mesh->nodes_per_cell == 0) return 3;
   return mesh->nodes_per_cell == 4 ? 2 : 0;
@@ -2846,13 +2969,14 @@ static bool fusable(const dxm_mesh* mesh) { return fused_kind(mesh) != 0; }
 static int integrate_displacement_host(dxm_material* m, dxm_mesh* mesh, const double* u_host, double* flux_aos, double* isv_aos,
                                        double* ct_aos, dxm_stats* stats, const int64_t* rows) {
   if (!m || !mesh || !u_host) return fail(-1, "null argument");
-  if (kLaws[m->law].no_displacement) return fail(-1, "%s", kLaws[m->law].no_displacement);
+  const bool plane_law = kLaws[m->law].plane_kind && mesh_2d(mesh);   // a 2-D law on a 2-D mesh: gradient kernel, then update kernel
+  if (kLaws[m->law].no_displacement && !plane_law) return fail(-1, "%s", kLaws[m->law].no_displacement);
   if (mesh->device != m->device) return fail(-1, "mesh and material live on different devices");
   if (dxm_mesh_npoints(mesh) != m->n) return fail(-1, "mesh has %lld Gauss points, material %lld",
                                                    (long long)dxm_mesh_npoints(mesh), (long long)m->n);
   DEVICE_GUARD(m);
   m->last_upload = DXM_UPLOAD_NONE;   // no gradient array crosses PCIe in this form
-  const bool fuse = m->opt_fused_gradient && fusable(mesh);   // gradient evaluated inside the update kernel
+  const bool fuse = m->opt_fused_gradient && fusable(mesh) && !plane_law;   // gradient evaluated inside the update kernel
   if (int rc = ensure_host_path_buffers(m, !fuse)) return rc;
   hipStream_t st = m->own_stream;
   if (int rc = sync_last(m)) return rc;
@@ -2861,7 +2985,7 @@ static int integrate_displacement_host(dxm_material* m, dxm_mesh* mesh, const do
   if (fuse) {
     src = mesh_source(mesh, mesh->d_u);
   } else {
-    if (int rc = dxm_mesh_gradient_device(mesh, mesh->d_u, gradient_kind(kLaws[m->law]), m->d_grad, st)) return rc;
+    if (int rc = dxm_mesh_gradient_device(mesh, mesh->d_u, gradient_kind(kLaws[m->law], mesh_2d(mesh)), m->d_grad, st)) return rc;
   }
   // the displacement upload (and the gradient array) are produced on own_stream; chunks on the second stream wait for it
   if (!mesh->grad_done) HIP_TRY(hipEventCreateWithFlags(&mesh->grad_done, hipEventDisableTiming));
@@ -2890,7 +3014,8 @@ int dxm_integrate_displacement_rows(dxm_material* m, dxm_mesh* mesh, const doubl
 int dxm_integrate_displacement_device(dxm_material* m, dxm_mesh* mesh, const double* u_dev, double dt,
                                       double* flux_dev, double* ct_dev, void* hip_stream) {
   if (!m || !mesh) return fail(-1, "null argument");
-  if (kLaws[m->law].no_displacement) return fail(-1, "%s", kLaws[m->law].no_displacement);
+  const bool plane_law = kLaws[m->law].plane_kind && mesh_2d(mesh);   // the 2-D laws have no fused form: the option makes no difference
+  if (kLaws[m->law].no_displacement && !plane_law) return fail(-1, "%s", kLaws[m->law].no_displacement);
   if (int rc = take_dt(m, dt)) return rc;
   if (mesh->device != m->device) return fail(-1, "mesh and material live on different devices");
   if (dxm_mesh_npoints(mesh) != m->n) return fail(-1, "mesh has %lld Gauss points, material %lld",
@@ -2899,13 +3024,13 @@ int dxm_integrate_displacement_device(dxm_material* m, dxm_mesh* mesh, const dou
   DEVICE_GUARD(m);
   hipStream_t st = (hipStream_t)hip_stream;
   const LawDesc& d = kLaws[m->law];
-  if (m->opt_fused_gradient && fusable(mesh)) {   // one kernel: no gradient array at all
+  if (m->opt_fused_gradient && fusable(mesh) && !plane_law) {   // one kernel: no gradient array at all
     const MeshSource src = mesh_source(mesh, u_dev);
     return launch(m, flux_dev /* unused, only checked for alignment */, flux_dev, ct_dev, st, &src);
   }
   // two kernels on the caller's stream through the handle's gradient scratch
   if (!m->d_grad) HIP_TRY(hipMalloc(&m->d_grad, sizeof(double) * m->n * d.n_grad));
-  if (int rc = dxm_mesh_gradient_device(mesh, u_dev, gradient_kind(d), m->d_grad, hip_stream)) return rc;
+  if (int rc = dxm_mesh_gradient_device(mesh, u_dev, gradient_kind(d, mesh_2d(mesh)), m->d_grad, hip_stream)) return rc;
   return launch(m, m->d_grad, flux_dev, ct_dev, st);
 }
 

@@ -1,5 +1,5 @@
-"""Device-side gradient evaluation for first-order hexahedra / tetrahedra and for Lagrange elements of any order on
-straight-sided simplices (``dxm_mesh_*`` of ``include/dxmat.h``).
+"""Device-side gradient evaluation for first-order hexahedra / tetrahedra, for Lagrange elements of any order on
+straight-sided simplices and for plane meshes of triangles or bilinear quadrilaterals (``dxm_mesh_*`` of ``include/dxmat.h``).
 
 The step before the hot path in the reference is ``QuadratureExpression.eval`` ->
 ``fem.Expression.eval`` (``quadrature_function.py:45-51``): dolfinx tabulates the UFL gradient at
@@ -21,8 +21,19 @@ def gauss_points_hex(degree=2):
 
 
 class _DeviceMesh:
+    #: topological dimension of the cells (``SimplexMesh``: 2 or 3, set per instance)
+    tdim = 3
+
     def gradient_device(self, u_ptr, kind, grad_ptr, stream=0):
-        """kind 0: Mandel strain (6); 1: F (9).  Device pointers, asynchronous on ``stream``."""
+        """Device pointers, asynchronous on ``stream``.  With ``H[i][a] = du_i / dX_a`` and ``r = sqrt(2) / 2``, ``kind``
+
+        * 0: Mandel strain (6);
+        * 1: deformation gradient ``F = I + H`` (9);
+        * 2: the plane-strain 4-vector ``[H00, H11, 0.0, r (H01 + H10)]`` of the ``hypothesis="plane_strain"`` laws;
+        * 3: the in-plane 3-vector ``[H00, H11, r (H01 + H10)]`` of the plane-stress laws.
+
+        Kinds 2 and 3 on two-dimensional meshes only (``tdim == 2``: :class:`PlaneMesh`, :class:`SimplexMesh` on triangles);
+        ``grad_ptr`` holds ``npoints`` rows of 6, 9, 4 or 3 doubles."""
         _lib.check(self._lib.dxm_mesh_gradient_device(self._handle, int(u_ptr), int(kind), int(grad_ptr), int(stream) or None))
 
     @property
@@ -259,3 +270,156 @@ class SimplexMesh(_DeviceMesh):
         if cells is not None:
             geom_conn, dofmap = geom_conn[np.asarray(cells)], dofmap[np.asarray(cells)]
         return cls(np.asarray(mesh.geometry.x), geom_conn, dofmap, n_dofs, dphi, device=device)
+
+
+# ---- plane meshes: triangles and bilinear quadrilaterals ---------------------------------------------------------------------------
+#: local vertex pairs of the edges of the reference quadrilateral [0,1]^2 (vertices (0,0),(1,0),(0,1),(1,1)) in basix's edge numbering
+BASIX_QUAD_EDGES = ((0, 1), (0, 2), (1, 3), (2, 3))
+#: the 1-D node (0: x = 0, 1: x = 1, 2: x = 1/2) in each direction of the nine Q2 dofs in basix's order: vertices, edges, interior
+_Q2_NODES = ((0, 0), (1, 0), (0, 1), (1, 1), (2, 0), (0, 2), (1, 2), (2, 1), (2, 2))
+
+
+def quad_quadrature(degree):
+    """Tensor Gauss-Legendre points (nqp, 2) on [0,1]^2 exact for polynomials of the given degree per direction (``degree // 2 + 1``
+    points per direction), second coordinate fastest.  For stand-alone use and tests; with dolfinx take basix's points
+    (:meth:`PlaneMesh.from_dolfinx` does), whose order defines the row order of the quadrature Functions."""
+    n = int(degree) // 2 + 1
+    x, _ = np.polynomial.legendre.leggauss(n)
+    x = 0.5 * (x + 1.0)
+    return np.array([[a, b] for a in x for b in x])
+
+
+def lagrange_quad_table(degree, points):
+    """Reference derivatives ``dphi[q, m, d] = d N_m / d xi_d`` of the tensor-product Lagrange basis Q1 or Q2 on [0,1]^2 at ``points``
+    (nqp, 2), dofs in basix's order: vertices (0,0),(1,0),(0,1),(1,1), then the midpoints of the edges :data:`BASIX_QUAD_EDGES`, then
+    the interior dof.  ``N = L_i(x) L_j(y)`` with the 1-D bases ``1 - t, t`` (Q1) and ``(1 - t)(1 - 2t), t (2t - 1), 4 t (1 - t)``."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    if degree == 1:
+        L = [np.stack([1.0 - pts[:, d], pts[:, d]], axis=1) for d in range(2)]
+        dL = [np.stack([-np.ones(len(pts)), np.ones(len(pts))], axis=1) for d in range(2)]
+        nodes = _Q2_NODES[:4]
+    elif degree == 2:
+        L = [np.stack([(1.0 - t) * (1.0 - 2.0 * t), t * (2.0 * t - 1.0), 4.0 * t * (1.0 - t)], axis=1) for t in (pts[:, 0], pts[:, 1])]
+        dL = [np.stack([4.0 * t - 3.0, 4.0 * t - 1.0, 4.0 - 8.0 * t], axis=1) for t in (pts[:, 0], pts[:, 1])]
+        nodes = _Q2_NODES
+    else:
+        raise ValueError("lagrange_quad_table: degree 1 or 2 (hand any other table to PlaneMesh directly)")
+    cols = [np.stack([dL[0][:, i] * L[1][:, j], L[0][:, i] * dL[1][:, j]], axis=1) for i, j in nodes]
+    return np.ascontiguousarray(np.stack(cols, axis=1))
+
+
+def q2_dofmap(cells):
+    """Second-order Lagrange (Q2) dofmap of a quadrilateral mesh given by its vertex table ``cells`` (n_cells, 4), vertices in
+    basix's order: vertex dofs keep the vertex numbers, then one dof per unique edge, then one per cell.  Returns
+    ``(dofmap (n_cells, 9), n_dofs, edge_vertices)`` with ``edge_vertices`` (n_edges, 2) the end points of the edge dof
+    ``n_vertices + k``; the interior dof of cell ``c`` is ``n_vertices + n_edges + c``."""
+    cells = np.asarray(cells, dtype=np.int64)
+    nv = int(cells.max()) + 1
+    pairs = np.stack([np.sort(cells[:, list(e)], axis=1) for e in BASIX_QUAD_EDGES], axis=1)   # (n_cells, 4, 2)
+    uniq, inv = np.unique(pairs.reshape(-1, 2), axis=0, return_inverse=True)
+    inner = nv + len(uniq) + np.arange(len(cells))
+    dofmap = np.concatenate([cells, nv + inv.reshape(len(cells), -1), inner[:, None]], axis=1).astype(np.int32)
+    return dofmap, nv + len(uniq) + len(cells), uniq
+
+
+class PlaneMesh(_DeviceMesh):
+    """Lagrange displacement of any order on a two-dimensional mesh of triangles or bilinear quadrilaterals
+    (``dxm_mesh_create_plane``): the N x N quadrilaterals of the reference's ``tests/uniaxial_tension.py`` and the tri6 mesh of
+    ``plane_elastoplasticity.py``.  It answers the four kinds of :meth:`gradient_device`, so it serves the 4-wide plane-strain laws,
+    the 3-wide plane-stress laws and, embedded, the 6-wide and 9-wide laws.
+
+    ``coords`` (n_vertices, 2|3) and ``geom_conn`` (n_cells, 3|4) give the geometry, ``geom_dphi`` (nqp, nv, 2) the reference
+    derivatives of ITS shape functions at the Gauss points (quadrilaterals: :func:`lagrange_quad_table` of degree 1, vertices in
+    basix's order (0,0),(1,0),(0,1),(1,1)); ``dofmap`` (n_cells, nd) indexes the ``n_dofs`` blocks of two displacement components
+    and ``dphi`` (nqp, nd, 2) are the derivatives of the field's shape functions at the same points.  Gauss point ``q`` of cell
+    ``c`` is point ``c * nqp + q``.  The library checks every index and ``det J`` at every Gauss point before it touches a device."""
+
+    tdim = 2
+
+    def __init__(self, coords, geom_conn, dofmap, n_dofs, geom_dphi, dphi, device=0):
+        self._lib = _lib.load()
+        geom_conn = np.ascontiguousarray(geom_conn, dtype=np.int32)
+        coords = np.asarray(coords, dtype=np.float64)
+        if coords.shape[1] == 2:
+            coords = np.concatenate([coords, np.zeros((len(coords), 1))], axis=1)
+        coords = np.ascontiguousarray(coords)
+        dofmap = np.ascontiguousarray(dofmap, dtype=np.int32)
+        geom_dphi = np.ascontiguousarray(geom_dphi, dtype=np.float64)
+        dphi = np.ascontiguousarray(dphi, dtype=np.float64)
+        if dphi.ndim != 3 or dphi.shape[1] != dofmap.shape[1] or dphi.shape[2] != 2 or len(dofmap) != len(geom_conn):
+            raise ValueError("dphi must be (nqp, nd, 2) with nd = dofmap.shape[1]; one dofmap row per cell")
+        if geom_dphi.shape != (dphi.shape[0], geom_conn.shape[1], 2):
+            raise ValueError("geom_dphi must be (nqp, nv, 2) with nv = geom_conn.shape[1] and the nqp of dphi")
+        self.n_nodes, self.n_cells, self.nqp = coords.shape[0], geom_conn.shape[0], dphi.shape[0]
+        self.nv, self.nd, self.n_dofs, self.device = geom_conn.shape[1], dofmap.shape[1], int(n_dofs), int(device)
+        h = self._lib.dxm_mesh_create_plane(coords.ctypes.data, self.n_nodes, geom_conn.ctypes.data, self.nv, self.n_cells,
+                                            dofmap.ctypes.data, self.nd, self.n_dofs, geom_dphi.ctypes.data, dphi.ctypes.data,
+                                            self.nqp, self.device)
+        if not h:
+            raise _lib.DxmError(f"dxm_mesh_create_plane failed: {_lib.last_error()}")
+        self._handle = h
+
+    @classmethod
+    def lagrange(cls, coords, cells, degree=1, quadrature_degree=None, device=0):
+        """Stand-alone constructor (no dolfinx): first- or second-order displacement on the vertex mesh ``(coords, cells)`` of
+        triangles (three columns; P2 dofs as numbered by :func:`p2_dofmap`, points of :func:`simplex_quadrature`, default degree
+        ``2 (degree - 1)``) or quadrilaterals (four columns in basix's vertex order; Q2 dofs as numbered by :func:`q2_dofmap`,
+        points of :func:`quad_quadrature`, default degree ``2 degree``).  Returns ``(mesh, dof_coords)`` with the
+        (n_dofs, coords.shape[1]) dof positions."""
+        coords, cells = np.asarray(coords, dtype=np.float64), np.asarray(cells)
+        if degree not in (1, 2):
+            raise ValueError("PlaneMesh.lagrange: degree 1 or 2 (hand any other table to PlaneMesh directly)")
+        if cells.shape[1] == 3:
+            pts = simplex_quadrature(2, 2 * (degree - 1) if quadrature_degree is None else quadrature_degree)
+            geom_dphi, dphi = lagrange_simplex_table(2, 1, pts), lagrange_simplex_table(2, degree, pts)
+            dofmap, n_dofs, edges = p2_dofmap(cells) if degree == 2 else (cells, len(coords), None)
+            inner = np.empty((0, coords.shape[1]))
+        elif cells.shape[1] == 4:
+            pts = quad_quadrature(2 * degree if quadrature_degree is None else quadrature_degree)
+            geom_dphi, dphi = lagrange_quad_table(1, pts), lagrange_quad_table(degree, pts)
+            dofmap, n_dofs, edges = q2_dofmap(cells) if degree == 2 else (cells, len(coords), None)
+            inner = coords[cells].mean(axis=1)            # the bilinear image of (1/2, 1/2)
+        else:
+            raise ValueError("PlaneMesh.lagrange: cells with 3 (triangles) or 4 (quadrilaterals) vertices")
+        mesh = cls(coords, cells, dofmap, n_dofs, geom_dphi, dphi, device=device)
+        if degree == 1:
+            return mesh, coords.copy()
+        return mesh, np.concatenate([coords, 0.5 * (coords[edges[:, 0]] + coords[edges[:, 1]]), inner], axis=0)
+
+    @classmethod
+    def from_dolfinx(cls, V, quadrature_degree, device=0, cells=None):
+        """From a dolfinx vector Lagrange space (any order, block size 2; ``cells``: those of one ``QuadratureMap`` instead of all)
+        on a first-order triangle or quadrilateral mesh: geometry from ``mesh.geometry`` with the table of basix's first-order
+        coordinate element, the dofmap of ``V`` as it is, Gauss points and the field's tabulated derivatives from basix -- so point
+        ``c * nqp + q`` is row ``c * nqp + q`` of the quadrature Functions and ``u.x.array`` is the vector to hand to
+        ``integrate_displacement``.  UNTESTED without dolfinx."""
+        import basix
+
+        mesh = V.mesh
+        if mesh.topology.dim != 2 or V.dofmap.index_map_bs != 2:
+            raise ValueError("PlaneMesh.from_dolfinx needs a vector Lagrange space with block size 2 on a two-dimensional mesh")
+        dofmap = np.asarray(V.dofmap.list, dtype=np.int32)
+        n_cells = dofmap.shape[0] if dofmap.ndim == 2 else len(dofmap) // len(V.dofmap.cell_dofs(0))
+        dofmap = dofmap.reshape(n_cells, -1)
+        geom_conn = np.asarray(mesh.geometry.dofmap, dtype=np.int32).reshape(n_cells, -1)
+        nv = geom_conn.shape[1]
+        if nv not in (3, 4):
+            raise ValueError("PlaneMesh.from_dolfinx needs a first-order triangle or quadrilateral geometry (no curved cells)")
+        cell = basix.CellType.triangle if nv == 3 else basix.CellType.quadrilateral
+        pts, _ = basix.make_quadrature(cell, int(quadrature_degree))
+        pts = np.asarray(pts)
+
+        def table(element, nd):
+            tab = np.asarray(element.tabulate(1, pts))
+            if tab.ndim == 4:
+                tab = tab[..., 0]
+            if tab.shape[2] != nd:      # blocked element tabulated with its block: the scalar basis is every second function
+                tab = tab[:, :, ::2]
+            return np.ascontiguousarray(tab[1:3].transpose(1, 2, 0))
+
+        geom_dphi = table(basix.create_element(basix.ElementFamily.P, cell, 1), nv)
+        dphi = table(V.element.basix_element, dofmap.shape[1])
+        n_dofs = V.dofmap.index_map.size_local + V.dofmap.index_map.num_ghosts
+        if cells is not None:
+            geom_conn, dofmap = geom_conn[np.asarray(cells)], dofmap[np.asarray(cells)]
+        return cls(np.asarray(mesh.geometry.x), geom_conn, dofmap, n_dofs, geom_dphi, dphi, device=device)

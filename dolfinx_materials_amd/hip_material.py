@@ -1134,9 +1134,11 @@ class HIPMaterial:
     def integrate_displacement(self, mesh, u, dt=None):
         """Same as :meth:`integrate`, with the gradient evaluated on the device from the nodal
         displacement vector ``u`` (``mesh``: :class:`~dolfinx_materials_amd.gradient.Hex8Mesh`,
-        :class:`~dolfinx_materials_amd.gradient.Tet4Mesh` or :class:`~dolfinx_materials_amd.gradient.SimplexMesh`):
+        :class:`~dolfinx_materials_amd.gradient.Tet4Mesh`, :class:`~dolfinx_materials_amd.gradient.SimplexMesh` or
+        :class:`~dolfinx_materials_amd.gradient.PlaneMesh`):
         only ``u`` crosses PCIe on the way in (the step before the path,
-        ``quadrature_function.py:45-51``)."""
+        ``quadrature_function.py:45-51``).  The 4-wide plane-strain laws and the 3-wide plane-stress laws take a two-dimensional
+        mesh (``mesh.tdim == 2``), whose gradient kernel writes their 4- or 3-wide strain; any other mesh is refused for them."""
         self._require()   # the mesh lives on one GPU
         self._refuse_with_row_deliveries("integrate_displacement")
         nf, ng = self._info.n_flux, self._info.n_grad
@@ -1181,7 +1183,9 @@ class HIPMaterial:
         """Device-resident form of :meth:`integrate_displacement`: ``u_ptr`` is the device address of
         the displacement vector (``mesh.displacement_size`` doubles), ``flux_ptr`` / ``ct_ptr`` device arrays as for
         :meth:`integrate_device`; asynchronous on ``stream``.  For hex8 meshes with 8 Gauss points per
-        cell, tet4 meshes and Lagrange simplex meshes the gradient is evaluated inside the update kernel."""
+        cell, tet4 meshes and Lagrange simplex meshes the gradient is evaluated inside the update kernel; on a
+        :class:`~dolfinx_materials_amd.gradient.PlaneMesh`, and for the 4-wide and 3-wide laws on every two-dimensional mesh, the
+        gradient kernel fills the handle's scratch array and the update kernel follows on the same stream."""
         self._host_mirrors_left_behind()
         self._chk(self._lib.dxm_integrate_displacement_device(
             self._require(), mesh._handle, int(u_ptr), self._dt(dt), int(flux_ptr), int(ct_ptr), int(stream) or None))

@@ -211,8 +211,10 @@ enum {
    * elastic point writes back the bits it read.  A caller that sets a Strain / Stress state sets epsp_n = eps_n - C^-1 s_n.
    * tangent = 0 writes C at every point (the reference's); tangent = 1 writes the algorithmic tangent of a yielded point,
    * A - (A n)(A n)^T / (n^T A n) with A = (C^-1 + l Q)^-1 and n = Q s, and C at an elastic one.  9 entries, row-major.
-   * DXM_TANGENT_FULL only; no material frame, no per-point parameter fields, none of the displacement forms, no fused
-   * displacement gradient (the mesh gradient kernels evaluate 6-wide strains or F), not served by a custom-hardening build.
+   * DXM_TANGENT_FULL only; no material frame, no per-point parameter fields, not served by a custom-hardening build.  The
+   * displacement forms (dxm_integrate_displacement*) are served on two-dimensional meshes (dxm_mesh_create_plane,
+   * dxm_mesh_create_simplex with tdim 2): the gradient kernel writes kind 3 of dxm_mesh_gradient_device, then this law's kernel runs;
+   * there is no fused form and option fused_gradient makes no difference.  On any other mesh they are refused.
    * dxm_stats: n_plastic counts the projected points; max_local_iters is the largest number of Newton steps a point took before
    * its residual met the bound; n_not_converged counts the points that reached the cap of dxm_set_newton (they write their last
    * iterate); n_nan counts points with a non-finite stress, state or (tangent = 1) tangent entry.
@@ -239,8 +241,9 @@ enum {
    * 6-wide law's block (whose out-of-plane rest is zero for such a state).  DXM_TANGENT_FULL only.
    * State of the two J2 laws: field 0 p (1), field 1 epsp (4, the same order), 5 SoA slots; the elastic law has none.
    * Parameters, validation, dxm_set_newton and dxm_stats as for the 6-wide law of the same name.
-   * No per-point parameter fields, no material frame, no external state variable, none of the displacement forms and no fused
-   * displacement gradient (the mesh gradient kernels evaluate 6-wide strains or F), not served by a custom-hardening build.
+   * No per-point parameter fields, no material frame, no external state variable, not served by a custom-hardening build.  The
+   * displacement forms are served on two-dimensional meshes as for DXM_LAW_PS_QUADRATIC, through kind 2 of
+   * dxm_mesh_gradient_device (eps_zz = 0.0 exactly); on any other mesh they are refused.
    * algorithmic_bytes_per_point = 192 (strain 32 in, stress 32 + tangent 128 out) / 272 (+ state 40 in, 40 out) / 272.
    * params = [E, nu] / [E, nu, sig0, H] / [E, nu, sig0, sigu, b] */
   DXM_LAW_PE_ELASTIC_ISO = 26,   /* id 25 is not assigned */
@@ -258,8 +261,8 @@ enum {
    * rtol seq_trial) of dxm_set_newton; both hardening laws iterate.
    * The tangent is one 3x3 block, 9 entries, row-major, exactly symmetric: the consistent (algorithmic) tangent at a yielded point,
    * the plane-stress C = E/(1-nu^2) [[1, nu, 0], [nu, 1, 0], [0, 0, 1-nu]] at an elastic one.  DXM_TANGENT_FULL only.
-   * No per-point parameter fields, no material frame, no external state variable, none of the displacement forms and no fused
-   * displacement gradient (the mesh gradient kernels evaluate 6-wide strains or F), not served by a custom-hardening build.
+   * No per-point parameter fields, no material frame, no external state variable, not served by a custom-hardening build.  The
+   * displacement forms are served on two-dimensional meshes as for DXM_LAW_PS_QUADRATIC (kind 3); on any other mesh they are refused.
    * dxm_stats: n_plastic counts the yielded points; max_local_iters is the largest number of Newton steps a point took before its
    * residual met the bound; n_not_converged counts the points that reached the cap of dxm_set_newton (they write their last
    * iterate); n_nan counts points with a non-finite stress, state or tangent entry (a non-finite strain takes the elastic path and
@@ -279,8 +282,8 @@ enum {
    * step just taken is at most max(rtol, 2^-49) radians (dxm_set_newton).  Every iterate lies on the yield surface by construction.
    * tangent = 0 writes C at every point (the reference's); tangent = 1 writes the algorithmic tangent of a yielded point (exactly
    * symmetric), and C at an elastic one.  9 entries, row-major.  DXM_TANGENT_FULL only; no material frame, no per-point parameter
-   * fields, no external state variable, none of the displacement forms, no fused displacement gradient, not served by a
-   * custom-hardening build.
+   * fields, no external state variable, not served by a custom-hardening build.  The displacement forms are served on
+   * two-dimensional meshes as for DXM_LAW_PS_QUADRATIC (kind 3); on any other mesh they are refused.
    * dxm_stats: n_plastic counts the projected points; max_local_iters is the largest number of steps of the angle a point took;
    * n_not_converged counts the points that reached the cap of dxm_set_newton (they write their last iterate, which is admissible);
    * n_nan counts points with a non-finite stress, state or (tangent = 1) tangent entry (a non-finite trial is not projected).
@@ -653,12 +656,29 @@ dxm_mesh* dxm_mesh_create_tet4(const double* coords, int64_t n_nodes, const int3
 dxm_mesh* dxm_mesh_create_simplex(int tdim, const double* coords, int64_t n_vertices, const int32_t* geom_conn,
                                   int64_t n_cells, const int32_t* dofmap, int nd, int64_t n_dofs,
                                   const double* dphi, int nqp, int device);
+/* Lagrange displacement of any order on triangles (nv = 3) or bilinear quadrilaterals (nv = 4), two components per dof.
+ * Geometry from the nv vertices of a cell through geom_dphi (nqp, nv, 2), the reference derivatives of the geometry's shape
+ * functions at the Gauss points; the field through its own dofmap (n_cells, nd) and dphi (nqp, nd, 2).  Both tables refer to the
+ * same reference coordinates.  coords (n_vertices, 3), third column ignored.  Point c * nqp + q is Gauss point q of cell c.
+ * nd <= 64, nqp <= 64.  Checked on the host, in this order, before a device is asked for: the arguments; every geom_conn and
+ * dofmap entry in range; det J finite, not zero and of one sign within each cell at every Gauss point (the message names the
+ * cell; a bow-tie quadrilateral is refused here).  The mesh answers every kind of dxm_mesh_gradient_device (kinds 0 and 1 embedded
+ * as for triangles above); the displacement forms run its gradient kernel on its own, then the update kernel (no fused form).
+ * A custom-hardening build creates such a mesh but refuses its gradient, and kinds 2 and 3 on any mesh: those kernels are the
+ * stock library's. */
+dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
+                                const int32_t* dofmap, int nd, int64_t n_dofs,
+                                const double* geom_dphi, const double* dphi, int nqp, int device);
 int dxm_mesh_destroy(dxm_mesh* mesh);
 int64_t dxm_mesh_npoints(const dxm_mesh* mesh);
-/* doubles in the displacement vector the mesh expects (3 per node; tdim per dof for dxm_mesh_create_simplex) */
+/* doubles in the displacement vector the mesh expects (3 per node; tdim per dof for dxm_mesh_create_simplex; 2 per dof for
+ * dxm_mesh_create_plane) */
 int64_t dxm_mesh_displacement_size(const dxm_mesh* mesh);
-/* kind 0: Mandel strain (6); kind 1: deformation gradient F = I + grad u (9).  u_dev: device
- * (dxm_mesh_displacement_size doubles); grad_dev: device (npoints, 6|9).  Asynchronous on hip_stream. */
+/* kind 0: Mandel strain (6); kind 1: deformation gradient F = I + grad u (9); on two-dimensional meshes only
+ * (dxm_mesh_create_plane, dxm_mesh_create_simplex with tdim 2; any other mesh refuses them), with H[i][a] = du_i / dX_a and
+ * r = sqrt(2)/2: kind 2 the plane-strain 4-vector [H00, H11, 0.0, r (H01 + H10)] of DXM_LAW_PE_*, kind 3 the in-plane 3-vector
+ * [H00, H11, r (H01 + H10)] of the plane-stress laws.  u_dev: device (dxm_mesh_displacement_size doubles); grad_dev: device
+ * (npoints, 6|9|4|3).  Asynchronous on hip_stream. */
 int dxm_mesh_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, double* grad_dev,
                              void* hip_stream);
 /* dxm_integrate with the gradient computed on the device from the host displacement vector
@@ -675,8 +695,9 @@ int dxm_integrate_displacement_rows(dxm_material* m, dxm_mesh* mesh, const doubl
 /* Device-resident form of dxm_integrate_displacement: u_dev (dxm_mesh_displacement_size doubles), flux_dev, ct_dev are device
  * arrays, the call is asynchronous on hip_stream and capturable like dxm_integrate_device.  For
  * hexahedra with 8 Gauss points per cell, for tetrahedra and for Lagrange simplices the gradient is evaluated inside the
- * update kernel (no strain / deformation-gradient array is written or read); otherwise the gradient kernel fills a scratch
- * array owned by the handle and the update kernel follows on the same stream. */
+ * update kernel (no strain / deformation-gradient array is written or read); otherwise (every law on a plane mesh, the 4-wide
+ * and 3-wide laws on any two-dimensional mesh) the gradient kernel fills a scratch array owned by the handle and the update
+ * kernel follows on the same stream. */
 int dxm_integrate_displacement_device(dxm_material* m, dxm_mesh* mesh, const double* u_dev, double dt,
                                       double* flux_dev, double* ct_dev, void* hip_stream);
 
