@@ -138,6 +138,7 @@ SYMBOLS = {
     "dxm_isv_device": (C.c_int, [_h, C.c_int, C.c_void_p, C.c_void_p]),
     "dxm_state_ptr": (C.c_void_p, [_h, C.c_int, C.c_int, C.c_int]),
     "dxm_clean_tiles": (C.c_int, [_h, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "dxm_packed_state": (C.c_int, [_h, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "dxm_integrate_displacement_device": (C.c_int, [_h, _h, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dxm_expand_tangent_device": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
     "dxm_expand_tangent_pack4_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),

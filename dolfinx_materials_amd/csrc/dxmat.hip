@@ -140,6 +140,7 @@ struct LaunchArgs {
   int tl;                    // tangent layout of THIS launch (the host path may ask for the coefficient form although the
                              // handle's layout is the full block: it rebuilds the block on the host)
   double dt;                 // the time increment of the call: read by the rate-dependent laws only (LawDesc::rate_dependent)
+  bool host_chunk;           // issued by the host-buffer form: kept off the packed copy of s0 (small_strain_clean.hpp)
 };
 
 constexpr unsigned L_FULL = 1u << TL_FULL, L_SYM = 1u << TL_SYM, L_COEF = 1u << TL_COEF, L_PACK4 = 1u << TL_PACK4;
@@ -1202,6 +1203,15 @@ struct dxm_material {
   bool stamps_stale = false;                // the counter wrapped: no stamp is believed until the next eager launch has zeroed them
   bool opt_elide_clean_state = true;
   mutable bool state_exposed = false;       // dxm_state_ptr handed out an address: the plain kernels from then on
+  // packed copy of s0 (the J2 laws; host_side.hpp: PackEpoch): a read-side cache of state[0] for the clean
+  // kernels, allocated by the first launch that builds it (+56 B/point while it exists), dropped at any time without changing a result
+  unsigned long long* pack_mask = nullptr;  // ceil(n / 64) words: bit l = point l of the tile has a slot that is not bit-zero
+  double* pack_buf = nullptr;               // ceil(n / 64) x 7 x 64 doubles: the tile's k kept points, slot c of the r-th at c k + r
+  dxm_host::PackEpoch pack;
+  hipStream_t pack_stream = nullptr;        // where the last launch that wrote or read the copy went
+  bool pack_touched = false;                // ... if there was one
+  bool pack_failed = false;                 // the allocation failed: the handle carries on without (until the option is set again)
+  bool opt_pack_old_state = true;
 };
 
 static int sync_last(dxm_material* m);
@@ -1209,15 +1219,39 @@ static int pf_refresh_elastic(dxm_material* m, hipStream_t st);
 
 // Called BEFORE anything but a clean kernel writes either state buffer (and by whoever learns of a write it could not see): all
 // stamps turn stale at once.  Launches still in flight may go on writing the old value, which is stale too.
-static void bump_clean_stamp(dxm_material* m) {
+// s0_kept: the writer is known to leave state[0] alone (a replayed graph: the update kernel writes s1 only), the packed copy of s0
+// stays; everybody else moves the s0 epoch on with the stamp.
+static void bump_clean_stamp(dxm_material* m, bool s0_kept = false) {
   if (!m->stamps) return;
+  if (!s0_kept) m->pack.move();
   bool wrapped = false;
   m->clean_stamp = dxm_host::next_clean_stamp(m->clean_stamp, &wrapped);
   if (wrapped) m->stamps_stale = true;
 }
 static int64_t stamp_words(const dxm_material* m) { return (m->ld + 63) / 64; }
 
+// the packed copy is given back (no launch may be reading it: the caller has waited, or hipFree does)
+static void free_pack(dxm_material* m) {
+  if (m->pack_mask) { (void)hipFree(m->pack_mask); m->pack_mask = nullptr; }
+  if (m->pack_buf) { (void)hipFree(m->pack_buf); m->pack_buf = nullptr; }
+  m->pack.move();
+  m->pack_touched = false;
+}
+// both arrays, when a launch first builds the copy.  False: no memory for them -- the HIP error is consumed, the handle goes on without
+static bool reserve_pack(dxm_material* m) {
+  if (m->pack_mask && m->pack_buf) return true;
+  const size_t nt = (size_t)((m->n + WAVE - 1) / WAVE);
+  if (hipMalloc(&m->pack_mask, sizeof(unsigned long long) * nt) == hipSuccess &&
+      hipMalloc(&m->pack_buf, sizeof(double) * 7 * WAVE * nt) == hipSuccess)
+    return true;
+  (void)hipGetLastError();
+  free_pack(m);
+  m->pack_failed = true;
+  return false;
+}
+
 static void free_state(dxm_material* m) {
+  free_pack(m);
   if (m->stamps) { (void)hipFree(m->stamps); m->stamps = nullptr; }
   if (!m->state_base) return;
   (void)hipFree(m->state_base);
@@ -1736,6 +1770,7 @@ int dxm_advance(dxm_material* m) {
     m->state[1] = t;
     m->s1_alias = true;
     m->parity ^= 1;   // launches now read / write the other buffer: dxm_launch_generation changes
+    m->pack.move();   // state[0] is the other buffer: a new s0 epoch (the packed copy of the old s0 is not read again)
     // Gradient and flux of the accepted state stay on the device as those of s0 (option keep_initial_io): the buffers the
     // last host-buffer call filled become d_grad0 / d_flux0 and the next call fills the other pair -- no copy.  Without a
     // new state in between (advance twice, advance after revert: s1 is served from s0 and this branch is not entered) s0
@@ -1834,12 +1869,39 @@ static void launch_small_strain(const LaunchArgs& a) {
       f.capturing = capturing;
       f.exposed = m->state_exposed;
       f.stamps_stale = m->stamps_stale;
-      const dxm_host::StateLaunch how = dxm_host::choose_state_launch(f);
+      // the packed copy of s0: none for a handle whose state address is out (and what it held is given back)
+      if (m->state_exposed && (m->pack_buf || m->pack_mask)) free_pack(m);
+      f.pack_option = m->opt_pack_old_state && !m->pack_failed;
+      f.full_range = a.off == 0 && cnt == m->n;
+      f.chunk_of_host_call = a.host_chunk;
+      f.epoch_launches = m->pack.launches;
+      f.built = m->pack.built;
+      f.ordered = !m->pack_touched || st == m->pack_stream || (m->launched && m->last_event_recorded);
+      dxm_host::StateLaunch how = dxm_host::choose_state_launch(f);
 #ifndef DXM_CUSTOM_HARDENING
-      if (how == dxm_host::StateLaunch::clean &&
+      using dxm_host::StateLaunch;
+      if (how == StateLaunch::clean_build || how == StateLaunch::clean_use) {
+        // the arrays on first use; behind the last launch that touched the copy where that one went to another stream
+        bool ok = f.ordered && (how == StateLaunch::clean_use || reserve_pack(m));
+        if (ok && m->pack_touched && st != m->pack_stream && hipStreamWaitEvent(st, m->last_event, 0) != hipSuccess) {
+          (void)hipGetLastError();
+          ok = false;
+        }
+        if (ok && small_strain_packed_launch(how == StateLaunch::clean_build ? 1 : 2, LAW, tl, grid, dyn_lds, st, m->prm, cnt, grad, s0, s1,
+                                             m->ld, flux, ct, bs, m->stamps, m->clean_stamp, m->pack_mask, m->pack_buf)) {
+          m->pack.note(f, how);
+          m->pack_stream = st;
+          m->pack_touched = true;
+          return;
+        }
+        how = StateLaunch::clean;   // no memory, no such instantiation, no way to order it: the kernel without the copy
+      }
+      if (how == StateLaunch::clean &&
           small_strain_clean_launch(LAW, tl, grid, dyn_lds, st, m->prm, cnt, grad, s0, s1, m->ld, flux, ct, bs, m->stamps + a.off / WAVE,
-                                    m->clean_stamp))
+                                    m->clean_stamp)) {
+        m->pack.note(f, how);
         return;
+      }
 #endif
       bump_clean_stamp(m);
     }
@@ -2114,7 +2176,7 @@ static void launch_ps_hosford(const LaunchArgs& a) {
 // tl: tangent layout of THIS launch (LaunchArgs)
 static int launch_range(dxm_material* m, int64_t off, int64_t cnt, const double* grad, double* flux,
                         double* ct, hipStream_t st, int stats_off, int* grid_out,
-                        const MeshSource* fused, int tl) {
+                        const MeshSource* fused, int tl, bool host_chunk = true) {
   if (((uintptr_t)grad | (uintptr_t)flux | (uintptr_t)ct) & 15)
     return fail(-1, "gradient / flux / tangent device arrays must be 16-byte aligned");
   m->io1_valid = 0;   // s1 is being rewritten; a host-buffer call that completes sets it again
@@ -2126,7 +2188,7 @@ static int launch_range(dxm_material* m, int64_t off, int64_t cnt, const double*
   if (!d.launch) return fail(-1, "law %d not launchable", m->law);
   if (fused && d.no_fused) return fail(-1, "%s", d.no_fused);
   if (!(d.launch_layouts & (1u << tl))) return fail(-1, "%s", d.launch_refusal);
-  d.launch(LaunchArgs{m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl, m->dt});
+  d.launch(LaunchArgs{m, grid, st, off, cnt, grad, flux, ct, stats_off, fused, tl, m->dt, host_chunk});
   HIP_TRY(hipGetLastError());
   *grid_out = grid;
   return 0;
@@ -2136,7 +2198,7 @@ static int launch(dxm_material* m, const double* grad, double* flux, double* ct,
                   const MeshSource* fused = nullptr) {
   if (m->n == 0) { m->last_grid = 0; return 0; }
   int grid = 0;
-  if (int rc = launch_range(m, 0, m->n, grad, flux, ct, st, 0, &grid, fused, m->tangent_layout)) return rc;
+  if (int rc = launch_range(m, 0, m->n, grad, flux, ct, st, 0, &grid, fused, m->tangent_layout, false)) return rc;
   m->last_grid = grid;
   m->launched = true;
   m->s1_alias = false;  // the kernel rewrites every slot of s1
@@ -3060,6 +3122,22 @@ int dxm_clean_tiles(dxm_material* m, int64_t* clean, int64_t* tiles) {
   return 0;
 }
 
+int dxm_packed_state(dxm_material* m, int64_t* tiles_packed, int64_t* points_kept) {
+  if (!m || !tiles_packed || !points_kept) return fail(-1, "null argument");
+  *tiles_packed = *points_kept = 0;
+  if (!m->pack.built || !m->pack_mask || !m->opt_pack_old_state || m->state_exposed || m->n == 0) return 0;
+  DEVICE_GUARD(m);
+  if (int rc = sync_last(m)) return rc;
+  const int64_t nt = (m->n + WAVE - 1) / WAVE;
+  std::vector<unsigned long long> host((size_t)nt);
+  if (int rc = download_to_host(host.data(), m->pack_mask, sizeof(unsigned long long) * (size_t)nt, m->own_stream)) return rc;
+  int64_t kept = 0;
+  for (unsigned long long v : host) kept += __builtin_popcountll(v);
+  *tiles_packed = nt;
+  *points_kept = kept;
+  return 0;
+}
+
 const char* dxm_kernel_name(const dxm_material* m) {
   if (!m) return "";
   if (m->frame_kind) return kLaws[m->law].frame_kernel[m->frame_kind - 1];
@@ -3413,7 +3491,7 @@ int dxm_notify_replay(dxm_material* m) {
   m->launched = true;
   m->last_event_recorded = false;   // nothing of the replay is known here: waits fall back to the device
   m->s1_alias = false;              // the replayed kernel rewrote every slot of s1
-  bump_clean_stamp(m);              // ... without maintaining the stamps
+  bump_clean_stamp(m, true);        // ... without maintaining the stamps; it read s0 and left it as it was: the packed copy stays
   return 0;
 }
 
@@ -3458,6 +3536,15 @@ int dxm_set_option(dxm_material* m, const char* name, double value) {
   } else if (k == "elide_clean_state") {
     m->opt_elide_clean_state = on;
     bump_clean_stamp(m);
+  } else if (k == "pack_old_state") {
+    if (!on && (m->pack_buf || m->pack_mask)) {   // off: the copy is given back, behind whatever still reads it
+      DEVICE_GUARD(m);
+      if (int rc = sync_last(m)) return rc;
+      free_pack(m);
+    }
+    m->opt_pack_old_state = on;
+    m->pack_failed = false;
+    m->pack.move();
   } else {
     return fail(-1, "unknown option '%s'", name);
   }

@@ -349,7 +349,15 @@ inline int launch_grid(int64_t cnt, int num_cu, int blocks_per_cu) {
 // The invariant: stamps[t] == clean_stamp  =>  tile t (64 points) holds the same bytes in both state buffers.
 // Only the clean kernels (small_strain_clean.hip) maintain it.  Every other launch rewrites s1 without looking at the stamps, so it
 // makes all of them stale first: the handle's clean_stamp moves on (plain_bump).  A handle without stamps has nothing to maintain.
-enum class StateLaunch { clean, plain, plain_bump };
+//
+// The packed copy of s0 ("Packed old state"): a read-side cache that only the clean kernels use, valid for one
+// s0 EPOCH -- the time during which nothing may have changed the contents of state[0].  Within an epoch the first launch that could
+// use a copy runs today's kernel (a load step that converges in one update never pays for a copy), the second one builds the copy
+// beside its own work (clean_build), the later ones read it instead of s0 (clean_use).  The invariant:
+//     built  =>  the copy was made from the bytes state[0] holds now, by a launch of this epoch.
+// PackEpoch below is the handle's record of it; every event that may change state[0], and every launch that is not one of the three
+// clean forms, moves the epoch on.
+enum class StateLaunch { clean, plain, plain_bump, clean_build, clean_use };
 struct StateLaunchFlags {
   bool has_stamps;     // a J2 law with its stamps allocated (LAW_J2_LINEAR / LAW_J2_VOCE in a stock build)
   bool option;         // option elide_clean_state
@@ -361,12 +369,41 @@ struct StateLaunchFlags {
   bool capturing;      // the stream is being captured: the launch may run any number of times later, unseen
   bool exposed;        // dxm_state_ptr has handed out a state address: writes through it are unseen
   bool stamps_stale;   // the stamp counter wrapped and the stamps have not been zeroed since
+  // the packed copy of s0 (all false / 0: the rule as it was before the copy existed)
+  bool pack_option;    // option pack_old_state, and the handle has not given the copy up (dxm_state_ptr, a failed allocation)
+  bool full_range;     // the launch covers every point of the handle
+  bool chunk_of_host_call;   // issued by the host-buffer form (one of its chunks, or its only one)
+  int epoch_launches;  // launches of this s0 epoch so far that passed every test above (PackEpoch::launches)
+  bool built;          // a build launch of this epoch has been issued (PackEpoch::built)
+  bool ordered;        // this launch runs behind that build launch: the same stream, or a wait for the handle's event was queued
 };
 inline StateLaunch choose_state_launch(const StateLaunchFlags& f) {
   if (!f.has_stamps) return StateLaunch::plain;
-  if (f.option && !f.fields && !f.frame && !f.fused && f.whole_tiles && !f.capturing && !f.exposed && !f.stamps_stale) return StateLaunch::clean;
+  if (f.option && !f.fields && !f.frame && !f.fused && f.whole_tiles && !f.capturing && !f.exposed && !f.stamps_stale) {
+    if (!f.pack_option || !f.full_range || f.chunk_of_host_call) return StateLaunch::clean;
+    if (f.built) return f.ordered ? StateLaunch::clean_use : StateLaunch::clean;
+    return f.epoch_launches >= 1 ? StateLaunch::clean_build : StateLaunch::clean;
+  }
   return StateLaunch::plain_bump;
 }
+// whether a launch counts towards the copy: what choose_state_launch tests before it looks at the epoch
+inline bool pack_candidate(const StateLaunchFlags& f, StateLaunch how) {
+  return (how == StateLaunch::clean || how == StateLaunch::clean_build || how == StateLaunch::clean_use) && f.pack_option && f.full_range &&
+         !f.chunk_of_host_call;
+}
+// The handle's record of the s0 epoch.  move(): state[0] may hold other bytes from now on (advance's swap, dxm_set_state, every
+// site that moves the clean stamp because it writes a state buffer).  note(): a launch was issued as `how`.
+struct PackEpoch {
+  int launches = 0;      // candidate launches of this epoch, saturating
+  bool built = false;
+  void move() { launches = 0; built = false; }
+  void note(const StateLaunchFlags& f, StateLaunch how) {
+    if (how == StateLaunch::plain_bump) { move(); return; }   // (the stamp moved: the same event)
+    if (!pack_candidate(f, how)) return;
+    if (how == StateLaunch::clean_build) built = true;
+    if (launches < 3) ++launches;
+  }
+};
 inline bool covers_whole_tiles(int64_t off, int64_t cnt, int64_t npoints) { return off % 64 == 0 && (cnt % 64 == 0 || off + cnt == npoints); }
 // the stamp after `s`: never 0 (what a tile that yielded is marked with); *wrapped: every stamp value has been used once, the
 // stamps must be zeroed before one of them is believed again

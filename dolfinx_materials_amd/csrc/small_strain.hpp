@@ -215,6 +215,9 @@ small_strain_kernel(const LawParams prm, const int64_t n, const double* __restri
   constexpr bool CLEAN = false;
   constexpr uint32_t* stamps = nullptr;   // (small_strain_clean.hip: named by the discarded CLEAN blocks of the body only)
   constexpr uint32_t stamp = 0;
+  constexpr int PACKED = 0;               // (small_strain_packed.hip: named by the discarded PACKED blocks of the body only)
+  constexpr unsigned long long* pack_mask = nullptr;
+  constexpr double* pack_buf = nullptr;
 #include "small_strain_body.hpp"
 }
 
@@ -231,6 +234,9 @@ small_strain_field_kernel(const LawParams prm, const ParamStreams pf, const int6
   constexpr bool CLEAN = false;
   constexpr uint32_t* stamps = nullptr;
   constexpr uint32_t stamp = 0;
+  constexpr int PACKED = 0;               // (small_strain_packed.hip: named by the discarded PACKED blocks of the body only)
+  constexpr unsigned long long* pack_mask = nullptr;
+  constexpr double* pack_buf = nullptr;
 #include "small_strain_body.hpp"
 }
 

@@ -3,6 +3,9 @@
 //   constexpr bool FIELDS    and    pf (ParamStreams: the kernel's argument, or an all-null constant that only discarded code names)
 //   constexpr bool CLEAN     and    stamps, stamp (small_strain_clean.hip: the per-tile stamps of the handle and the value that means
 //                                   "this tile's bytes are the same in both state buffers"; null constants elsewhere, as for pf)
+//   constexpr int PACKED     and    pack_mask, pack_buf (small_strain_packed.hip: the packed copy of s0, one 64-bit mask per tile and the
+//                                   non-zero points' slots at the tile's pitch of 7 x 64 doubles; 0 the old state comes from s0, 1 it
+//                                   does and the copy is built from it, 2 it comes from the copy; 0 and null constants elsewhere)
 // beside the common arguments (prm, n, eps, s0, s1, ld, sig, ct, stats, src) and template parameters (LAW, TL, GRAD).  Shared as
 // text and not through a function: see the comment at the top of small_strain.hpp.
   __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * SS_LDS_PER_WAVE];
@@ -45,7 +48,25 @@
       // ---- 1. coalesced strain load (3 x 1 KiB per wave) into LDS ------------------------------
 #include "tile_rows6_load.hpp"
       // ---- old state, SoA (issued before the LDS round trip completes) -------------------------
-      if constexpr (ss_has_state<LAW>) {
+      if constexpr (ss_has_state<LAW> && PACKED == 2) {
+        // PACKED use: the tile's mask says which points hold a slot that is not bit-zero (one word per wave, made scalar like the
+        // stamp); those k points read their seven slots from the packed copy, slot c of the r-th of them at c k + r of the tile's
+        // pitch, the others keep zeros.  A tile of never-yielded points (k = 0) issues no state load.
+        const unsigned long long mv = pack_mask[tile];
+        // (the builtin returns an int: through unsigned, or bit 31 of the low word would fill the high one)
+        const unsigned long long msk = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(mv >> 32)) << 32) |
+                                       (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)mv);
+        if (msk != 0ull) {
+          if ((msk >> lane) & 1ull) {
+            const int k = __popcll(msk);
+            const double* q = pack_buf + tile * (int64_t)(7 * WAVE) +
+                              __builtin_amdgcn_mbcnt_hi((unsigned)(msk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)msk, 0u));
+            p_n = stream_load<3>(q);
+#pragma unroll
+            for (int c = 0; c < 6; ++c) ep[c] = stream_load<3>(q + (1 + c) * k);
+          }
+        }
+      } else if constexpr (ss_has_state<LAW>) {
         if (valid) {
           p_n = stream_load<3>(s0 + gi);
 #pragma unroll
@@ -58,6 +79,23 @@
       // ---- 2. my point's strain ----------------------------------------------------------------
 #include "tile_rows6_take.hpp"
       wave_lds_sync();  // staging region is reused for the stress below
+      if constexpr (ss_has_state<LAW> && PACKED == 1) {
+        // PACKED build: the copy the use form reads, made of what was just loaded (here, where the update waits for the old state
+        // anyway).  A test on the bits: -0.0 and NaN are kept and come back as they are; a lane past the end holds zeros.
+        unsigned long long bits = (unsigned long long)__double_as_longlong(p_n);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) bits |= (unsigned long long)__double_as_longlong(ep[c]);
+        const unsigned long long msk = __ballot(bits != 0ull);
+        if (bits != 0ull) {
+          const int k = __popcll(msk);
+          double* q = pack_buf + tile * (int64_t)(7 * WAVE) +
+                      __builtin_amdgcn_mbcnt_hi((unsigned)(msk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)msk, 0u));
+          stream_store<1>(q, p_n);
+#pragma unroll
+          for (int c = 0; c < 6; ++c) stream_store<1>(q + (1 + c) * k, ep[c]);
+        }
+        if (lane == 0) pack_mask[tile] = msk;
+      }
     } else {
       double Hd[9];
       if constexpr (GRAD == 1) {

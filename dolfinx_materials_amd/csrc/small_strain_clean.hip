@@ -17,6 +17,9 @@ small_strain_clean_kernel(const LawParams prm, const int64_t n, const double* __
   constexpr bool FIELDS = false;
   constexpr ParamStreams pf = {};
   constexpr bool CLEAN = true;
+  constexpr int PACKED = 0;
+  constexpr unsigned long long* pack_mask = nullptr;   // named by the discarded PACKED blocks of the body only
+  constexpr double* pack_buf = nullptr;
   MeshSource src{};   // named by the discarded GRAD != 0 blocks of the body only (not const: they divide by a member of it)
 #include "small_strain_body.hpp"
 }

@@ -1207,8 +1207,10 @@ class HIPMaterial:
     def set_option(self, name, value):
         """Per-handle options of ``include/dxmat.h`` (``"pipeline"``, ``"split_streams"``, ``"packed_transfer"``, ``"packed_min_points"``,
         ``"register_input"``, ``"stage_ahead"``, ``"keep_initial_io"``, ``"pageable_dma"``, ``"host_threads"``, ``"max_chunks"``,
-        ``"fused_gradient"``, ``"blocks_per_cu"``, ``"verbose"``; process-wide:
-        ``"query_foreign_pointers"``)."""
+        ``"fused_gradient"``, ``"blocks_per_cu"``, ``"elide_clean_state"``, ``"pack_old_state"``, ``"verbose"``; process-wide:
+        ``"query_foreign_pointers"``).  ``"pack_old_state"`` (the J2 laws, device-pointer form): from the third update of a load step
+        on, the kernel reads the old state from a packed copy that leaves out the points whose state is all zeros; same bits, +56
+        B/point of device memory while the copy exists, 0 frees it."""
         for h in self._handles():
             self._chk(self._lib.dxm_set_option(h, name.encode(), float(value)))
 

@@ -511,6 +511,12 @@ const double* dxm_state_ptr(const dxm_material* m, int which, int field, int com
  * how many (*tiles = ceil(npoints / 64)); a launch with option "elide_clean_state" skips the state store of such a tile while no point
  * of it yields.  Waits for the last launch.  Other laws (and a custom-hardening build) report 0 of 0.  Returns 0 or < 0. */
 int dxm_clean_tiles(dxm_material* m, int64_t* clean, int64_t* tiles);
+/* The J2 laws: the packed copy of s0 that option "pack_old_state" keeps for the update kernel.  While a valid copy exists -- a launch
+ * of the present load step has built it, and nothing may have changed s0 since -- *tiles_packed = ceil(npoints / 64), the tiles it
+ * covers, and *points_kept the points held in it: those with a slot of s0 that is not bit-zero.  0 and 0 when there is no valid copy
+ * (none built yet since the last dxm_advance / dxm_set_state / plain launch, option off, a state address handed out, other laws).
+ * Waits for the last launch.  Returns 0 or < 0. */
+int dxm_packed_state(dxm_material* m, int64_t* tiles_packed, int64_t* points_kept);
 /* Rebuild full tangents from their coefficient form on the device: coef_dev (npoints, 9) as written with
  * DXM_TANGENT_COEF -> ct_dev (npoints, 36), the block DXM_TANGENT_FULL writes, bit for bit; asynchronous on
  * hip_stream of `device`.  For consumers that move the 72 B/point form (e.g. across xGMI: an all-gather of
@@ -586,6 +592,15 @@ int dxm_notify_replay(dxm_material* m);
  *                            such a tile.  Results and both state buffers are bit for bit those of 0.  Launches captured into a
  *                            HIP graph, launches with parameter fields or a fused gradient, and every launch after dxm_state_ptr
  *                            use the kernel of 0; a replayed graph must be reported with dxm_notify_replay as before
+ *   "pack_old_state" 1 | 0   the J2 laws, where "elide_clean_state" applies and the launch covers all points of the handle (device-
+ *                            pointer form): s0 does not change between the updates of one load step, and a point that has never
+ *                            yielded holds seven zeros there.  With 1 the second such launch since s0 last changed also writes a
+ *                            packed copy of s0 -- per 64-point tile one 64-bit mask and the slots of the points that are not all
+ *                            bit-zero -- and the later ones read that copy instead of s0: 56 B less per never-yielded point.
+ *                            Results and both state buffers are bit for bit those of 0.  The copy costs +56 B/point of device memory
+ *                            from its first build on (without it if that allocation fails); dxm_advance, dxm_set_state, a launch
+ *                            of another form and dxm_state_ptr (for good) end its validity, dxm_revert and dxm_notify_replay do
+ *                            not; 0 frees it (default 1; dxm_packed_state reports)
  *   "verbose"        0 | 1   host-buffer form: log the chunk timeline, page-locking and upload-mode decisions to stderr (default 0) */
 int dxm_set_option(dxm_material* m, const char* name, double value);
 /* get_initial_state_dict / get_final_state_dict without a device array of the caller: packs the
