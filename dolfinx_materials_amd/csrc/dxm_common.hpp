@@ -147,6 +147,9 @@ typedef double double2_t __attribute__((ext_vector_type(2)));
 // tensor indices (SI[I], SJ[I]) of component I of a symmetric 6-vector [11, 22, 33, 12, 13, 23] (the Mandel and the DXM_SYM order)
 constexpr int SI[6] = {0, 1, 2, 0, 0, 1}, SJ[6] = {0, 1, 2, 1, 2, 2};
 
+// column of a row-major 3 x 3 -> slot of the symmetric record the plane-stress kernels stage per point: 0 1 2 / 1 3 4 / 2 4 5
+constexpr int sym3_slot(int col) { return col < 3 ? col : (col < 6 ? (col == 3 ? 1 : col - 1) : (col == 6 ? 2 : col - 3)); }
+
 // A general symmetric 6x6 tangent is staged per point as the 21 entries of its upper triangle, row by row (hosford.hip,
 // orthotropic.hip, written out by tile_tri21_store.hpp; hyperelastic.hip keeps its CC in registers in the same order)
 constexpr int TRI21 = 21;

@@ -2047,17 +2047,20 @@ static void launch_heat_phase_change(const LaunchArgs& a) {
                        m->state[1] + a.off, a.flux, a.ct, m->d_stats + a.stats_off);
 }
 
-// the constants both plane-stress kernels read: the stiffness as cvxpy_materials.py:16-18 forms it
-static void ps_elastic_constants(PsParams& q, double E, double nu) {
+// the plane-stress stiffness as cvxpy_materials.py:16-18 forms it, and its eigenvalues: what every plane-stress launcher puts into
+// its kernel's record, each entry one or two individually rounded operations
+struct PsStiffness { double c11, c12, c33, CA, CB; };   // CA = E/(1-nu), CB = E/(1+nu)
+static PsStiffness ps_stiffness(double E, double nu) {
 #pragma clang fp contract(off)
   const double c0 = E / (1.0 - nu * nu);
-  q.p[PS_C11] = c0;
-  q.p[PS_C12] = c0 * nu;
-  q.p[PS_C33] = c0 * (1.0 - nu);
-  q.p[PS_E] = E;
-  q.p[PS_NU] = nu;
-  q.p[PS_CA] = E / (1.0 - nu);
-  q.p[PS_CB] = E / (1.0 + nu);
+  return {c0, c0 * nu, c0 * (1.0 - nu), E / (1.0 - nu), E / (1.0 + nu)};
+}
+// the constants both plane-stress kernels read
+static void ps_elastic_constants(PsParams& q, double E, double nu) {
+  const PsStiffness k = ps_stiffness(E, nu);
+  q.p[PS_C11] = k.c11; q.p[PS_C12] = k.c12; q.p[PS_C33] = k.c33;
+  q.p[PS_E] = E; q.p[PS_NU] = nu;
+  q.p[PS_CA] = k.CA; q.p[PS_CB] = k.CB;
 }
 
 static void launch_ps_quadratic(const LaunchArgs& a) {
@@ -2127,15 +2130,11 @@ template <int LAW> static void launch_plane_strain(const LaunchArgs& a) {
 template <int HARD> static void launch_plane_stress_j2(const LaunchArgs& a) {
 #pragma clang fp contract(off)
   dxm_material* m = a.m;
-  const double E = m->raw_params[0], nu = m->raw_params[1];
+  const PsStiffness k = ps_stiffness(m->raw_params[0], m->raw_params[1]);
   PsJ2Params q{};
   q.law = m->prm;
-  const double c0 = E / (1.0 - nu * nu);
-  q.c11 = c0;
-  q.c12 = c0 * nu;
-  q.c33 = c0 * (1.0 - nu);
-  q.CA = E / (1.0 - nu);
-  q.CB = E / (1.0 + nu);
+  q.c11 = k.c11; q.c12 = k.c12; q.c33 = k.c33;
+  q.CA = k.CA; q.CB = k.CB;
   q.ka = q.CA / 3.0;
   q.kmax = fmax(q.ka, q.CB);
   q.kmin = fmin(q.ka, q.CB);
@@ -2148,22 +2147,19 @@ static void launch_ps_hosford(const LaunchArgs& a) {
   dxm_material* m = a.m;
   const double* p = m->raw_params.data();   // [E, nu, sig0, a, tangent] (build_ps_hosford)
   const double E = p[0], nu = p[1];
+  const PsStiffness k = ps_stiffness(E, nu);
   PshParams q{};
-  const double c0 = E / (1.0 - nu * nu);
-  q.p[PSH_C11] = c0;
-  q.p[PSH_C12] = c0 * nu;
-  q.p[PSH_C33] = c0 * (1.0 - nu);
-  q.p[PSH_E] = E;
-  q.p[PSH_NU] = nu;
-  q.p[PSH_SQA] = sqrt(E / (1.0 - nu));
-  q.p[PSH_SQB] = sqrt(E / (1.0 + nu));
+  q.p[PSH_C11] = k.c11; q.p[PSH_C12] = k.c12; q.p[PSH_C33] = k.c33;
+  q.p[PSH_E] = E; q.p[PSH_NU] = nu;
+  q.p[PSH_SQA] = sqrt(k.CA);   // sqrt(E / (1 - nu)), sqrt(E / (1 + nu)): the quotient rounded, then the root
+  q.p[PSH_SQB] = sqrt(k.CB);
   q.p[PSH_SIG0] = p[2];
   q.p[PSH_A] = p[3];
   q.p[PSH_AM1] = p[3] - 1.0;
   q.p[PSH_AM2] = p[3] - 2.0;
   q.p[PSH_INVA] = 1.0 / p[3];
   q.p[PSH_TOL] = m->prm.tol;
-  q.p[PSH_CB] = E / (1.0 + nu);
+  q.p[PSH_CB] = k.CB;
   constexpr double eps4 = 4.0 * 2.220446049250313e-16;
   q.p[PSH_KLO] = pow(0.5, q.p[PSH_INVA]) * (1.0 - eps4);
   q.p[PSH_KHI] = pow(1.5, q.p[PSH_INVA]) * (1.0 + eps4);

@@ -13,12 +13,11 @@
 // Mapping: one thread per point, one wave per tile of 64 points, 256-thread workgroups, grid-stride over the
 // tiles; the lanes of a wave exchange through a wave-private LDS region ordered by wave_lds_sync(), no workgroup barrier inside the
 // tile loop; one BlockStats record per workgroup.
-// Memory: a tile's gradient and flux rows of 3 are 1536 contiguous bytes, moved as 96 accesses of 16 B over the lanes and
-// redistributed through LDS; T and the enthalpy are 8 B per lane.  The tangent is never held per thread: each point stages
-// (-k, dj/dT[0..2], c) in LDS and the wave writes the 12 / 13 numbers per point in output order as 16 B-per-lane non-temporal
-// stores.  A tile's tangent is 6144 / 6656 B and starts on a multiple of 512 B, so every 128 B line is written whole; the six
-// structural zeros of -k I are written (the layout is the reference's jacobian_flatten).  A ragged last tile is bounded by lane:
-// nothing is read or written past the launch's points.
+// Memory: a tile's gradient and flux rows of 3 move through LDS by tile_rows3_load.hpp / tile_rows3_store.hpp; T and the enthalpy
+// are 8 B per lane.  The tangent is never held per thread: each point stages (-k, dj/dT[0..2], c) in LDS and tile_entries_store.hpp
+// writes the 12 / 13 numbers per point in output order.  A tile's tangent is 6144 / 6656 B and starts on a multiple of 512 B, so
+// every 128 B line is written whole; the six structural zeros of -k I are written (the layout is the reference's jacobian_flatten).
+// A ragged last tile is bounded by lane in those three texts.
 #include "heat_transfer.hpp"
 
 namespace dxm {
@@ -51,21 +50,8 @@ heat_transfer_kernel(const HeatParams prm, const int64_t n, const double* __rest
     const bool valid = lane < npts;
     const int64_t gi = base + lane;
 
-    // ---- 1. the tile's gradient rows: 96 x 16 B, coalesced, into LDS (zeros beyond the last point) ----------------------
-    {
-      const double* g0 = grad + base * 3;
-      const int nd = npts * 3;
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < WAVE * 3 / 2) {
-          double2_t v = {0.0, 0.0};
-          if (2 * q + 1 < nd) v = stream_load<2>(reinterpret_cast<const double2_t*>(g0) + q);
-          else if (2 * q < nd) v.x = stream_load<2>(g0 + 2 * q);
-          stage2[q] = v;
-        }
-      }
-    }
+    // ---- 1. the tile's gradient rows into LDS; the temperature ------------------------------------------------------------
+#include "tile_rows3_load.hpp"
     double T = t_uniform;
     if constexpr (TFIELD) {
       if (valid) T = stream_load<3>(tfield + gi);
@@ -117,39 +103,14 @@ heat_transfer_kernel(const HeatParams prm, const int64_t n, const double* __rest
     wave_lds_sync();
 
     // ---- 3. the flux rows, as they came in -------------------------------------------------------------------------------
-    {
-      double* f0 = flux + base * 3;
-      const int nd = npts * 3;
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < WAVE * 3 / 2) {
-          const double2_t v = stage2[q];
-          if (2 * q + 1 < nd) stream_store<0>(reinterpret_cast<double2_t*>(f0) + q, v);
-          else if (2 * q < nd) stream_store<0>(f0 + 2 * q, v.x);
-        }
-      }
-    }
+#include "tile_rows3_store.hpp"
     // ---- 4. the tangent in output order: entry e of the tile belongs to point e / W, column e % W ------------------------
-    {
-      double* c0 = ct + base * W;
-      const int nd = npts * W;
-      auto entry = [&](int e) -> double {
-        const int p = e / W, col = e - p * W;
-        const double raw = rec[p * HT_REC + (col < 9 ? 0 : col - 8)];
-        return col < 9 ? ((col & 3) == 0 ? raw : 0.0) : raw;
-      };
-      constexpr int NQ = WAVE * W / 2;
-#pragma unroll
-      for (int pass = 0; pass < (NQ + WAVE - 1) / WAVE; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < NQ && 2 * q < nd) {
-          const double2_t v = {entry(2 * q), entry(2 * q + 1)};
-          if (2 * q + 1 < nd) stream_store<0>(reinterpret_cast<double2_t*>(c0) + q, v);
-          else stream_store<0>(c0 + 2 * q, v.x);
-        }
-      }
-    }
+    auto entry = [&](int e) -> double {
+      const int p = e / W, col = e - p * W;
+      const double raw = rec[p * HT_REC + (col < 9 ? 0 : col - 8)];
+      return col < 9 ? ((col & 3) == 0 ? raw : 0.0) : raw;
+    };
+#include "tile_entries_store.hpp"
     wave_lds_sync();   // the LDS region is rewritten by the next tile
   }
 

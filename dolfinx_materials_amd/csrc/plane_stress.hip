@@ -17,11 +17,10 @@
 //
 // Mapping and memory as heat_transfer.hip: one thread per point, one wave per tile of 64 points, 256-thread workgroups, grid-stride
 // over the tiles, wave-private LDS ordered by wave_lds_sync(), one BlockStats record per workgroup.  A tile's strain and stress
-// rows of 3 are 1536 contiguous bytes, moved as 96 accesses of 16 B over the lanes and redistributed through LDS; the plastic
-// strain is three 8 B-per-lane SoA streams.  The 9-wide tangent is never held per thread: it is written in output order as
-// 16 B-per-lane non-temporal stores (a tile's is 4608 B and starts on a multiple of 512 B: every 128 B line is written whole);
-// with tangent = 0 an entry depends on its column only, with tangent = 1 each point stages its six distinct numbers in LDS.  A
-// ragged last tile is bounded by lane: nothing is read or written past the launch's points.
+// rows of 3 move through LDS by tile_rows3_load.hpp / tile_rows3_store.hpp; the plastic strain is three 8 B-per-lane SoA streams.
+// The 9-wide tangent is never held per thread: tile_entries_store.hpp writes it in output order (a tile's is 4608 B and starts on
+// a multiple of 512 B: every 128 B line is written whole); with tangent = 0 an entry depends on its column only, with tangent = 1
+// each point stages its six distinct numbers in LDS.  A ragged last tile is bounded by lane in those three texts.
 #include "plane_stress.hpp"
 
 namespace dxm {
@@ -33,10 +32,11 @@ plane_stress_kernel(const PsParams prm, const int64_t n, const double* __restric
                     BlockStats* __restrict__ stats) {
 #pragma clang fp contract(off)
   static_assert(SURFACE == PS_QUADRATIC || TANGENT == 0, "the polygonal law writes the elastic tangent only");
+  constexpr int W = 9;   // tangent entries per point: the row-major 3 x 3
   __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * PS_LDS_PER_WAVE];
   __shared__ unsigned long long red[4 * WAVES_PER_BLOCK];
   static_assert(PS_LDS_BYTES == sizeof(lds_all) + sizeof(red), "plane_stress.hpp states the LDS of the kernel");
-  static_assert((WAVE * 3) % 2 == 0 && (WAVE * 9) % 2 == 0 && (PS_LDS_PER_WAVE * 8) % 16 == 0, "16 B accesses of whole tiles");
+  static_assert((WAVE * 3) % 2 == 0 && (WAVE * W) % 2 == 0 && (PS_LDS_PER_WAVE * 8) % 16 == 0, "16 B accesses of whole tiles");
 
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x >> 6;
@@ -56,21 +56,8 @@ plane_stress_kernel(const PsParams prm, const int64_t n, const double* __restric
     const bool valid = lane < npts;
     const int64_t gi = base + lane;
 
-    // ---- 1. the tile's strain rows: 96 x 16 B, coalesced, into LDS (zeros beyond the last point); the plastic strain ----------
-    {
-      const double* g0 = grad + base * 3;
-      const int nd = npts * 3;
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < WAVE * 3 / 2) {
-          double2_t v = {0.0, 0.0};
-          if (2 * q + 1 < nd) v = stream_load<2>(reinterpret_cast<const double2_t*>(g0) + q);
-          else if (2 * q < nd) v.x = stream_load<2>(g0 + 2 * q);
-          stage2[q] = v;
-        }
-      }
-    }
+    // ---- 1. the tile's strain rows into LDS; the plastic strain ------------------------------------------------------------------
+#include "tile_rows3_load.hpp"
     double epn[3] = {0.0, 0.0, 0.0};
     if (valid) {
 #pragma unroll
@@ -219,44 +206,17 @@ plane_stress_kernel(const PsParams prm, const int64_t n, const double* __restric
     wave_lds_sync();
 
     // ---- 3. the stress rows, as the strain came in ---------------------------------------------------------------------------
-    {
-      double* f0 = flux + base * 3;
-      const int nd = npts * 3;
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < WAVE * 3 / 2) {
-          const double2_t v = stage2[q];
-          if (2 * q + 1 < nd) stream_store<0>(reinterpret_cast<double2_t*>(f0) + q, v);
-          else if (2 * q < nd) stream_store<0>(f0 + 2 * q, v.x);
-        }
-      }
-    }
+#include "tile_rows3_store.hpp"
     // ---- 4. the tangent in output order: entry e of the tile belongs to point e / 9, column e % 9 of the row-major 3 x 3 ----
-    {
-      double* c0 = ct + base * 9;
-      const int nd = npts * 9;
-      auto entry = [&](int e) -> double {
-        const int p = e / 9, col = e - p * 9;
-        if constexpr (TANGENT) {
-          // (row, column) -> slot of the symmetric record: 0 1 2 / 1 3 4 / 2 4 5
-          const int slot = col < 3 ? col : (col < 6 ? (col == 3 ? 1 : col - 1) : (col == 6 ? 2 : col - 3));
-          return rec[p * PS_REC + slot];
-        } else {
-          return (col == 0 || col == 4) ? c11 : ((col == 1 || col == 3) ? c12 : (col == 8 ? c33 : 0.0));
-        }
-      };
-      constexpr int NQ = WAVE * 9 / 2;
-#pragma unroll
-      for (int pass = 0; pass < (NQ + WAVE - 1) / WAVE; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < NQ && 2 * q < nd) {
-          const double2_t v = {entry(2 * q), entry(2 * q + 1)};
-          if (2 * q + 1 < nd) stream_store<0>(reinterpret_cast<double2_t*>(c0) + q, v);
-          else stream_store<0>(c0 + 2 * q, v.x);
-        }
+    auto entry = [&](int e) -> double {
+      const int p = e / W, col = e - p * W;
+      if constexpr (TANGENT) {
+        return rec[p * PS_REC + sym3_slot(col)];
+      } else {
+        return (col == 0 || col == 4) ? c11 : ((col == 1 || col == 3) ? c12 : (col == 8 ? c33 : 0.0));
       }
-    }
+    };
+#include "tile_entries_store.hpp"
     wave_lds_sync();   // the LDS region is rewritten by the next tile
   }
 

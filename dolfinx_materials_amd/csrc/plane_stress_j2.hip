@@ -27,7 +27,7 @@
 //   end: |g| <= max(tol, rtol seq_tr), the tolerance of the 6-wide laws (dxm_set_newton); the step computed from that last residual
 //     is still taken, unsafeguarded.  A point at the cap is counted and writes its last iterate.
 // eps_p = eps - C^-1 s at a yielded point.  Tangent, with A = diag(C_i / (1 + dg k_i)), n = 3/2 P s, theta = 1 - 2/3 R' dg:
-//   D = A - (A n)(A n)^T / (n^T A n + R' seq^2 / theta),   R' = 0: lines 121-127 of plane_stress.hip with q = 3/2
+//   D = A - (A n)(A n)^T / (n^T A n + R' seq^2 / theta),   R' = 0: the TANGENT block of plane_stress.hip with q = 3/2
 // rotated back from the basis; the plane-stress C at an elastic point.  Six distinct numbers: the block is exactly symmetric.
 // A non-finite strain takes the elastic path (no comparison with NaN holds), keeps its state bits and counts once in n_nan.
 //
@@ -36,11 +36,10 @@
 //
 // Mapping and memory as plane_stress.hip: one thread per point, one wave per tile of 64 points, 256-thread workgroups, grid-stride
 // over the tiles, wave-private LDS ordered by wave_lds_sync() (no workgroup barrier in the tile loop), one BlockStats record per
-// workgroup.  A tile's strain and stress rows of 3 are 1536 contiguous bytes, moved as 96 accesses of 16 B over the lanes and
-// redistributed through LDS; the state is four 8 B-per-lane SoA streams in and out (an elastic point writes back the bits it read).
-// The 9-wide tangent is never held per thread: each point stages its six distinct numbers in LDS and the wave writes the tile's
-// 4608 B in output order as 16 B-per-lane non-temporal stores (a tile starts on a multiple of 512 B: every 128 B line is written
-// whole).  A ragged last tile is bounded by lane: nothing is read or written past the launch's points.
+// workgroup.  A tile's strain and stress rows of 3 move through LDS by tile_rows3_load.hpp / tile_rows3_store.hpp; the state is four
+// 8 B-per-lane SoA streams in and out (an elastic point writes back the bits it read).  The 9-wide tangent is never held per thread:
+// each point stages its six distinct numbers in LDS and tile_entries_store.hpp writes the tile's 4608 B in output order (a tile
+// starts on a multiple of 512 B: every 128 B line is written whole).  A ragged last tile is bounded by lane in those three texts.
 // 184 B/point: strain 24 + state 32 in, stress 24 + tangent 72 + state 32 out.
 #include "plane_stress_j2.hpp"
 
@@ -57,10 +56,11 @@ plane_stress_j2_kernel(const PsJ2Params prm, const int64_t n, const double* __re
                        double* __restrict__ s1, const int64_t ld, double* __restrict__ flux, double* __restrict__ ct,
                        BlockStats* __restrict__ stats) {
 #pragma clang fp contract(off)
+  constexpr int W = 9;   // tangent entries per point: the row-major 3 x 3
   __shared__ __attribute__((aligned(16))) double lds_all[WAVES_PER_BLOCK * PSJ_LDS_PER_WAVE];
   __shared__ unsigned long long red[4 * WAVES_PER_BLOCK];
   static_assert(PSJ_LDS_BYTES == sizeof(lds_all) + sizeof(red), "plane_stress_j2.hpp states the LDS of the kernel");
-  static_assert((WAVE * 3) % 2 == 0 && (WAVE * 9) % 2 == 0 && (PSJ_LDS_PER_WAVE * 8) % 16 == 0, "16 B accesses of whole tiles");
+  static_assert((WAVE * 3) % 2 == 0 && (WAVE * W) % 2 == 0 && (PSJ_LDS_PER_WAVE * 8) % 16 == 0, "16 B accesses of whole tiles");
 
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x >> 6;
@@ -81,21 +81,8 @@ plane_stress_j2_kernel(const PsJ2Params prm, const int64_t n, const double* __re
     const bool valid = lane < npts;
     const int64_t gi = base + lane;
 
-    // ---- 1. the tile's strain rows: 96 x 16 B, coalesced, into LDS (zeros beyond the last point); the old state ---------------
-    {
-      const double* g0 = grad + base * 3;
-      const int nd = npts * 3;
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < WAVE * 3 / 2) {
-          double2_t v = {0.0, 0.0};
-          if (2 * q + 1 < nd) v = stream_load<2>(reinterpret_cast<const double2_t*>(g0) + q);
-          else if (2 * q < nd) v.x = stream_load<2>(g0 + 2 * q);
-          stage2[q] = v;
-        }
-      }
-    }
+    // ---- 1. the tile's strain rows into LDS; the old state -------------------------------------------------------------------------
+#include "tile_rows3_load.hpp"
     double p_n = 0.0, epn[3] = {0.0, 0.0, 0.0};
     if (valid) {
       p_n = stream_load<3>(s0 + gi);
@@ -221,40 +208,13 @@ plane_stress_j2_kernel(const PsJ2Params prm, const int64_t n, const double* __re
     wave_lds_sync();
 
     // ---- 3. the stress rows, as the strain came in ---------------------------------------------------------------------------
-    {
-      double* f0 = flux + base * 3;
-      const int nd = npts * 3;
-#pragma unroll
-      for (int pass = 0; pass < 2; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < WAVE * 3 / 2) {
-          const double2_t v = stage2[q];
-          if (2 * q + 1 < nd) stream_store<0>(reinterpret_cast<double2_t*>(f0) + q, v);
-          else if (2 * q < nd) stream_store<0>(f0 + 2 * q, v.x);
-        }
-      }
-    }
+#include "tile_rows3_store.hpp"
     // ---- 4. the tangent in output order: entry e of the tile belongs to point e / 9, column e % 9 of the row-major 3 x 3 ----
-    {
-      double* c0 = ct + base * 9;
-      const int nd = npts * 9;
-      auto entry = [&](int e) -> double {
-        const int p = e / 9, col = e - p * 9;
-        // (row, column) -> slot of the symmetric record: 0 1 2 / 1 3 4 / 2 4 5
-        const int slot = col < 3 ? col : (col < 6 ? (col == 3 ? 1 : col - 1) : (col == 6 ? 2 : col - 3));
-        return rec[p * PSJ_REC + slot];
-      };
-      constexpr int NQ = WAVE * 9 / 2;
-#pragma unroll
-      for (int pass = 0; pass < (NQ + WAVE - 1) / WAVE; ++pass) {
-        const int q = lane + pass * WAVE;
-        if (q < NQ && 2 * q < nd) {
-          const double2_t v = {entry(2 * q), entry(2 * q + 1)};
-          if (2 * q + 1 < nd) stream_store<0>(reinterpret_cast<double2_t*>(c0) + q, v);
-          else stream_store<0>(c0 + 2 * q, v.x);
-        }
-      }
-    }
+    auto entry = [&](int e) -> double {
+      const int p = e / W, col = e - p * W;
+      return rec[p * PSJ_REC + sym3_slot(col)];
+    };
+#include "tile_entries_store.hpp"
     wave_lds_sync();   // the LDS region is rewritten by the next tile
   }
 

@@ -62,7 +62,8 @@ def test_the_unit_is_built_into_the_library_and_named_by_the_tool():
     hpp = open(os.path.join(chk.CSRC, "heat_transfer.hpp")).read()
     assert hpp.count('__attribute__((visibility("hidden")))') == 3      # every host entry point of the unit
     for f in ("heat_transfer.hip", "heat_transfer.hpp"):
-        src = open(os.path.join(chk.CSRC, f)).read()
+        src = chk.unit_text(chk.CSRC, f)                                            # with the tile I/O texts it includes
+        assert f.endswith(".hpp") or ("reinterpret_cast<const double2_t*>(g0)" in src and "constexpr int NQ" in src)
         assert not re.findall(r"\basm\b", re.sub(r"//[^\n]*", "", src)), f          # plain C++: no inline assembly at all
         code = re.sub(r"//[^\n]*", "", src)
         assert "__syncthreads" not in code and "atomic" not in code.replace("__ATOMIC", "")

@@ -44,7 +44,8 @@ def test_the_unit_is_built_into_the_library_and_named_by_the_tool():
     hpp = open(os.path.join(chk.CSRC, "plane_stress.hpp")).read()
     assert "__global__" not in hpp and "__device__" not in hpp                        # host entry points and constants only
     assert hpp.count('__attribute__((visibility("hidden")))') == 3                    # every host entry point of the unit
-    hip = open(os.path.join(chk.CSRC, "plane_stress.hip")).read()
+    hip = chk.unit_text(chk.CSRC, "plane_stress.hip")                                 # with the tile I/O texts it includes
+    assert "reinterpret_cast<const double2_t*>(g0)" in hip and "constexpr int NQ" in hip
     code = re.sub(r"//[^\n]*", "", hip)
     assert not re.findall(r"\basm\b", code)                                           # plain C++: no inline assembly at all
     assert "__syncthreads" not in code and "atomic" not in code.replace("__ATOMIC", "")

@@ -59,7 +59,8 @@ def test_the_unit_is_built_into_the_library_and_named_by_the_tool():
     assert "__global__" not in hpp and "__device__" not in hpp                        # host entry points and constants only
     assert hpp.count('__attribute__((visibility("hidden")))') == 3                    # every host entry point of the unit
     assert "PSJ_LDS_BYTES == 18560" in hpp and "static_assert" in hpp
-    hip = open(os.path.join(chk.CSRC, "plane_stress_j2.hip")).read()
+    hip = chk.unit_text(chk.CSRC, "plane_stress_j2.hip")                              # with the tile I/O texts it includes
+    assert "reinterpret_cast<const double2_t*>(g0)" in hip and "constexpr int NQ" in hip
     code = re.sub(r"//[^\n]*", "", hip)
     assert not re.findall(r"\basm\b", code)            # no inline assembly of its own: only dxm_common.hpp's opaque(), through DXM_MUL
     assert "__syncthreads" not in code and "s_barrier" not in code and "atomic" not in code.replace("__ATOMIC", "")

@@ -5,15 +5,16 @@ hosford,orthotropic}.hip), on the cross-compiler alone:
 1. the resources of every kernel, read from -Rpass-analysis=kernel-resource-usage: no scratch and no spilled VGPR anywhere, and
    the kernels with per-point parameter fields within the bounds of the uniform J2 kernels (at most 128 VGPRs, the same static LDS,
    exactly 32 instantiations);
-   With --all-units the same for the units added since (small_strain_clean, single_crystal, heat_transfer), whose kernels need not
-   keep to the bounds of the J2 kernels;
+   With --all-units the same for the units added since (LATER_UNITS below), whose kernels need not keep to the bounds of the J2
+   kernels;
 2. (--parent REV) the device assembly of every unit is byte for byte what the sources of git revision REV give (but for the
    compilation-unit id, which hashes the source file's path); the parent's resource figures are printed beside the tree's.
 
     python tools/check_device_asm.py [--parent HEAD~1] [--write-digests FILE.json]
 
 Prints one line per kernel, one line per unit and a JSON summary; exit status 1 if a bound is broken or an assembly file differs.
-The helpers are what tests/test_{param_fields,hyperelastic,hosford,orthotropic}_build.py and tests/test_tile_fragments.py assert with."""
+The helpers are what tests/test_*_build.py and tests/test_tile_fragments.py assert with; unit_text() is the text of a unit that
+their scans for required and forbidden words read: the unit's file with the tile_*.hpp texts it includes in place."""
 import argparse
 import hashlib
 import json
@@ -34,6 +35,12 @@ LATER_UNITS = ("small_strain_clean", "single_crystal", "heat_transfer", "log_str
                "plane_strain", "plane_stress_j2", "plane_stress_hosford", "plane_gradient", "small_strain_packed")
 MAX_VGPRS = 128
 J2_STATIC_LDS = 30848     # small_strain.hpp: 4 waves x (64 x 6 + 64 x 9) doubles + the 4 x 4 status words
+
+
+def unit_text(csrc, name):
+    """csrc/NAME with every `#include "tile_*.hpp"` line replaced by that file's contents: the tile I/O steps are text of the kernel"""
+    src = open(os.path.join(csrc, name)).read()
+    return re.sub(r'^[ \t]*#include "(tile_\w+\.hpp)"[^\n]*$', lambda m: open(os.path.join(csrc, m.group(1))).read(), src, flags=re.M)
 
 
 def device_asm(csrc, unit, out, remarks=False):
