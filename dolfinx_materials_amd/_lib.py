@@ -27,6 +27,7 @@ LAW_PS_QUADRATIC, LAW_PS_POLYGON = 23, 24   # (22 is not assigned)
 LAW_PE_ELASTIC_ISO, LAW_PE_J2_LINEAR, LAW_PE_J2_VOCE = 26, 27, 28   # plane strain (25 is not assigned)
 LAW_PS_J2_LINEAR, LAW_PS_J2_VOCE = 30, 31   # plane-stress J2 with hardening (29 is not assigned)
 LAW_PS_HOSFORD = 33   # plane-stress Hosford (32 is not assigned)
+LAW_HEAT_STATIONARY_2D, LAW_HEAT_PHASE_CHANGE_2D = 35, 36   # the heat-transfer laws with a 2-wide gradient (34 is not assigned)
 DXM_MAX_EXTERNAL_STATE, DXM_MAX_TANGENT_BLOCKS = 2, 4
 S0, S1 = 0, 1
 
@@ -166,6 +167,12 @@ SYMBOLS = {
         _h,
         [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int],
     ),
+    "dxm_mesh_create_plane_scalar": (
+        _h,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+         C.c_int],
+    ),
+    "dxm_mesh_scalar_gradient_device": (C.c_int, [_h, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dxm_mesh_destroy": (C.c_int, [_h]),
     "dxm_mesh_npoints": (C.c_int64, [_h]),
     "dxm_mesh_displacement_size": (C.c_int64, [_h]),

@@ -43,6 +43,7 @@
 #include "plane_stress_j2.hpp"
 #include "plane_stress_hosford.hpp"
 #include "plane_gradient.hpp"
+#include "heat_plane.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -186,6 +187,9 @@ struct LawDesc {
   int plane_kind;                         // the gradient kind a two-dimensional mesh is asked for (plane_gradient.hpp: 2 the plane-strain
                                           // 4-vector, 3 the in-plane 3-vector); there the two refusals above do not apply and the gradient
                                           // kernel always runs on its own.  0: the law is 6 or 9 wide on every mesh
+  bool nodal_scalar;                      // the displacement forms take the nodal values of a SCALAR field on a scalar mesh
+                                          // (dxm_mesh_create_plane_scalar) in place of a displacement: the law's gradient is that
+                                          // field's and its external state variable 0 the field's value at the point
 };
 
 // doubles per point of the full tangent layout: the sum of the law's blocks
@@ -467,6 +471,8 @@ static void launch_orthotropic(const LaunchArgs& a);
 static void launch_single_crystal(const LaunchArgs& a);
 static void launch_heat_stationary(const LaunchArgs& a);
 static void launch_heat_phase_change(const LaunchArgs& a);
+static void launch_heat_stationary_2d(const LaunchArgs& a);
+static void launch_heat_phase_change_2d(const LaunchArgs& a);
 static void launch_log_strain(const LaunchArgs& a);
 static void launch_fs_single_crystal(const LaunchArgs& a);
 static void launch_ps_quadratic(const LaunchArgs& a);
@@ -1051,13 +1057,87 @@ constexpr LawDesc law_ps_hosford() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29 and 32 are not assigned and stay empty rows (law_known)
+// The two heat-transfer laws under a two-dimensional hypothesis (heat_plane.hip): temperature gradient in (16 B), heat flux (16) and
+// the blocks of the tangent out, 2 x 2 | 2 x 1 [| 1 x 1]; parameters, build functions, external state variable and HeatParams are
+// those of laws 16 / 17.  nodal_scalar: the displacement forms take the nodal temperature on a scalar mesh
+constexpr LawDesc heat_plane_law(int id, int n_params, const char* kernel) {
+  LawDesc d{};
+  d.id = id;
+  d.n_grad = d.n_flux = 2;
+  d.n_params = d.n_params_custom = n_params;
+  d.kernel = kernel;
+  d.ext_kernel = kernel;   // one instantiation reads a uniform temperature or a stream
+  d.n_ext = 1;
+  d.ext_name[0] = "Temperature";
+  d.ext_default[0] = 293.15;   // mfront.py:109-110
+  d.blocks[0] = tangent_block(DXM_BLOCK_ROW_FLUX, 0, DXM_BLOCK_COL_GRADIENT, 0, 2, 2);
+  d.blocks[1] = tangent_block(DXM_BLOCK_ROW_FLUX, 0, DXM_BLOCK_COL_EXTERNAL, 0, 2, 1);
+  d.n_blocks = 2;
+  d.ct_full = 6;
+  d.blocks_per_cu = HP_BLOCKS_PER_CU;   // heat_plane.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.nodal_scalar = true;
+  return d;
+}
+
+// counted as 64 B/point: temperature gradient in (16) and tangent out (48); with the flux (16) the kernel moves 80
+constexpr LawDesc law_heat_stationary_2d() {
+  LawDesc d = heat_plane_law(DXM_LAW_HEAT_STATIONARY_2D, 2, "heat_plane_kernel<0, 0");
+  d.alg_bytes = 64;
+  d.build = build_heat_stationary;
+  d.residency_kernel = DXM_STOCK_ONLY(heat_plane_stationary_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_heat_stationary_2d);
+  d.no_fields = "per-point parameter fields are not served for two-dimensional stationary heat transfer: A and B are per-handle "
+                "constants (the temperature is an external state variable: dxm_set_external_state)";
+  d.stock_only = "two-dimensional stationary heat transfer has no hardening law: it is served by the stock libdxmat, not by a "
+                 "custom-hardening build";
+  d.set_refusal = d.launch_refusal = "the two-dimensional stationary heat-transfer tangent is two blocks of 4 + 2 entries, not a "
+                                     "symmetric 6x6: only DXM_TANGENT_FULL is available, no packed record (sym / coef / pack4) exists "
+                                     "for this law";
+  d.no_fused = d.no_displacement = "two-dimensional stationary heat transfer takes a temperature gradient, not a strain or a deformation "
+                                   "gradient: the displacement forms (dxm_integrate_displacement*) serve it from the nodal temperature "
+                                   "on a scalar mesh (dxm_mesh_create_plane_scalar) only; on this mesh pass grad(T) as an array";
+  d.no_frame = "two-dimensional stationary heat transfer is isotropic (a scalar conductivity): a material frame changes nothing in its "
+               "update";
+  return d;
+}
+
+// counted as 80 B/point: gradient in (16), tangent (56) and enthalpy (8) out; with the flux (16) the kernel moves 96.  The enthalpy
+// is written, never read
+constexpr LawDesc law_heat_phase_change_2d() {
+  LawDesc d = heat_plane_law(DXM_LAW_HEAT_PHASE_CHANGE_2D, 7, "heat_plane_kernel<1, 0");
+  d.alg_bytes = 80;
+  d.n_isv_fields = d.n_fields = 1;
+  state_field(d, 0, "Enthalpy", 1, 0);
+  d.n_slots = 1;
+  d.blocks[2] = tangent_block(DXM_BLOCK_ROW_STATE, 0, DXM_BLOCK_COL_EXTERNAL, 0, 1, 1);
+  d.n_blocks = 3;
+  d.ct_full = 7;
+  d.build = build_heat_phase_change;
+  d.residency_kernel = DXM_STOCK_ONLY(heat_plane_phase_change_kernel_fn);
+  d.launch = DXM_STOCK_ONLY(launch_heat_phase_change_2d);
+  d.no_fields = "per-point parameter fields are not served for two-dimensional heat transfer with phase change: its constants are "
+                "formed once per handle (the temperature is an external state variable: dxm_set_external_state)";
+  d.stock_only = "two-dimensional heat transfer with phase change has no hardening law: it is served by the stock libdxmat, not by a "
+                 "custom-hardening build";
+  d.set_refusal = d.launch_refusal = "the two-dimensional phase-change tangent is three blocks of 4 + 2 + 1 entries, not a symmetric "
+                                     "6x6: only DXM_TANGENT_FULL is available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fused = d.no_displacement = "two-dimensional heat transfer with phase change takes a temperature gradient, not a strain or a "
+                                   "deformation gradient: the displacement forms (dxm_integrate_displacement*) serve it from the nodal "
+                                   "temperature on a scalar mesh (dxm_mesh_create_plane_scalar) only; on this mesh pass grad(T) as an array";
+  d.no_frame = "two-dimensional heat transfer with phase change is isotropic (a scalar conductivity): a material frame changes nothing "
+               "in its update";
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32 and 34 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
     law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(), {}, law_fs_single_crystal(), {},
     law_ps_quadratic(), law_ps_polygon(), {}, law_pe_elastic(), law_pe_j2_linear(), law_pe_j2_voce(), {},
     law_ps_j2_linear(), law_ps_j2_voce(), {}, law_ps_hosford(),
+    {}, law_heat_stationary_2d(), law_heat_phase_change_2d(),
 };
 
 constexpr bool rows_in_place() {
@@ -1068,8 +1148,8 @@ constexpr bool rows_in_place() {
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
                   !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel && !kLaws[29].kernel &&
-                  !kLaws[32].kernel,
-              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29 and 32 are not assigned");
+                  !kLaws[32].kernel && !kLaws[34].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32 and 34 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -1193,6 +1273,12 @@ struct dxm_material {
   int ext_kind[DXM_MAX_EXTERNAL_STATE] = {};
   double ext_uniform[DXM_MAX_EXTERNAL_STATE] = {};
   double* ext_field[DXM_MAX_EXTERNAL_STATE] = {};
+  // the nodal forms of the laws with LawDesc::nodal_scalar, for the duration of one call: 0 none, 1 the update kernel evaluates the
+  // field at its points from nodal_src, 2 it reads the value stream d_nodal_value the scalar gradient kernel wrote.  The handle's own
+  // external state above is neither read nor changed by such a call
+  int nodal_mode = 0;
+  ScalarSource nodal_src{};
+  double* d_nodal_value = nullptr;          // n doubles, allocated by the first such call without a fused gradient
   int frame_kind = 0;
   Frame9 frame_uniform{};
   double* frame_streams = nullptr;          // the field as nine SoA streams of ld doubles each (the kernel reads 8 B per lane)
@@ -1517,6 +1603,7 @@ int dxm_destroy(dxm_material* m) {
   for (double* q : m->pf_stream) if (q) (void)hipFree(q);
   if (m->frame_streams) (void)hipFree(m->frame_streams);
   for (double* q : m->ext_field) if (q) (void)hipFree(q);
+  if (m->d_nodal_value) (void)hipFree(m->d_nodal_value);
   for (hipEvent_t e : m->ring_done) if (e) (void)hipEventDestroy(e);
   if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
   if (m->pipe_stream) (void)hipStreamDestroy(m->pipe_stream);
@@ -2015,18 +2102,22 @@ static void launch_single_crystal(const LaunchArgs& a) {
 }
 
 // the external state variable of the range: the field advances with it like the state slots
-static void launch_heat_stationary(const LaunchArgs& a) {
-  dxm_material* m = a.m;
+static HeatParams heat_params_stationary(const dxm_material* m) {
   HeatParams hp{};
   hp.p[HT_A] = m->raw_params[0];
   hp.p[HT_B] = m->raw_params[1];
+  return hp;
+}
+static void launch_heat_stationary(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  const HeatParams hp = heat_params_stationary(m);
   heat_transfer_launch(HT_STATIONARY, a.grid, a.st, hp, a.cnt, a.grad, m->ext_uniform[0], m->ext_kind[0] ? m->ext_field[0] + a.off : nullptr,
                        nullptr, a.flux, a.ct, m->d_stats + a.stats_off);
 }
 
-static void launch_heat_phase_change(const LaunchArgs& a) {
+// what both phase-change kernels read (heat_transfer.hpp: HeatParams): each entry a parameter or one individually rounded operation
+static HeatParams heat_params_phase_change(const dxm_material* m) {
 #pragma clang fp contract(off)
-  dxm_material* m = a.m;
   const double* p = m->raw_params.data();   // [Tm, ks, cs, kl, cl, dhsl, Tsmooth] (build_heat_phase_change)
   const double Tm = p[0], ks = p[1], cs = p[2], kl = p[3], cl = p[4], dhsl = p[5], Tsm = p[6];
   HeatParams hp{};
@@ -2043,8 +2134,30 @@ static void launch_heat_phase_change(const LaunchArgs& a) {
   hp.p[HT_CSTS] = cs * hp.p[HT_TS];
   const double cc = (cs + cl) * Tsm;
   hp.p[HT_HL3] = cc / 2;
+  return hp;
+}
+static void launch_heat_phase_change(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  const HeatParams hp = heat_params_phase_change(m);
   heat_transfer_launch(HT_PHASE_CHANGE, a.grid, a.st, hp, a.cnt, a.grad, m->ext_uniform[0], m->ext_kind[0] ? m->ext_field[0] + a.off : nullptr,
                        m->state[1] + a.off, a.flux, a.ct, m->d_stats + a.stats_off);
+}
+
+// The 2-wide laws (heat_plane.hip) on the same records.  In a nodal call (dxm_material::nodal_mode) the temperature of a point is
+// the field's: evaluated by the kernel itself from the mesh (1), or the stream the scalar gradient kernel wrote beside the
+// gradient (2); the handle's own external state is not read then
+static void launch_heat_plane(int law, const HeatParams& hp, const LaunchArgs& a, double* enthalpy) {
+  dxm_material* m = a.m;
+  const double* tfield = m->ext_kind[0] ? m->ext_field[0] + a.off : nullptr;
+  ScalarSource src = m->nodal_src;
+  src.point0 = a.off;
+  if (m->nodal_mode == 2) tfield = m->d_nodal_value + a.off;
+  heat_plane_launch(law, a.grid, a.st, hp, a.cnt, a.grad, m->ext_uniform[0], tfield, m->nodal_mode == 1 ? &src : nullptr, enthalpy, a.flux,
+                    a.ct, m->d_stats + a.stats_off);
+}
+static void launch_heat_stationary_2d(const LaunchArgs& a) { launch_heat_plane(HT_STATIONARY, heat_params_stationary(a.m), a, nullptr); }
+static void launch_heat_phase_change_2d(const LaunchArgs& a) {
+  launch_heat_plane(HT_PHASE_CHANGE, heat_params_phase_change(a.m), a, a.m->state[1] + a.off);
 }
 
 // the plane-stress stiffness as cvxpy_materials.py:16-18 forms it, and its eigenvalues: what every plane-stress launcher puts into
@@ -2734,6 +2847,10 @@ struct dxm_mesh {
   int geom_nv = 0;
   double* d_gdphi = nullptr;
   bool plane = false;
+  // a SCALAR field on a plane mesh (dxm_mesh_create_plane_scalar): one value per dof, and the values of the field's shape functions
+  // at the Gauss points, (nqp, nd), beside their derivatives.  Read by heat_plane.hip only: every kind of dxm_mesh_gradient_device refuses
+  bool scalar = false;
+  double* d_phi = nullptr;
 };
 
 // triangles through dxm_mesh_create_simplex, triangles and quadrilaterals through dxm_mesh_create_plane
@@ -2856,18 +2973,27 @@ dxm_mesh* dxm_mesh_create_simplex(int tdim, const double* coords, int64_t n_vert
   return mesh;
 }
 
-dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
-                                const int32_t* dofmap, int nd, int64_t n_dofs, const double* geom_dphi, const double* dphi, int nqp,
-                                int device) {
+// dxm_mesh_create_plane (components 2, phi null) and dxm_mesh_create_plane_scalar (components 1, with the value table phi)
+static dxm_mesh* plane_mesh_create(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
+                                   const int32_t* dofmap, int nd, int64_t n_dofs, const double* geom_dphi, const double* phi,
+                                   const double* dphi, int nqp, int device, int components) {
+  const bool scalar = components == 1;
   // every check runs on the host before a device is asked for: the kernels are never launched on indices that were not checked
   if (nv != 3 && nv != 4) {
     fail(-1, "a plane mesh has nv = 3 (triangles) or nv = 4 (bilinear quadrilaterals) vertices per cell, not %d", nv);
     return nullptr;
   }
-  if (!coords || !geom_conn || !dofmap || !geom_dphi || !dphi || n_vertices <= 0 || n_cells <= 0 || nd < nv ||
+  if (!coords || !geom_conn || !dofmap || !geom_dphi || !dphi || (scalar && !phi) || n_vertices <= 0 || n_cells <= 0 || nd < nv ||
       nd > PLANE_GRAD_MAX_ND || n_dofs <= 0 || nqp <= 0 || nqp > PLANE_GRAD_MAX_NQP) {
     fail(-1, "invalid plane mesh arguments");
     return nullptr;
+  }
+  if (scalar) {   // a NaN in a table would reach every point: the values, then the field's derivatives, then the geometry's
+    const struct { const char* name; const double* tab; int64_t len; } tabs[3] = {
+        {"phi", phi, (int64_t)nqp * nd}, {"dphi", dphi, (int64_t)nqp * nd * 2}, {"geom_dphi", geom_dphi, (int64_t)nqp * nv * 2}};
+    for (const auto& t : tabs)
+      for (int64_t k = 0; k < t.len; ++k)
+        if (!std::isfinite(t.tab[k])) { fail(-1, "table %s: entry %lld is not finite", t.name, (long long)k); return nullptr; }
   }
   for (int64_t k = 0; k < n_cells * nv; ++k)
     if (geom_conn[k] < 0 || geom_conn[k] >= n_vertices) { fail(-1, "geometry connectivity entry %lld out of range", (long long)k); return nullptr; }
@@ -2905,6 +3031,7 @@ dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const 
   dxm_mesh* mesh = new dxm_mesh();
   mesh->nodes_per_cell = 0;
   mesh->plane = true;
+  mesh->scalar = scalar;
   mesh->device = device;
   mesh->n_nodes = n_vertices;
   mesh->n_cells = n_cells;
@@ -2913,7 +3040,7 @@ dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const 
   mesh->nd = nd;
   mesh->geom_nv = nv;
   mesh->n_dofs = n_dofs;
-  mesh->u_len = 2 * n_dofs;
+  mesh->u_len = components * n_dofs;
   DeviceGuard guard(device);
   bool ok = guard.ok;
   ok = ok && hipMalloc(&mesh->d_coords, sizeof(double) * 3 * n_vertices) == hipSuccess;
@@ -2927,12 +3054,28 @@ dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const 
   ok = ok && upload_from_host(mesh->d_dofmap, dofmap, sizeof(int32_t) * nd * n_cells, nullptr) == 0;
   ok = ok && upload_from_host(mesh->d_gdphi, geom_dphi, sizeof(double) * nqp * nv * 2, nullptr) == 0;
   ok = ok && upload_from_host(mesh->d_dphi, dphi, sizeof(double) * nqp * nd * 2, nullptr) == 0;
+  if (scalar) {
+    ok = ok && hipMalloc(&mesh->d_phi, sizeof(double) * nqp * nd) == hipSuccess;
+    ok = ok && upload_from_host(mesh->d_phi, phi, sizeof(double) * nqp * nd, nullptr) == 0;
+  }
   if (!ok) {
     fail(-3, "device allocation / upload of the mesh failed");
     dxm_mesh_destroy(mesh);
     return nullptr;
   }
   return mesh;
+}
+
+dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
+                                const int32_t* dofmap, int nd, int64_t n_dofs, const double* geom_dphi, const double* dphi, int nqp,
+                                int device) {
+  return plane_mesh_create(coords, n_vertices, geom_conn, nv, n_cells, dofmap, nd, n_dofs, geom_dphi, nullptr, dphi, nqp, device, 2);
+}
+
+dxm_mesh* dxm_mesh_create_plane_scalar(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
+                                       const int32_t* dofmap, int nd, int64_t n_dofs, const double* geom_dphi, const double* phi,
+                                       const double* dphi, int nqp, int device) {
+  return plane_mesh_create(coords, n_vertices, geom_conn, nv, n_cells, dofmap, nd, n_dofs, geom_dphi, phi, dphi, nqp, device, 1);
 }
 
 int dxm_mesh_destroy(dxm_mesh* mesh) {
@@ -2945,6 +3088,7 @@ int dxm_mesh_destroy(dxm_mesh* mesh) {
   if (mesh->d_dofmap) (void)hipFree(mesh->d_dofmap);
   if (mesh->d_dphi) (void)hipFree(mesh->d_dphi);
   if (mesh->d_gdphi) (void)hipFree(mesh->d_gdphi);
+  if (mesh->d_phi) (void)hipFree(mesh->d_phi);
   if (mesh->grad_done) (void)hipEventDestroy(mesh->grad_done);
   delete mesh;
   return 0;
@@ -2958,6 +3102,9 @@ static MeshSource mesh_source(const dxm_mesh* mesh, const double* u_dev);
 int dxm_mesh_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, double* grad_dev,
                              void* hip_stream) {
   if (!mesh || !u_dev || !grad_dev) return fail(-1, "null argument");
+  if (mesh->scalar)
+    return fail(-1, "a scalar mesh (dxm_mesh_create_plane_scalar) holds one value per dof, not a displacement: it has no strain or "
+                    "deformation gradient of any kind; dxm_mesh_scalar_gradient_device evaluates grad(T) and T on it");
   if (kind < 0 || kind > 3)
     return fail(-1, "gradient kind must be 0 (strain), 1 (F), 2 (plane-strain 4-vector) or 3 (in-plane 3-vector)");
   if (kind >= 2 && !mesh_2d(mesh))
@@ -3024,9 +3171,130 @@ static MeshSource mesh_source(const dxm_mesh* mesh, const double* u_dev) {
 }
 static bool fusable(const dxm_mesh* mesh) { return fused_kind(mesh) != 0; }
 
+// ---- a scalar field on a plane mesh: grad(T) and T at the Gauss points, and the nodal forms of the laws that read them ----------
+#ifndef DXM_CUSTOM_HARDENING
+static ScalarSource scalar_source(const dxm_mesh* mesh, const double* t_dev) {
+  ScalarSource s{};
+  s.coords = mesh->d_coords; s.conn = mesh->d_conn; s.dofmap = mesh->d_dofmap; s.gdphi = mesh->d_gdphi; s.phi = mesh->d_phi;
+  s.dphi = mesh->d_dphi; s.t = t_dev; s.point0 = 0; s.nqp = mesh->qp.nqp; s.nv = mesh->geom_nv; s.nd = mesh->nd;
+  return s;
+}
+#endif
+
+int dxm_mesh_scalar_gradient_device(dxm_mesh* mesh, const double* t_dev, double* grad_dev, double* value_dev, void* hip_stream) {
+  if (!mesh || !t_dev || !grad_dev) return fail(-1, "null argument");
+  if (!mesh->scalar)
+    return fail(-1, "dxm_mesh_scalar_gradient_device needs a scalar mesh (dxm_mesh_create_plane_scalar): this mesh carries a "
+                    "displacement, whose gradients dxm_mesh_gradient_device evaluates");
+  if ((uintptr_t)grad_dev & 15) return fail(-1, "the gradient device array must be 16-byte aligned");
+#ifdef DXM_CUSTOM_HARDENING
+  return fail(-1, "the scalar gradient kernel (a mesh of dxm_mesh_create_plane_scalar) is served by the stock libdxmat, not by a "
+                  "custom-hardening build, which is dxmat.hip alone");
+#else
+  DEVICE_GUARD(mesh);
+  HIP_TRY(scalar_gradient_launch((hipStream_t)hip_stream, scalar_source(mesh, t_dev), mesh->n_cells * mesh->qp.nqp, grad_dev, value_dev));
+  return 0;
+#endif
+}
+
+// a scalar mesh and a law that reads a scalar field belong together: every other pairing is refused, the handle left as it was
+static bool nodal_pairing(const dxm_material* m, const dxm_mesh* mesh) { return mesh->scalar || kLaws[m->law].nodal_scalar; }
+static int nodal_refusal(const dxm_material* m, const dxm_mesh* mesh) {
+  const LawDesc& d = kLaws[m->law];
+  if (!mesh->scalar) return fail(-1, "%s", d.no_displacement);   // a law of a scalar field on a mesh that carries a displacement
+  if (!d.nodal_scalar) {
+    if (d.no_displacement && !d.plane_kind) return fail(-1, "%s", d.no_displacement);   // as on every other mesh
+    return fail(-1, "a scalar mesh (dxm_mesh_create_plane_scalar) carries a temperature, not a displacement: it serves the "
+                    "two-dimensional heat-transfer laws (DXM_LAW_HEAT_STATIONARY_2D, DXM_LAW_HEAT_PHASE_CHANGE_2D) only, not law %d",
+                m->law);
+  }
+  if (mesh->device != m->device) return fail(-1, "mesh and material live on different devices");
+  if (dxm_mesh_npoints(mesh) != m->n) return fail(-1, "mesh has %lld Gauss points, material %lld",
+                                                   (long long)dxm_mesh_npoints(mesh), (long long)m->n);
+  return 0;
+}
+
+#ifndef DXM_CUSTOM_HARDENING
+// the nodal mode of the handle lasts for one call
+struct NodalCall {
+  dxm_material* m;
+  NodalCall(dxm_material* m_, const dxm_mesh* mesh, const double* t_dev, int mode) : m(m_) {
+    m->nodal_src = scalar_source(mesh, t_dev);
+    m->nodal_mode = mode;
+  }
+  ~NodalCall() { m->nodal_mode = 0; m->nodal_src = ScalarSource{}; }
+};
+
+// fused_gradient 0: grad(T) and T into the handle's scratch on st, for the update kernel that follows there
+static int nodal_scratch(dxm_material* m, const dxm_mesh* mesh, const double* t_dev, hipStream_t st) {
+  if (!m->d_grad) HIP_TRY(hipMalloc(&m->d_grad, sizeof(double) * m->n * kLaws[m->law].n_grad));
+  if (!m->d_nodal_value) HIP_TRY(hipMalloc(&m->d_nodal_value, sizeof(double) * m->n));
+  HIP_TRY(scalar_gradient_launch(st, scalar_source(mesh, t_dev), m->n, m->d_grad, m->d_nodal_value));
+  return 0;
+}
+#endif
+
+// dxm_integrate_displacement / _rows with the nodal temperature t_host (n_dofs doubles) in place of a displacement
+static int integrate_nodal_host(dxm_material* m, dxm_mesh* mesh, const double* t_host, double* flux_aos, double* isv_aos, double* ct_aos,
+                                dxm_stats* stats, const int64_t* rows) {
+  if (int rc = nodal_refusal(m, mesh)) return rc;
+#ifdef DXM_CUSTOM_HARDENING
+  return fail(-1, "%s", kLaws[m->law].stock_only);
+#else
+  if (m->n == 0) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    return 0;
+  }
+  DEVICE_GUARD(m);
+  m->last_upload = DXM_UPLOAD_NONE;   // no gradient array crosses PCIe in this form
+  const bool fuse = m->opt_fused_gradient;   // T and grad(T) evaluated inside the update kernel
+  if (int rc = ensure_host_path_buffers(m, true)) return rc;   // (the chunks address d_grad by offset in either mode)
+  hipStream_t st = m->own_stream;
+  if (int rc = sync_last(m)) return rc;
+  if (int rc = upload_from_host(mesh->d_u, t_host, sizeof(double) * mesh->u_len, st)) return rc;
+  if (!fuse)
+    if (int rc = nodal_scratch(m, mesh, mesh->d_u, st)) return rc;
+  // the upload (and the scratch) are produced on own_stream; chunks on the second stream wait for it
+  if (!mesh->grad_done) HIP_TRY(hipEventCreateWithFlags(&mesh->grad_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(mesh->grad_done, st));
+  auto upload = [&](int64_t, int64_t, hipStream_t s) -> int {
+    if (s != st) HIP_TRY(hipStreamWaitEvent(s, mesh->grad_done, 0));
+    return 0;
+  };
+  NodalCall call(m, mesh, mesh->d_u, fuse ? 1 : 2);
+  const int rc = run_and_download(m, upload, flux_aos, isv_aos, ct_aos, stats, nullptr, nullptr, rows);
+  if (fuse) m->io1_valid &= ~1;   // grad(T) never existed as an array
+  return rc;
+#endif
+}
+
+// dxm_integrate_displacement_device with the nodal temperature t_dev in place of a displacement
+static int integrate_nodal_device(dxm_material* m, dxm_mesh* mesh, const double* t_dev, double dt, double* flux_dev, double* ct_dev,
+                                  void* hip_stream) {
+  if (int rc = nodal_refusal(m, mesh)) return rc;
+#ifdef DXM_CUSTOM_HARDENING
+  return fail(-1, "%s", kLaws[m->law].stock_only);
+#else
+  if (int rc = take_dt(m, dt)) return rc;
+  if (m->n > 0 && (!t_dev || !flux_dev || !ct_dev)) return fail(-1, "null device pointer");
+  DEVICE_GUARD(m);
+  hipStream_t st = (hipStream_t)hip_stream;
+  if (m->opt_fused_gradient) {   // one kernel: no gradient array, no temperature array
+    NodalCall call(m, mesh, t_dev, 1);
+    return launch(m, flux_dev /* unused, only checked for alignment */, flux_dev, ct_dev, st);
+  }
+  // two kernels on the caller's stream through the handle's scratch
+  if (m->n > 0)
+    if (int rc = nodal_scratch(m, mesh, t_dev, st)) return rc;
+  NodalCall call(m, mesh, t_dev, 2);
+  return launch(m, m->d_grad, flux_dev, ct_dev, st);
+#endif
+}
+
 static int integrate_displacement_host(dxm_material* m, dxm_mesh* mesh, const double* u_host, double* flux_aos, double* isv_aos,
                                        double* ct_aos, dxm_stats* stats, const int64_t* rows) {
   if (!m || !mesh || !u_host) return fail(-1, "null argument");
+  if (nodal_pairing(m, mesh)) return integrate_nodal_host(m, mesh, u_host, flux_aos, isv_aos, ct_aos, stats, rows);   // a scalar field's nodal values
   const bool plane_law = kLaws[m->law].plane_kind && mesh_2d(mesh);   // a 2-D law on a 2-D mesh: gradient kernel, then update kernel
   if (kLaws[m->law].no_displacement && !plane_law) return fail(-1, "%s", kLaws[m->law].no_displacement);
   if (mesh->device != m->device) return fail(-1, "mesh and material live on different devices");
@@ -3072,6 +3340,7 @@ int dxm_integrate_displacement_rows(dxm_material* m, dxm_mesh* mesh, const doubl
 int dxm_integrate_displacement_device(dxm_material* m, dxm_mesh* mesh, const double* u_dev, double dt,
                                       double* flux_dev, double* ct_dev, void* hip_stream) {
   if (!m || !mesh) return fail(-1, "null argument");
+  if (nodal_pairing(m, mesh)) return integrate_nodal_device(m, mesh, u_dev, dt, flux_dev, ct_dev, hip_stream);   // a scalar field's nodal values
   const bool plane_law = kLaws[m->law].plane_kind && mesh_2d(mesh);   // the 2-D laws have no fused form: the option makes no difference
   if (kLaws[m->law].no_displacement && !plane_law) return fail(-1, "%s", kLaws[m->law].no_displacement);
   if (int rc = take_dt(m, dt)) return rc;

@@ -1,5 +1,6 @@
 """Device-side gradient evaluation for first-order hexahedra / tetrahedra, for Lagrange elements of any order on
-straight-sided simplices and for plane meshes of triangles or bilinear quadrilaterals (``dxm_mesh_*`` of ``include/dxmat.h``).
+straight-sided simplices and for plane meshes of triangles or bilinear quadrilaterals (``dxm_mesh_*`` of ``include/dxmat.h``); a scalar
+field on a plane mesh (:class:`PlaneScalarMesh`: the temperature and its gradient, for the two-dimensional heat-transfer laws).
 
 The step before the hot path in the reference is ``QuadratureExpression.eval`` ->
 ``fem.Expression.eval`` (``quadrature_function.py:45-51``): dolfinx tabulates the UFL gradient at
@@ -423,3 +424,141 @@ class PlaneMesh(_DeviceMesh):
         if cells is not None:
             geom_conn, dofmap = geom_conn[np.asarray(cells)], dofmap[np.asarray(cells)]
         return cls(np.asarray(mesh.geometry.x), geom_conn, dofmap, n_dofs, geom_dphi, dphi, device=device)
+
+
+# ---- a scalar field on a plane mesh: the temperature of the two-dimensional heat-transfer laws -------------------------------------
+def lagrange_simplex_values(tdim, degree, points):
+    """Values ``phi[q, m] = N_m(xi_q)`` of the Lagrange basis of the given degree (1 or 2) on the reference simplex at ``points``
+    (nqp, tdim): the table beside :func:`lagrange_simplex_table`, dofs in the same order."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, tdim)
+    lam = np.concatenate([1.0 - pts.sum(axis=1, keepdims=True), pts], axis=1)          # (nqp, tdim+1)
+    if degree == 1:
+        return np.ascontiguousarray(lam)
+    if degree != 2:
+        raise ValueError("lagrange_simplex_values: degree 1 or 2 (hand any other table to PlaneScalarMesh directly)")
+    cols = [lam[:, v] * (2.0 * lam[:, v] - 1.0) for v in range(tdim + 1)]
+    cols += [4.0 * lam[:, i] * lam[:, j] for i, j in BASIX_EDGES[tdim]]
+    return np.ascontiguousarray(np.stack(cols, axis=1))
+
+
+def lagrange_quad_values(degree, points):
+    """Values ``phi[q, m] = N_m(xi_q)`` of the tensor-product Lagrange basis Q1 or Q2 on [0,1]^2 at ``points`` (nqp, 2): the table
+    beside :func:`lagrange_quad_table`, dofs in the same order."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+    if degree == 1:
+        L = [np.stack([1.0 - pts[:, d], pts[:, d]], axis=1) for d in range(2)]
+        nodes = _Q2_NODES[:4]
+    elif degree == 2:
+        L = [np.stack([(1.0 - t) * (1.0 - 2.0 * t), t * (2.0 * t - 1.0), 4.0 * t * (1.0 - t)], axis=1) for t in (pts[:, 0], pts[:, 1])]
+        nodes = _Q2_NODES
+    else:
+        raise ValueError("lagrange_quad_values: degree 1 or 2 (hand any other table to PlaneScalarMesh directly)")
+    return np.ascontiguousarray(np.stack([L[0][:, i] * L[1][:, j] for i, j in nodes], axis=1))
+
+
+class PlaneScalarMesh(_DeviceMesh):
+    """A scalar Lagrange field of any order -- a temperature -- on a two-dimensional mesh of triangles or bilinear quadrilaterals
+    (``dxm_mesh_create_plane_scalar``): what the reference's heat-transfer demos differentiate (``ufl.grad(T)``, 2 wide, with ``T``
+    itself as the external state variable).  Arguments as for :class:`PlaneMesh`, with ONE value per dof and the table ``phi``
+    (nqp, nd) of the field's shape functions at the Gauss points beside their derivatives ``dphi`` (nqp, nd, 2).
+
+    With a heat-transfer material of ``hypothesis="plane_strain"`` the mesh goes where a displacement mesh goes
+    (``HIPMaterial.integrate_displacement*``, ``QuadratureMap.register_device_gradient``) and the nodal temperature where the
+    displacement goes: the update kernel interpolates ``T`` and ``grad(T)`` at its own points.  :meth:`gradient_device` refuses:
+    :meth:`scalar_gradient_device` is this mesh's stand-alone evaluation."""
+
+    tdim = 2
+    #: the external state variable the nodal forms interpolate themselves (a ``QuadratureMap`` does not upload it then)
+    nodal_variable = "Temperature"
+
+    def __init__(self, coords, geom_conn, dofmap, n_dofs, geom_dphi, phi, dphi, device=0):
+        self._lib = _lib.load()
+        geom_conn = np.ascontiguousarray(geom_conn, dtype=np.int32)
+        coords = np.asarray(coords, dtype=np.float64)
+        if coords.shape[1] == 2:
+            coords = np.concatenate([coords, np.zeros((len(coords), 1))], axis=1)
+        coords = np.ascontiguousarray(coords)
+        dofmap = np.ascontiguousarray(dofmap, dtype=np.int32)
+        geom_dphi = np.ascontiguousarray(geom_dphi, dtype=np.float64)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        dphi = np.ascontiguousarray(dphi, dtype=np.float64)
+        if dphi.ndim != 3 or dphi.shape[1] != dofmap.shape[1] or dphi.shape[2] != 2 or len(dofmap) != len(geom_conn):
+            raise ValueError("dphi must be (nqp, nd, 2) with nd = dofmap.shape[1]; one dofmap row per cell")
+        if phi.shape != dphi.shape[:2]:
+            raise ValueError("phi must be (nqp, nd), the values beside the derivatives dphi (nqp, nd, 2)")
+        if geom_dphi.shape != (dphi.shape[0], geom_conn.shape[1], 2):
+            raise ValueError("geom_dphi must be (nqp, nv, 2) with nv = geom_conn.shape[1] and the nqp of dphi")
+        self.n_nodes, self.n_cells, self.nqp = coords.shape[0], geom_conn.shape[0], dphi.shape[0]
+        self.nv, self.nd, self.n_dofs, self.device = geom_conn.shape[1], dofmap.shape[1], int(n_dofs), int(device)
+        h = self._lib.dxm_mesh_create_plane_scalar(coords.ctypes.data, self.n_nodes, geom_conn.ctypes.data, self.nv, self.n_cells,
+                                                   dofmap.ctypes.data, self.nd, self.n_dofs, geom_dphi.ctypes.data, phi.ctypes.data,
+                                                   dphi.ctypes.data, self.nqp, self.device)
+        if not h:
+            raise _lib.DxmError(f"dxm_mesh_create_plane_scalar failed: {_lib.last_error()}")
+        self._handle = h
+
+    def scalar_gradient_device(self, t_ptr, grad_ptr, value_ptr=0, stream=0):
+        """Device pointers, asynchronous on ``stream``: ``grad(T)`` into ``grad_ptr`` (npoints, 2) and, unless ``value_ptr`` is 0,
+        ``T`` into ``value_ptr`` (npoints) at the Gauss points from the ``n_dofs`` nodal values at ``t_ptr``."""
+        _lib.check(self._lib.dxm_mesh_scalar_gradient_device(self._handle, int(t_ptr), int(grad_ptr), int(value_ptr) or None,
+                                                             int(stream) or None))
+
+    @classmethod
+    def lagrange(cls, coords, cells, degree=1, quadrature_degree=None, device=0):
+        """Stand-alone constructor (no dolfinx), the mirror of :meth:`PlaneMesh.lagrange`: a first- or second-order scalar field on
+        the vertex mesh ``(coords, cells)`` of triangles or quadrilaterals, the same dof numbering, points and default quadrature
+        degrees.  Returns ``(mesh, dof_coords)``."""
+        coords, cells = np.asarray(coords, dtype=np.float64), np.asarray(cells)
+        if degree not in (1, 2):
+            raise ValueError("PlaneScalarMesh.lagrange: degree 1 or 2 (hand any other table to PlaneScalarMesh directly)")
+        if cells.shape[1] == 3:
+            pts = simplex_quadrature(2, 2 * (degree - 1) if quadrature_degree is None else quadrature_degree)
+            geom_dphi, dphi, phi = lagrange_simplex_table(2, 1, pts), lagrange_simplex_table(2, degree, pts), lagrange_simplex_values(2, degree, pts)
+            dofmap, n_dofs, edges = p2_dofmap(cells) if degree == 2 else (cells, len(coords), None)
+            inner = np.empty((0, coords.shape[1]))
+        elif cells.shape[1] == 4:
+            pts = quad_quadrature(2 * degree if quadrature_degree is None else quadrature_degree)
+            geom_dphi, dphi, phi = lagrange_quad_table(1, pts), lagrange_quad_table(degree, pts), lagrange_quad_values(degree, pts)
+            dofmap, n_dofs, edges = q2_dofmap(cells) if degree == 2 else (cells, len(coords), None)
+            inner = coords[cells].mean(axis=1)            # the bilinear image of (1/2, 1/2)
+        else:
+            raise ValueError("PlaneScalarMesh.lagrange: cells with 3 (triangles) or 4 (quadrilaterals) vertices")
+        mesh = cls(coords, cells, dofmap, n_dofs, geom_dphi, phi, dphi, device=device)
+        if degree == 1:
+            return mesh, coords.copy()
+        return mesh, np.concatenate([coords, 0.5 * (coords[edges[:, 0]] + coords[edges[:, 1]]), inner], axis=0)
+
+    @classmethod
+    def from_dolfinx(cls, V, quadrature_degree, device=0, cells=None):
+        """From a dolfinx SCALAR Lagrange space (any order, block size 1; ``cells``: those of one ``QuadratureMap`` instead of all)
+        on a first-order triangle or quadrilateral mesh, as :meth:`PlaneMesh.from_dolfinx` does for a vector space: point
+        ``c * nqp + q`` is row ``c * nqp + q`` of the quadrature Functions and ``T.x.array`` is the vector to hand to
+        ``integrate_displacement``.  UNTESTED without dolfinx."""
+        import basix
+
+        mesh = V.mesh
+        if mesh.topology.dim != 2 or V.dofmap.index_map_bs != 1:
+            raise ValueError("PlaneScalarMesh.from_dolfinx needs a scalar Lagrange space (block size 1) on a two-dimensional mesh")
+        dofmap = np.asarray(V.dofmap.list, dtype=np.int32)
+        n_cells = dofmap.shape[0] if dofmap.ndim == 2 else len(dofmap) // len(V.dofmap.cell_dofs(0))
+        dofmap = dofmap.reshape(n_cells, -1)
+        geom_conn = np.asarray(mesh.geometry.dofmap, dtype=np.int32).reshape(n_cells, -1)
+        nv = geom_conn.shape[1]
+        if nv not in (3, 4):
+            raise ValueError("PlaneScalarMesh.from_dolfinx needs a first-order triangle or quadrilateral geometry (no curved cells)")
+        cell = basix.CellType.triangle if nv == 3 else basix.CellType.quadrilateral
+        pts, _ = basix.make_quadrature(cell, int(quadrature_degree))
+        pts = np.asarray(pts)
+
+        def tables(element):
+            tab = np.asarray(element.tabulate(1, pts))
+            if tab.ndim == 4:
+                tab = tab[..., 0]
+            return np.ascontiguousarray(tab[0]), np.ascontiguousarray(tab[1:3].transpose(1, 2, 0))
+
+        _, geom_dphi = tables(basix.create_element(basix.ElementFamily.P, cell, 1))
+        phi, dphi = tables(V.element.basix_element)
+        n_dofs = V.dofmap.index_map.size_local + V.dofmap.index_map.num_ghosts
+        if cells is not None:
+            geom_conn, dofmap = geom_conn[np.asarray(cells)], dofmap[np.asarray(cells)]
+        return cls(np.asarray(mesh.geometry.x), geom_conn, dofmap, n_dofs, geom_dphi, phi, dphi, device=device)

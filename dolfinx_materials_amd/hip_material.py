@@ -125,7 +125,8 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_FS_SINGLE_CRYSTAL_FCC:
             raise ValueError("the finite-strain single-crystal tangent dP/dF is 81 independent numbers: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for this law; use 'full'")
-        if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_HEAT_STATIONARY, _lib.LAW_HEAT_PHASE_CHANGE):
+        if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_HEAT_STATIONARY, _lib.LAW_HEAT_PHASE_CHANGE,
+                                                                           _lib.LAW_HEAT_STATIONARY_2D, _lib.LAW_HEAT_PHASE_CHANGE_2D):
             raise ValueError("the heat-transfer tangent is several blocks (flux / gradient, flux / temperature, enthalpy / temperature), not "
                              f"a symmetric 6x6: no packed tangent record (tangent_layout={tangent_layout!r}) exists for these laws; use 'full'")
         if tangent_layout != "full" and getattr(behavior, "law", None) in (_lib.LAW_PS_QUADRATIC, _lib.LAW_PS_POLYGON):
@@ -1138,7 +1139,11 @@ class HIPMaterial:
         :class:`~dolfinx_materials_amd.gradient.PlaneMesh`):
         only ``u`` crosses PCIe on the way in (the step before the path,
         ``quadrature_function.py:45-51``).  The 4-wide plane-strain laws and the 3-wide plane-stress laws take a two-dimensional
-        mesh (``mesh.tdim == 2``), whose gradient kernel writes their 4- or 3-wide strain; any other mesh is refused for them."""
+        mesh (``mesh.tdim == 2``), whose gradient kernel writes their 4- or 3-wide strain; any other mesh is refused for them.
+
+        The heat-transfer laws of ``hypothesis="plane_strain"`` take a :class:`~dolfinx_materials_amd.gradient.PlaneScalarMesh` and the
+        NODAL TEMPERATURE as ``u`` (``T.x.array``): gradient and temperature of a point are those of the interpolated field, and the
+        material's own ``Temperature`` (``update_external_state_variable``) is neither read nor changed by such a call."""
         self._require()   # the mesh lives on one GPU
         self._refuse_with_row_deliveries("integrate_displacement")
         nf, ng = self._info.n_flux, self._info.n_grad

@@ -695,7 +695,10 @@ class FCCMericCailletaudFiniteStrainSingleCrystalViscoPlasticity(FiniteStrainBeh
 class HeatTransferBehavior(Behavior):
     """Base of the heat-transfer laws: gradient ``TemperatureGradient`` (3), flux ``HeatFlux`` (3) and one external state variable,
     ``Temperature``, the value at the end of the step (``HIPMaterial.update_external_state_variable``).  The gradient is 3 wide
-    whatever the dimension of the problem: a 2-D caller pads ``grad(T)`` with a zero."""
+    under the default hypothesis: a 2-D caller pads ``grad(T)`` with a zero.  ``hypothesis="plane_strain"`` (what the reference's
+    heat-transfer demos load their law with, ``MFrontMaterial(..., hypothesis="plane_strain")``): gradient and flux are 2 wide,
+    ``[d/dx, d/dy]``, the tangent blocks ``(2, 2)``, ``(2, 1)`` [``(1, 1)``]; with a :class:`gradient.PlaneScalarMesh` such a
+    material is updated from the nodal temperature (``HIPMaterial.integrate_displacement*``)."""
 
     gradient_name = "TemperatureGradient"
     flux_name = "HeatFlux"
@@ -703,6 +706,15 @@ class HeatTransferBehavior(Behavior):
     nflux = 3
     external_state_variables = {"Temperature": 1}
     NAMES = ()
+
+    #: the law of ``hypothesis="plane_strain"``
+    law_2d = None
+
+    def _set_hypothesis(self, hypothesis):
+        self.hypothesis = _check_hypothesis(hypothesis)
+        if hypothesis == "plane_strain":
+            self.ngrad = self.nflux = 2
+            self.law = self.law_2d
 
     def validate(self):
         for k in self.NAMES:
@@ -731,20 +743,22 @@ class StationaryHeatTransfer(HeatTransferBehavior):
     (MFront does not refuse it either)."""
 
     law = _lib.LAW_HEAT_STATIONARY
+    law_2d = _lib.LAW_HEAT_STATIONARY_2D
     NAMES = ("A", "B")
     MFRONT_DEFAULTS = {"A": 0.0375, "B": 2.165e-4}
 
-    def __init__(self, A: float = MFRONT_DEFAULTS["A"], B: float = MFRONT_DEFAULTS["B"]):
+    def __init__(self, A: float = MFRONT_DEFAULTS["A"], B: float = MFRONT_DEFAULTS["B"], hypothesis: str = "3d"):
+        self._set_hypothesis(hypothesis)
         self.A, self.B = A, B
         self.validate()
 
     @classmethod
-    def from_mfront_properties(cls, props: dict | None = None):
+    def from_mfront_properties(cls, props: dict | None = None, hypothesis: str = "3d"):
         props = dict(props or {})
         extra = set(props) - set(cls.NAMES)
         if extra:
             raise ValueError(f"stationary heat transfer parameters: unknown {sorted(extra)}")
-        return cls(**{**cls.MFRONT_DEFAULTS, **props})
+        return cls(**{**cls.MFRONT_DEFAULTS, **props}, hypothesis=hypothesis)
 
 
 class HeatTransferPhaseChange(HeatTransferBehavior):
@@ -755,6 +769,7 @@ class HeatTransferPhaseChange(HeatTransferBehavior):
     entry names."""
 
     law = _lib.LAW_HEAT_PHASE_CHANGE
+    law_2d = _lib.LAW_HEAT_PHASE_CHANGE_2D
     NAMES = ("MeltingTemperature", "SolidConductivity", "SolidHeatCapacity", "LiquidConductivity", "LiquidHeatCapacity", "FusionEnthalpy",
              "Tsmooth")
     MFRONT_DEFAULTS = {"MeltingTemperature": 933.15, "SolidConductivity": 210.0, "SolidHeatCapacity": 3.0e6, "LiquidConductivity": 95.0,
@@ -763,7 +778,8 @@ class HeatTransferPhaseChange(HeatTransferBehavior):
     def __init__(self, MeltingTemperature=MFRONT_DEFAULTS["MeltingTemperature"], SolidConductivity=MFRONT_DEFAULTS["SolidConductivity"],
                  SolidHeatCapacity=MFRONT_DEFAULTS["SolidHeatCapacity"], LiquidConductivity=MFRONT_DEFAULTS["LiquidConductivity"],
                  LiquidHeatCapacity=MFRONT_DEFAULTS["LiquidHeatCapacity"], FusionEnthalpy=MFRONT_DEFAULTS["FusionEnthalpy"],
-                 Tsmooth=MFRONT_DEFAULTS["Tsmooth"]):
+                 Tsmooth=MFRONT_DEFAULTS["Tsmooth"], hypothesis: str = "3d"):
+        self._set_hypothesis(hypothesis)
         for k, v in zip(self.NAMES, (MeltingTemperature, SolidConductivity, SolidHeatCapacity, LiquidConductivity, LiquidHeatCapacity,
                                      FusionEnthalpy, Tsmooth)):
             setattr(self, k, v)
@@ -775,13 +791,13 @@ class HeatTransferPhaseChange(HeatTransferBehavior):
             raise ValueError(f"HeatTransferPhaseChange: Tsmooth must be > 0, got {self.Tsmooth}")
 
     @classmethod
-    def from_mfront_properties(cls, props: dict | None = None):
+    def from_mfront_properties(cls, props: dict | None = None, hypothesis: str = "3d"):
         """Parameters keyed by the file's entry names; those not given keep the file's defaults."""
         props = dict(props or {})
         extra = set(props) - set(cls.NAMES)
         if extra:
             raise ValueError(f"heat transfer with phase change parameters: unknown {sorted(extra)}")
-        return cls(**{**cls.MFRONT_DEFAULTS, **props})
+        return cls(**{**cls.MFRONT_DEFAULTS, **props}, hypothesis=hypothesis)
 
 
 class PlaneStressBehavior(Behavior):

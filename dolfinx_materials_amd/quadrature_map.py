@@ -357,7 +357,11 @@ class AcceleratedUpdate:
         ``lambda: u.x.array`` is the callable): only that vector is uploaded per update, the step before the path
         (``quadrature_function.py:45-51``) runs inside the update kernel.  ``mesh`` holds the cells of this map in its
         order: all cells of the mesh for a map over everything, the connectivity restricted to ``self.cells`` for a map
-        over a subset (``Hex8Mesh(coords, conn[cells])``)."""
+        over a subset (``Hex8Mesh(coords, conn[cells])``).
+
+        With a heat-transfer material of ``hypothesis="plane_strain"`` the mesh is a ``gradient.PlaneScalarMesh`` and the callable
+        returns the nodal temperature (``lambda: T.x.array``): ``update()`` then runs through the nodal form, the kernel interpolates
+        ``T`` and ``grad(T)`` at its points, and a registered ``Temperature`` variable is not uploaded."""
         plan = self._accel_plan()
         if mesh.npoints != plan.npoints or not (plan.identity or plan.row_outputs):
             raise ValueError("device gradient evaluation needs a mesh object with exactly the cells of this map, in its order")
@@ -445,7 +449,12 @@ class AcceleratedUpdate:
 
     def update_external_state_variables(self):
         """``quadrature_map.py:220-225`` with the material handed the rows of this map's own points."""
+        # a scalar mesh (gradient.PlaneScalarMesh) interpolates its own field at the points: a variable of that name is not uploaded
+        plan = self._accel_plan()
+        nodal = getattr(plan.device_gradient[0], "nodal_variable", None) if plan.device_gradient is not None else None
         for name, esv in self.external_state_variables.items():
+            if name == nodal:
+                continue
             esv.eval(self.cells)
             self.material.update_external_state_variable(name, self._accel_own_rows(name, esv))
 

@@ -290,7 +290,32 @@ enum {
    * algorithmic_bytes_per_point = 168: strain 24 + state 24 in, stress 24 + tangent 72 + state 24 out.
    * params = [E, nu, sig0, a, tangent], all finite, E > 0, -1 < nu < 1, sig0 > 0, 2 <= a <= 100, tangent 0 or 1 */
   DXM_LAW_PS_HOSFORD = 33,   /* id 32 is not assigned */
-  DXM_LAW_COUNT = 34
+  /* (before ids 35 and 36 the table ended here, with DXM_LAW_COUNT = 34
+   * and DXM_ABI_VERSION 6, which stays)
+   * DXM_LAW_HEAT_STATIONARY and DXM_LAW_HEAT_PHASE_CHANGE under a two-dimensional hypothesis: what the reference's heat-transfer
+   * demos ask for (demos/mfront/heat_transfer/nonlinear_heat_transfer.py:247 and phase_change.py:265 load their law with
+   * hypothesis="plane_strain" and register ufl.grad(T) as a 2-wide TemperatureGradient).  Gradient TemperatureGradient (2) =
+   * [dT/dx, dT/dy], flux HeatFlux (2); the external state variable Temperature with the setters and the default of the 3-wide laws;
+   * the phase-change law has the internal state variable Enthalpy (1).  Parameters and their validation are those of the 3-wide law.
+   * Tangent, DXM_TANGENT_FULL only, the blocks of dxm_law_blocks_get one after the other: (HeatFlux, TemperatureGradient) 2 x 2 =
+   * [-k, 0, 0, -k] with both zeros written, (HeatFlux, Temperature) 2 x 1, and for the phase-change law (Enthalpy, Temperature) 1 x 1:
+   * 6 / 7 doubles per point.  The arithmetic is that of the 3-wide kernels, operation for operation: flux, tangent entries, enthalpy
+   * and dxm_stats.n_nan equal those of the 3-wide law on [g0, g1, 0] bit for bit.
+   * No material frame, no per-point parameter fields, not served by a custom-hardening build.
+   * THE DISPLACEMENT FORMS (dxm_integrate_displacement, _rows, _device) take these laws with a scalar mesh
+   * (dxm_mesh_create_plane_scalar) and the NODAL TEMPERATURE vector in place of the displacement: gradient and temperature of a
+   * point are those of the interpolated field, T = sum_m T_m phi_m and grad(T) = Ji^T sum_m T_m dphi_m.  In these calls the handle's
+   * own external state (uniform value or field, dxm_set_external_state*) is neither read nor changed.  With option fused_gradient 1
+   * (default) the update kernel evaluates both at its own points and no gradient or temperature array exists; with 0 the kernel of
+   * dxm_mesh_scalar_gradient_device fills scratch arrays owned by the handle and the update kernel reads them on the same stream:
+   * both deliver the same bits.  Refused, with a sentence and the handle left as it was: these laws with a mesh that carries a
+   * displacement, any other law with a scalar mesh, a mesh whose number of Gauss points is not the handle's.
+   * algorithmic_bytes_per_point = 64 (gradient 16 + tangent 48; the flux, 16 more, is written too) / 80 (+ 8 of tangent + 8 of
+   * Enthalpy); dxm_algorithmic_bytes adds 8 with a temperature per point.
+   * params = [A, B] / [Tm, ks, cs, kl, cl, dhsl, Tsmooth] */
+  DXM_LAW_HEAT_STATIONARY_2D = 35,   /* id 34 is not assigned */
+  DXM_LAW_HEAT_PHASE_CHANGE_2D = 36,
+  DXM_LAW_COUNT = 37
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */
@@ -684,10 +709,20 @@ dxm_mesh* dxm_mesh_create_simplex(int tdim, const double* coords, int64_t n_vert
 dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
                                 const int32_t* dofmap, int nd, int64_t n_dofs,
                                 const double* geom_dphi, const double* dphi, int nqp, int device);
+/* A SCALAR Lagrange field (a temperature) of any order on the same cells: ONE value per dof, dxm_mesh_displacement_size = n_dofs.
+ * phi (nqp, nd) holds the values of the field's nd shape functions at the Gauss points beside their derivatives dphi (nqp, nd, 2);
+ * the other arguments, the bounds and the host-side checks are those of dxm_mesh_create_plane, in the same order and with the same
+ * sentences (arguments; indices; det J; the device), all reached without a GPU; after the arguments it also refuses a table entry
+ * (phi, dphi, geom_dphi) that is not finite.  The mesh serves dxm_mesh_scalar_gradient_device and, with DXM_LAW_HEAT_STATIONARY_2D /
+ * DXM_LAW_HEAT_PHASE_CHANGE_2D, the displacement forms, which then take the nodal temperature; it refuses every kind of
+ * dxm_mesh_gradient_device.  A custom-hardening build creates such a mesh and refuses both uses. */
+dxm_mesh* dxm_mesh_create_plane_scalar(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
+                                       const int32_t* dofmap, int nd, int64_t n_dofs,
+                                       const double* geom_dphi, const double* phi, const double* dphi, int nqp, int device);
 int dxm_mesh_destroy(dxm_mesh* mesh);
 int64_t dxm_mesh_npoints(const dxm_mesh* mesh);
 /* doubles in the displacement vector the mesh expects (3 per node; tdim per dof for dxm_mesh_create_simplex; 2 per dof for
- * dxm_mesh_create_plane) */
+ * dxm_mesh_create_plane; 1 per dof for dxm_mesh_create_plane_scalar) */
 int64_t dxm_mesh_displacement_size(const dxm_mesh* mesh);
 /* kind 0: Mandel strain (6); kind 1: deformation gradient F = I + grad u (9); on two-dimensional meshes only
  * (dxm_mesh_create_plane, dxm_mesh_create_simplex with tdim 2; any other mesh refuses them), with H[i][a] = du_i / dX_a and
@@ -696,6 +731,12 @@ int64_t dxm_mesh_displacement_size(const dxm_mesh* mesh);
  * (npoints, 6|9|4|3).  Asynchronous on hip_stream. */
 int dxm_mesh_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, double* grad_dev,
                              void* hip_stream);
+/* On a scalar mesh: grad(T) = Ji^T sum_m T_m dphi_m into grad_dev (npoints, 2; 16-byte aligned) and, unless value_dev is NULL,
+ * T = sum_m T_m phi_m into value_dev (npoints) at the Gauss points, from the nodal values t_dev (n_dofs doubles); point c * nqp + q
+ * is Gauss point q of cell c.  All device memory; asynchronous on hip_stream.  Every operation is individually rounded, the sums
+ * run in the dofmap's local order: the update kernels of the nodal forms evaluate the same text and deliver the same bits.  A mesh
+ * that carries a displacement refuses (< 0, message); a refused call writes nothing. */
+int dxm_mesh_scalar_gradient_device(dxm_mesh* mesh, const double* t_dev, double* grad_dev, double* value_dev, void* hip_stream);
 /* dxm_integrate with the gradient computed on the device from the host displacement vector
  * u_host (dxm_mesh_displacement_size doubles): uploads u, evaluates the law's gradient, runs the constitutive update,
  * downloads flux / isv / tangent (any may be NULL).  mesh npoints must equal the handle's. */

@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2 ps_hosford]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2 ps_hosford heat_plane]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -44,6 +44,9 @@ and law 27 / 28 (plane strain, the strain embedded as [xx, yy, 0, sqrt(2) xy]; 2
 ps_hosford: plane-stress Hosford plasticity (id 33, 168 B/point) at the cvxpy demo's parameters and a = 10, both tangent modes, on wholly
 elastic, mixed and fully yielded batches, next to ps_vonmises (law 23, the same bytes) of the same process on the same strains
 (bench_plane_stress_hosford).
+heat_plane: the two-dimensional heat-transfer laws (ids 35, 36; 64 / 80 B/point) next to laws 16 / 17 of the same process on the padded
+gradient, their nodal form on a Q1 quadrilateral grid at both settings of fused_gradient, and the host form next to the padded 3-wide
+route (bench_heat_plane).
 --blocks-per-cu: the new kernels at each of these grid sizes as well.
 
 --param-fields K [K ...] (j2_linear, j2_voce): after the uniform kernel, the kernel that reads K bound parameter streams
@@ -622,6 +625,113 @@ def bench_plane_stress_hosford(a):
     torch.cuda.empty_cache()
 
 
+def bench_heat_plane(a):
+    """--laws heat_plane: the 2-wide laws 35 / 36 beside the 3-wide laws 16 / 17 OF THIS PROCESS on the padded gradient (array form,
+    uniform temperature and one temperature per point; ratio to the 3-wide time scaled by the bytes, 64/120 and 80/136, + 8 each with a
+    temperature stream); the nodal form on a Q1 grid of 4-point quadrilaterals next to "gradient kernel + array form" (option
+    fused_gradient 0); with --blocks-per-cu the array form at each grid size; and the host form (nodal temperature up) next to the
+    padded 3-wide route through law 16 (gradient and temperature up), time per update and bytes up."""
+    import time
+
+    import torch
+
+    import dolfinx_materials_amd.materials as jm
+    from dolfinx_materials_amd.gradient import PlaneScalarMesh
+    from dolfinx_materials_amd.jaxmat import JAXMaterial
+    from helpers import to_device
+
+    side = max(2, int(round((a.points / 4) ** 0.5)))
+    xs = np.linspace(0.0, 1.0, side + 1)
+    X, Y = np.meshgrid(xs, xs, indexing="ij")
+    coords = np.stack([X.ravel(), Y.ravel()], axis=1)
+    i, j = (v.ravel() for v in np.meshgrid(np.arange(side), np.arange(side), indexing="ij"))
+    idx = lambda di, dj: (i + di) * (side + 1) + (j + dj)   # noqa: E731
+    cells = np.stack([idx(0, 0), idx(1, 0), idx(0, 1), idx(1, 1)], axis=1).astype(np.int32)
+    mesh, xd = PlaneScalarMesh.lagrange(coords, cells, degree=1)
+    n = mesh.npoints
+    st = torch.cuda.current_stream().cuda_stream
+    rng = np.random.default_rng(2026)
+    g2 = rng.normal(size=(n, 2)) * 100.0
+    g = {2: to_device(g2), 3: to_device(np.concatenate([g2, np.zeros((n, 1))], axis=1))}
+    t_nodal = np.ascontiguousarray(933.15 + 3.0 * (xd[:, 0] - 0.5) + 0.02 * rng.standard_normal(len(xd)))
+    t_dev = to_device(t_nodal)
+
+    def timed(call):
+        def once():
+            for _ in range(a.warmup):
+                call()
+            torch.cuda.synchronize()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+            for e0, e1 in ev:
+                e0.record()
+                call()
+                e1.record()
+            torch.cuda.synchronize()
+            return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+        t = [once(), once(), once()]
+        return float(np.median(t)), [round(x, 4) for x in t]
+
+    def line(tag, m, ms, reps, **more):
+        rc, stats = m.stats()
+        ab = m.algorithmic_bytes_per_point
+        r = {"law": tag, "points": n, "kernel": m.kernel_name, "kernel_ms_repeats": reps, "kernel_ms": round(ms, 4), "Mpoints_per_s": round(n / ms / 1e3, 1),
+             "algorithmic_bytes_per_point": ab, "GBs": round(ab * n / ms / 1e6, 1), "frac_of_8TBs": round(ab * n / ms / 1e6 / 8000, 4), "nan": stats["n_nan"], "rc": rc}
+        r.update(more)
+        print(json.dumps(r), flush=True)
+
+    for name, make in (("stationary", lambda hyp: jm.StationaryHeatTransfer(hypothesis=hyp)),
+                       ("phase_change", lambda hyp: jm.HeatTransferPhaseChange.from_mfront_properties({"Tsmooth": 1.0}, hypothesis=hyp))):
+        m3, m2 = JAXMaterial(make("3d")), JAXMaterial(make("plane_strain"))
+        out = {}
+        for m, w in ((m3, 3), (m2, 2)):
+            m.set_data_manager(n)
+            out[w] = (torch.empty((n, w), dtype=torch.float64, device=g[w].device), torch.empty((n, m.tangent_size), dtype=torch.float64, device=g[w].device))
+        Tfield = rng.uniform(600.0, 1300.0, n) if name == "phase_change" else rng.uniform(300.0, 1500.0, n)
+        for tag in ("uniformT", "fieldT"):
+            wide = {}
+            for m, w in ((m3, 3), (m2, 2)):
+                m.update_external_state_variable("Temperature", (933.4 if name == "phase_change" else 700.0) if tag == "uniformT" else Tfield)
+                ms, reps = timed(lambda m=m, w=w: m.integrate_device(g[w].data_ptr(), out[w][0].data_ptr(), out[w][1].data_ptr(), st))
+                if w == 3:
+                    wide = dict(ms=ms, ab=m.algorithmic_bytes_per_point, reps=reps)
+                    line(f"heat_{name}+{tag}", m, ms, reps)
+                else:
+                    scaled = wide["ms"] * m.algorithmic_bytes_per_point / wide["ab"]
+                    line(f"heat_plane_{name}+{tag}", m, ms, reps, wide_ms=round(wide["ms"], 4), wide_ms_repeats=wide["reps"],
+                         byte_ratio_to_wide=round(m.algorithmic_bytes_per_point / wide["ab"], 4), wide_scaled_ms=round(scaled, 4),
+                         ratio_to_yardstick=round(ms / scaled, 3))
+        # the nodal form: one launch, and "gradient kernel + array form" through the handle's scratch
+        for fused in (1, 0):
+            m2.set_option("fused_gradient", fused)
+            ms, reps = timed(lambda: m2.integrate_displacement_device(mesh, t_dev.data_ptr(), out[2][0].data_ptr(), out[2][1].data_ptr(), st))
+            line(f"heat_plane_{name}+nodal+fused{fused}", m2, ms, reps, n_dofs=int(mesh.n_dofs))
+        m2.set_option("fused_gradient", 1)
+        if name == "stationary":
+            # the host forms: the nodal temperature up (n_dofs x 8 B) against grad(T) padded and T up through law 16 (32 B/point)
+            g3_host, T_host = np.ascontiguousarray(np.concatenate([g2, np.zeros((n, 1))], axis=1)), np.ascontiguousarray(Tfield)
+            for tag, call, up in (("nodal", lambda: m2.integrate_displacement(mesh, t_nodal), 8 * int(mesh.n_dofs)),
+                                  ("padded3", lambda: (m3.update_external_state_variable("Temperature", T_host), m3.integrate(g3_host)), 32 * n)):
+                for _ in range(3):
+                    call()
+                ts = []
+                for _ in range(5):
+                    t0 = time.perf_counter()
+                    call()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                print(json.dumps({"law": f"heat_plane_stationary+host+{tag}", "points": n, "update_ms_repeats": [round(x, 3) for x in ts],
+                                  "update_ms": round(float(np.median(ts)), 3), "bytes_up": up}), flush=True)
+            del g3_host, T_host
+        for bpc in a.blocks_per_cu or ():      # last, the handle keeps the grid: the array form with a temperature stream at each grid size
+            m2.set_option("blocks_per_cu", bpc)
+            ms, reps = timed(lambda: m2.integrate_device(g[2].data_ptr(), out[2][0].data_ptr(), out[2][1].data_ptr(), st))
+            line(f"heat_plane_{name}+fieldT+bpc{bpc}", m2, ms, reps)
+        m3.close()
+        m2.close()
+        del out
+        torch.cuda.empty_cache()
+    mesh.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -631,12 +741,12 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0, help="also time the plain-C oracle on this many points")
     ap.add_argument("--sym", action="store_true", help="symmetric-packed tangent (small-strain laws)")
     ap.add_argument("--blocks-per-cu", type=int, nargs="+", default=None,
-                    help="ramberg_osgood, plane_strain, ps_j2, ps_hosford: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
+                    help="ramberg_osgood, plane_strain, ps_j2, ps_hosford, heat_plane: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
-                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws or
+                         "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "heat_plane" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws or
                          any(law.startswith("ps_") for law in a.laws) or "plane_strain" in a.laws):   # (ps_j2 among them)
         ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal, heat-transfer or logarithmic-strain law")
     import torch
@@ -674,6 +784,9 @@ def main():
             continue
         if law == "ps_hosford":   # law 33 beside law 23 of this process: six lines
             bench_plane_stress_hosford(a)
+            continue
+        if law == "heat_plane":   # laws 35 / 36 beside laws 16 / 17 of this process, the nodal forms, the host form
+            bench_heat_plane(a)
             continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)

@@ -32,7 +32,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 UNITS = ("dxmat", "ramberg_osgood", "param_fields", "hyperelastic", "hosford", "orthotropic")
 # the units added since (--all-units): compared with the parent's where the parent has them
 LATER_UNITS = ("small_strain_clean", "single_crystal", "heat_transfer", "log_strain", "fs_single_crystal", "plane_stress",
-               "plane_strain", "plane_stress_j2", "plane_stress_hosford", "plane_gradient", "small_strain_packed")
+               "plane_strain", "plane_stress_j2", "plane_stress_hosford", "plane_gradient", "small_strain_packed",
+               "heat_plane")
 MAX_VGPRS = 128
 J2_STATIC_LDS = 30848     # small_strain.hpp: 4 waves x (64 x 6 + 64 x 9) doubles + the 4 x 4 status words
 
