@@ -170,6 +170,40 @@ def restrict_plane_strain_tangent(C66):
     return np.ascontiguousarray(C66[..., idx, :][..., :, idx])
 
 
+#: positions, in the non-symmetric 9-vector, of the five components [00, 11, 22, 01, 10] a plane deformation gradient has
+#: (``utils.py:168-172``: ``nonsymmetric_tensor_to_vector`` of a 2x2 tensor with its ``T22``)
+PLANE_F_IDX = (0, 1, 2, 3, 4)
+
+
+def embed_plane_F(v5):
+    """(..., 5) ``[F00, F11, F22, F01, F10]`` -> (..., 9) ``[11, 22, 33, 12, 21, 13, 31, 23, 32]`` with zero out-of-plane shears: the
+    deformation gradient ``[[F00, F01, 0], [F10, F11, 0], [0, 0, F22]]`` of a plane-strain state."""
+    v5 = np.asarray(v5, dtype=np.float64)
+    if v5.shape[-1] != 5:
+        raise ValueError(f"a plane deformation gradient has 5 components [F00, F11, F22, F01, F10], got shape {v5.shape}")
+    out = np.zeros(v5.shape[:-1] + (9,))
+    out[..., list(PLANE_F_IDX)] = v5
+    return out
+
+
+def restrict_plane_F(v9):
+    """(..., 9) -> (..., 5) ``[00, 11, 22, 01, 10]``: the components a plane non-symmetric tensor has (the other four are zero in
+    such a state and are dropped, whatever they hold)."""
+    v9 = np.asarray(v9, dtype=np.float64)
+    if v9.shape[-1] != 9:
+        raise ValueError(f"a non-symmetric 9-vector has 9 components, got shape {v9.shape}")
+    return np.ascontiguousarray(v9[..., list(PLANE_F_IDX)])
+
+
+def restrict_plane_F_tangent(A99):
+    """(..., 9, 9) -> (..., 5, 5): rows and columns ``[0, 1, 2, 3, 4]`` of a 9-wide ``dP/dF``, the block of the plane-strain law."""
+    A99 = np.asarray(A99, dtype=np.float64)
+    if A99.shape[-2:] != (9, 9):
+        raise ValueError(f"a 9-wide tangent block is (..., 9, 9), got shape {A99.shape}")
+    idx = list(PLANE_F_IDX)
+    return np.ascontiguousarray(A99[..., idx, :][..., :, idx])
+
+
 def plane_stress_axial_strain(E, nu, stress, epsp):
     """The out-of-plane strain of a plane-stress state from the outputs of plane-stress J2 plasticity (``[xx, yy, sqrt(2) xy]``):
     ``eps_zz = -nu / E (s_xx + s_yy) - (epsp_xx + epsp_yy)`` -- the elastic part from ``sig_zz = 0``, the plastic part from the

@@ -44,6 +44,7 @@
 #include "plane_stress_hosford.hpp"
 #include "plane_gradient.hpp"
 #include "heat_plane.hpp"
+#include "ogden_plane.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -480,6 +481,7 @@ static void launch_ps_polygon(const LaunchArgs& a);
 template <int LAW> static void launch_plane_strain(const LaunchArgs& a);
 template <int HARD> static void launch_plane_stress_j2(const LaunchArgs& a);
 static void launch_ps_hosford(const LaunchArgs& a);
+static void launch_ogden_pe(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -1130,7 +1132,40 @@ constexpr LawDesc law_heat_phase_change_2d() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32 and 34 are not assigned and stay empty rows (law_known)
+// Ogden under the plane-strain hypothesis (ogden_plane.hip): the 5-wide F in (40 B), PK1 (40) + the 5x5 dP/dF (200) + the isochoric PK2
+// stress as [xx, yy, zz, sqrt(2) xy] (32) out: 312 B/point; the state is written, never read.  Parameters, their checks and the kernel's
+// record are those of law 7 (build_ogden).  No external state variable is declared (n_ext = 0)
+constexpr LawDesc law_ogden_pe() {
+  LawDesc d{};
+  d.id = DXM_LAW_OGDEN_PE;
+  d.n_grad = d.n_flux = OGP_DIM;
+  d.n_params = d.n_params_custom = 3;
+  d.n_isv_fields = d.n_fields = 1;
+  state_field(d, 0, "PK2Stress", OGP_NSLOTS, 0);
+  d.n_slots = OGP_NSLOTS;
+  d.alg_bytes = 312;
+  d.kernel = "ogden_plane_kernel";
+  d.no_fields = "per-point parameter fields are not served for plane-strain Ogden hyperelasticity: the kernel takes its exponents as "
+                "per-handle constants";
+  d.build = build_ogden;
+  d.stock_only = "plane-strain Ogden hyperelasticity has no hardening law: it is served by the stock libdxmat, not by a custom-hardening "
+                 "build";
+  d.residency_kernel = DXM_STOCK_ONLY(ogden_plane_kernel_fn);
+  d.blocks_per_cu = OGP_BLOCKS_PER_CU;   // ogden_plane.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.set_refusal = d.launch_refusal = "the plane-strain Ogden tangent dP/dF is a 5x5 block of 25 entries, not a symmetric 6x6: only "
+                                     "DXM_TANGENT_FULL is available, no packed record (sym / coef / pack4) exists for this law";
+  d.no_fused = d.no_displacement = "plane-strain Ogden hyperelasticity takes the 5-wide deformation gradient [F00, F11, F22, F01, F10]: "
+                                   "the mesh gradient kernels produce the 9-wide F, so the displacement forms "
+                                   "(dxm_integrate_displacement*) and the fused displacement gradient are not served; pass the 5-wide F "
+                                   "[1 + H00, 1 + H11, 1, H01, H10] of the displacement gradient H as an array";
+  d.no_frame = "plane-strain Ogden hyperelasticity is isotropic (a function of the principal stretches): a material frame changes "
+               "nothing in its update";
+  d.launch = DXM_STOCK_ONLY(launch_ogden_pe);   // ogden_plane.hip: F from the (N, 5) array, the full 5x5 tangent
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34 and 37 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
@@ -1138,6 +1173,7 @@ static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_ps_quadratic(), law_ps_polygon(), {}, law_pe_elastic(), law_pe_j2_linear(), law_pe_j2_voce(), {},
     law_ps_j2_linear(), law_ps_j2_voce(), {}, law_ps_hosford(),
     {}, law_heat_stationary_2d(), law_heat_phase_change_2d(),
+    {}, law_ogden_pe(),
 };
 
 constexpr bool rows_in_place() {
@@ -1148,8 +1184,8 @@ constexpr bool rows_in_place() {
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
                   !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel && !kLaws[29].kernel &&
-                  !kLaws[32].kernel && !kLaws[34].kernel,
-              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32 and 34 are not assigned");
+                  !kLaws[32].kernel && !kLaws[34].kernel && !kLaws[37].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34 and 37 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -2052,6 +2088,11 @@ static void launch_ramberg_osgood(const LaunchArgs& a) {
 static void launch_ogden(const LaunchArgs& a) {
   dxm_material* m = a.m;
   ogden_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[1] + a.off, m->ld, a.flux, a.ct, m->d_stats + a.stats_off);
+}
+
+static void launch_ogden_pe(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  ogden_plane_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[1] + a.off, m->ld, a.flux, a.ct, m->d_stats + a.stats_off);
 }
 
 static void launch_hosford(const LaunchArgs& a) {

@@ -110,6 +110,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_OGDEN:
             raise ValueError("the Ogden kernel writes the full 81-entry dP/dF only: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for this law")
+        if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_OGDEN_PE:
+            raise ValueError("the plane-strain Ogden tangent dP/dF is a 5x5 block of 25 entries, not a symmetric 6x6: no packed tangent "
+                             f"record (tangent_layout={tangent_layout!r}) exists for this law; use 'full'")
         if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_LOG_STRAIN_J2:
             raise ValueError("the logarithmic-strain plasticity kernel writes the full 81-entry dP/dF only: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for this law")
@@ -537,9 +540,15 @@ class HIPMaterial:
         if isv and self._out_isv is None:
             self._out_isv = self._own("isv", (self._n, self._info.n_isv_total))
 
+    @property
+    def _gradient_is_F(self):
+        """The gradient is a deformation gradient, whose natural state is the identity: the 9-vector, or the 5-vector
+        ``[F00, F11, F22, F01, F10]`` of plane-strain Ogden (the diagonal comes first in both)."""
+        return self._info.n_grad == 9 or self.behavior.law == _lib.LAW_OGDEN_PE
+
     def _initial_gradient(self):
         g = np.zeros((self._n, self._info.n_grad))
-        if self._info.n_grad == 9:
+        if self._gradient_is_F:
             g[:, :3] = 1.0  # F = I
         return g
 
@@ -904,7 +913,7 @@ class HIPMaterial:
         (``finite_strain_elastoplasticity.py:181``)."""
         n = int(n)
         g = np.zeros((n, int(self._info.n_grad)))
-        if self._info.n_grad == 9:
+        if self._gradient_is_F:
             g[:, :3] = 1.0
         out = {self._gname: g, self._fname: np.zeros((n, int(self._info.n_flux)))}
         for name, dim in self.internal_state_variables.items():
@@ -974,7 +983,7 @@ class HIPMaterial:
                 raise DxmError(f"explicit-state update of {n} points: external state variable {name!r} is a field over the {self._n} Gauss "
                                "points of this material, so the call must pass one gradient row per Gauss point")
             sc.update_external_state_variable(name, value)
-        wanted = list(self.internal_state_variables) + ([self._gname] if ng == 9 else [])
+        wanted = list(self.internal_state_variables) + ([self._gname] if self._gradient_is_F else [])
         sc.set_initial_state_dict({k: start[k] for k in wanted})
         flux, isv, ct = sc.integrate(g, self._dt(dt))
         new_state = {self._gname: g.copy(), self._fname: np.array(flux)}

@@ -307,14 +307,25 @@ class OgdenHyperelasticity(FiniteStrainBehavior):
     ``JAXMaterial(OgdenHyperelasticity(...))`` stands where the reference's hyperelasticity demo uses
     ``MFrontMaterial(lib, "Ogden")``: gradient ``DeformationGradient`` (9), flux ``FirstPiolaKirchhoffStress`` (9), tangent block
     ``(9, 9)``; :meth:`from_mfront_properties` takes the ``material_properties`` dictionary of that call.  Full tangent only; the
-    displacement forms need option ``fused_gradient`` off (no fused kernel for this law)."""
+    displacement forms need option ``fused_gradient`` off (no fused kernel for this law).
+
+    ``hypothesis="plane_strain"`` (``MFrontMaterial(lib, "Ogden", hypothesis="plane_strain")``): the gradient is the 5-vector
+    ``[F00, F11, F22, F01, F10]`` of a 2x2 tensor with its out-of-plane stretch (``utils.py:168-172``), the flux the 5-wide PK1 in the
+    same order, the tangent block ``(5, 5)`` and ``PK2Stress`` the 4-vector ``[xx, yy, zz, sqrt(2) xy]``: the 9-wide law on the embedded
+    ``F``, restricted (``conventions.embed_plane_F`` / ``restrict_plane_F`` / ``restrict_plane_F_tangent``).  ``F22`` is read, not
+    assumed to be 1.  F is passed as an array: the displacement forms are not served under this hypothesis."""
 
     law = _lib.LAW_OGDEN
     gradient_name = "DeformationGradient"
     flux_name = "FirstPiolaKirchhoffStress"
     MFRONT_DEFAULTS = {"alpha": 28.8, "mu": 27778.0, "K": 69444444.0}
 
-    def __init__(self, mu: float = MFRONT_DEFAULTS["mu"], alpha: float = MFRONT_DEFAULTS["alpha"], K: float = MFRONT_DEFAULTS["K"]):
+    def __init__(self, mu: float = MFRONT_DEFAULTS["mu"], alpha: float = MFRONT_DEFAULTS["alpha"], K: float = MFRONT_DEFAULTS["K"],
+                 hypothesis: str = "3d"):
+        if _check_hypothesis(hypothesis) == "plane_strain":
+            self.hypothesis = hypothesis
+            self.law = _lib.LAW_OGDEN_PE
+            self.ngrad = self.nflux = 5
         self.mu = float(mu)
         self.alpha = float(alpha)
         self.K = float(K)
@@ -322,14 +333,14 @@ class OgdenHyperelasticity(FiniteStrainBehavior):
             raise ValueError(f"Ogden: alpha must be non-zero, mu and K > 0 (all finite); got alpha={alpha}, mu={mu}, K={K}")
 
     @classmethod
-    def from_mfront_properties(cls, props: dict | None = None):
+    def from_mfront_properties(cls, props: dict | None = None, hypothesis: str = "3d"):
         """``material_properties`` of ``MFrontMaterial(..., "Ogden", material_properties=...)``: any of ``alpha``, ``mu``, ``K``;
-        what is absent keeps the behaviour file's default, as MFront parameters do."""
+        what is absent keeps the behaviour file's default, as MFront parameters do.  ``hypothesis``: that of the same call."""
         props = dict(props or {})
         extra = set(props) - set(cls.MFRONT_DEFAULTS)
         if extra:
             raise ValueError(f"Ogden material properties: unknown {sorted(extra)} (the behaviour has alpha, mu, K)")
-        return cls(**{**cls.MFRONT_DEFAULTS, **{k: float(v) for k, v in props.items()}})
+        return cls(**{**cls.MFRONT_DEFAULTS, **{k: float(v) for k, v in props.items()}}, hypothesis=hypothesis)
 
     def params(self):
         return [self.alpha, self.mu, self.K]

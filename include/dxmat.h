@@ -315,7 +315,28 @@ enum {
    * params = [A, B] / [Tm, ks, cs, kl, cl, dhsl, Tsmooth] */
   DXM_LAW_HEAT_STATIONARY_2D = 35,   /* id 34 is not assigned */
   DXM_LAW_HEAT_PHASE_CHANGE_2D = 36,
-  DXM_LAW_COUNT = 37
+  /* (before id 38 the table ended here, with
+   * DXM_LAW_COUNT = 37
+   * and DXM_ABI_VERSION 6, which stays)
+   * DXM_LAW_OGDEN under the plane-strain hypothesis: what MFrontMaterial(lib, "Ogden", hypothesis="plane_strain") exchanges.
+   * Gradient DeformationGradient (5) = [F00, F11, F22, F01, F10], the 5-vector utils.py:168-172 builds from a 2x2 tensor with its
+   * out-of-plane stretch; flux FirstPiolaKirchhoffStress (5) in the same order; tangent dP/dF 5 x 5, row-major, 25 doubles per
+   * point.  BY DEFINITION the law is DXM_LAW_OGDEN evaluated on F9 = [F00, F11, F22, F01, F10, 0, 0, 0, 0], of which are kept:
+   * components 0..4 of PK1 (the other four are exactly zero for such an F), rows and columns 0..4 of the 9 x 9 dP/dF (the dropped
+   * cross derivatives vanish by the reflection z -> -z) and the components [xx, yy, zz, sqrt(2) xy] of the internal state variable
+   * PK2Stress (4, MFront's 2-D symmetric tensor; the isochoric part of S, written by every update, never read, zero initially).
+   * F22 is read like the other components: a plane-strain caller passes 1.0, the law does not assume it.
+   * dxm_stats: n_nan counts the points with J = F22 (F00 F11 - F01 F10) <= 0 or a non-finite input, whose outputs are NaN as for
+   * DXM_LAW_OGDEN; n_plastic, n_not_converged and max_local_iters are 0 (closed form: C = F^T F is a 2 x 2 block and F22^2, one
+   * rotation diagonalises it).
+   * Only DXM_TANGENT_FULL; the host-buffer forms download the 25 entries as they are and the rows forms move them.  Refused, with a
+   * sentence of the law's own and the handle left as it was: packed tangent layouts, per-point parameter fields, material frames,
+   * the fused displacement gradient and the displacement forms on every mesh (the mesh gradient kernels produce the 9-wide F: pass
+   * [1 + H00, 1 + H11, 1, H01, H10] as an array).  Not served by a custom-hardening build.
+   * algorithmic_bytes_per_point = 312: F 40 in, PK1 40 + tangent 200 + state 32 out (DXM_LAW_OGDEN on the embedded F: 840).
+   * params = [alpha, mu, K] as DXM_LAW_OGDEN, with its checks */
+  DXM_LAW_OGDEN_PE = 38,   /* id 37 is not assigned */
+  DXM_LAW_COUNT = 39
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */
