@@ -45,6 +45,7 @@
 #include "plane_gradient.hpp"
 #include "heat_plane.hpp"
 #include "ogden_plane.hpp"
+#include "hosford_plane.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -482,6 +483,7 @@ template <int LAW> static void launch_plane_strain(const LaunchArgs& a);
 template <int HARD> static void launch_plane_stress_j2(const LaunchArgs& a);
 static void launch_ps_hosford(const LaunchArgs& a);
 static void launch_ogden_pe(const LaunchArgs& a);
+static void launch_pe_hosford(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -1165,7 +1167,39 @@ constexpr LawDesc law_ogden_pe() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34 and 37 are not assigned and stay empty rows (law_known)
+// Hosford under the plane-strain hypothesis (hosford_plane.hip): law 10 in the four components [xx, yy, zz, sqrt(2) xy].  Strain in
+// (32 B), p and the hidden 4-wide plastic strain read (40); stress (32), the 4x4 tangent (128) and the nine state slots (72) out: 304
+// B/point.  Parameters, their checks and the kernel's record are those of law 10 (build_hosford).  On a two-dimensional mesh the
+// displacement forms run the plane gradient kernel (plane_kind) and then the update kernel, as laws 26-28 do
+constexpr LawDesc law_pe_hosford() {
+  // what the plane-strain rows share: the widths, L_FULL only, plane_kind = GRAD_PLANE_STRAIN4, kNoFrame; the sentences are this law's own
+  LawDesc d = plane_strain_law(DXM_LAW_PE_HOSFORD_LINEAR, 5, 304, "hosford_plane_kernel");
+  static_assert(HFP_DIM == PE_DIM, "the 4-wide strain of the plane-strain rows");
+  d.n_isv_fields = 2;
+  d.n_fields = 3;   // field 2 is hidden state: what the update is driven by (hosford_plane.hpp)
+  state_field(d, 0, "ElasticStrain", HFP_DIM, HFP_SLOT_EEL);
+  state_field(d, 1, "EquivalentPlasticStrain", 1, HFP_SLOT_P);
+  state_field(d, 2, "PlasticStrain", HFP_DIM, HFP_SLOT_EP);
+  d.n_slots = HFP_NSLOTS;
+  d.no_fields = "per-point parameter fields are not served for plane-strain Hosford plasticity: the kernel takes its exponent's "
+                "constants per handle";
+  d.build = build_hosford;
+  d.stock_only = "plane-strain Hosford plasticity takes linear hardening only: it is served by the stock libdxmat, not by a "
+                 "custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(hosford_plane_kernel_fn);
+  d.blocks_per_cu = HFP_BLOCKS_PER_CU;   // hosford_plane.hpp
+  d.set_refusal = d.launch_refusal = "the plane-strain Hosford tangent is a general symmetric 4x4 block of 16 entries, not a symmetric 6x6 "
+                                     "and not of the form c1 1x1 + c2 I + c3 n x n: only DXM_TANGENT_FULL is available, no packed record "
+                                     "(sym / coef / pack4) exists for this law";
+  d.no_fused = d.no_displacement = "plane-strain Hosford plasticity takes a 4-wide strain [xx, yy, zz, sqrt(2) xy]: the mesh gradient "
+                                   "kernels evaluate 6-wide strains or F, so the displacement forms (dxm_integrate_displacement*) and the "
+                                   "fused displacement gradient are not served on a mesh that is not "
+                                   "two-dimensional; pass the strain as an array";
+  d.launch = DXM_STOCK_ONLY(launch_pe_hosford);   // hosford_plane.hip: strain from the (N, 4) array, the full 4x4 tangent
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34, 37 and 39 are not assigned and stay empty rows (law_known)
 static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
@@ -1174,6 +1208,7 @@ static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     law_ps_j2_linear(), law_ps_j2_voce(), {}, law_ps_hosford(),
     {}, law_heat_stationary_2d(), law_heat_phase_change_2d(),
     {}, law_ogden_pe(),
+    {}, law_pe_hosford(),
 };
 
 constexpr bool rows_in_place() {
@@ -1184,8 +1219,8 @@ constexpr bool rows_in_place() {
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
                   !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel && !kLaws[29].kernel &&
-                  !kLaws[32].kernel && !kLaws[34].kernel && !kLaws[37].kernel,
-              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34 and 37 are not assigned");
+                  !kLaws[32].kernel && !kLaws[34].kernel && !kLaws[37].kernel && !kLaws[39].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34, 37 and 39 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -2093,6 +2128,12 @@ static void launch_ogden(const LaunchArgs& a) {
 static void launch_ogden_pe(const LaunchArgs& a) {
   dxm_material* m = a.m;
   ogden_plane_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[1] + a.off, m->ld, a.flux, a.ct, m->d_stats + a.stats_off);
+}
+
+static void launch_pe_hosford(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  hosford_plane_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
+                       m->d_stats + a.stats_off);
 }
 
 static void launch_hosford(const LaunchArgs& a) {

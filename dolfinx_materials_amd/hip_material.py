@@ -119,6 +119,10 @@ class HIPMaterial:
         if tangent_layout in ("coef", "pack4") and getattr(behavior, "law", None) == _lib.LAW_HOSFORD_LINEAR:
             raise ValueError("the Hosford tangent is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no "
                              f"coefficients (tangent_layout={tangent_layout!r}); use 'full' or 'sym'")
+        if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_PE_HOSFORD_LINEAR:
+            raise ValueError("the plane-strain Hosford tangent is a general symmetric 4x4 block of 16 entries, not a symmetric 6x6 and not of "
+                             f"the form c1 1x1 + c2 I + c3 n x n: no packed tangent record (tangent_layout={tangent_layout!r}) exists for "
+                             "this law; use 'full'")
         if tangent_layout in ("coef", "pack4") and getattr(behavior, "law", None) == _lib.LAW_ORTHOTROPIC_ELASTIC:
             raise ValueError("the orthotropic tangent Q^T C Q is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there "
                              f"are no coefficients (tangent_layout={tangent_layout!r}); use 'full' or 'sym'")
@@ -333,8 +337,9 @@ class HIPMaterial:
     @property
     def _has_hidden_plastic_strain(self):
         """Hosford: the kernel is handed the total strain, so its state is the plastic strain (hidden field 2), rebuilt from
-        (Strain_n, ElasticStrain_n) when either is set.  Logarithmic-strain plasticity: the same with the Hencky strain of F_n."""
-        return self.behavior.law in (_lib.LAW_HOSFORD_LINEAR, _lib.LAW_LOG_STRAIN_J2)
+        (Strain_n, ElasticStrain_n) when either is set (four components under the plane-strain hypothesis).  Logarithmic-strain
+        plasticity: the same with the Hencky strain of F_n."""
+        return self.behavior.law in (_lib.LAW_HOSFORD_LINEAR, _lib.LAW_PE_HOSFORD_LINEAR, _lib.LAW_LOG_STRAIN_J2)
 
     @property
     def _has_plane_stress_state(self):
@@ -742,14 +747,15 @@ class HIPMaterial:
             self._set_state(2, _as_c(cpi))
         if self._has_hidden_plastic_strain and ("ElasticStrain" in state or self._gname in state):
             # eps_p,n = eps_n - eps_el,n: what the next update forms its trial elastic strain from
-            eel = _as_c(state["ElasticStrain"], (self._n, 6)) if "ElasticStrain" in state else self._isv_dict(S0)["ElasticStrain"]
+            w = 4 if self.behavior.law == _lib.LAW_PE_HOSFORD_LINEAR else 6
+            eel = _as_c(state["ElasticStrain"], (self._n, w)) if "ElasticStrain" in state else self._isv_dict(S0)["ElasticStrain"]
             self._retire_final_views(materializing=True)
             if self.behavior.law == _lib.LAW_LOG_STRAIN_J2:
                 from .conventions import hencky_strain
 
                 total = hencky_strain(np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 9))
             else:
-                total = np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 6)
+                total = np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, w)
             self._set_state(2, _as_c(total - eel))
 
         if self._has_plane_stress_state and (self._fname in state or self._gname in state):

@@ -359,14 +359,24 @@ class HosfordIsotropicHardening(SmallStrainBehavior):
     ``JAXMaterial(HosfordIsotropicHardening(...))`` stands where the demo uses ``MFrontMaterial(lib, "IsotropicPlasticHosfordFlowLinear",
     material_properties=...)``: gradient ``Strain``, flux ``Stress``; :meth:`from_mfront_properties` takes that dictionary.  Tangent
     layouts ``"full"`` and ``"sym"`` (a general symmetric 6x6: no ``"coef"`` / ``"pack4"``); uniform properties only; the displacement
-    forms need option ``fused_gradient`` off."""
+    forms need option ``fused_gradient`` off.
+
+    ``hypothesis="plane_strain"`` (the demo's plane mesh; ``MFrontMaterial(..., hypothesis="plane_strain")``): strain, stress and
+    ``ElasticStrain`` are the 4-vectors ``[xx, yy, zz, sqrt(2) xy]``, the tangent block is a general symmetric ``(4, 4)``: the 6-wide law
+    on the embedded strain, restricted (``conventions.embed_plane_strain`` / ``restrict_plane_strain`` /
+    ``restrict_plane_strain_tangent``).  ``eps_zz`` is read, not assumed to be 0.  Full tangent only; on a ``PlaneMesh`` the
+    displacement forms evaluate the 4-wide strain themselves."""
 
     law = _lib.LAW_HOSFORD_LINEAR
     gradient_name = "Strain"
     flux_name = "Stress"
     MFRONT_NAMES = ("young_modulus", "poisson_ratio", "R0", "hardening_slope")
 
-    def __init__(self, elasticity: LinearElasticIsotropic, yield_stress, a: float = 10.0):
+    def __init__(self, elasticity: LinearElasticIsotropic, yield_stress, a: float = 10.0, hypothesis: str = "3d"):
+        if _check_hypothesis(hypothesis) == "plane_strain":
+            self.hypothesis = hypothesis
+            self.law = _lib.LAW_PE_HOSFORD_LINEAR
+            self.ngrad = self.nflux = 4
         if not isinstance(yield_stress, LinearHardening):
             raise TypeError("Hosford plasticity is served with linear hardening only: yield_stress must be a materials.LinearHardening(R0, H), "
                             f"got {type(yield_stress).__name__}")
@@ -378,15 +388,16 @@ class HosfordIsotropicHardening(SmallStrainBehavior):
             raise ValueError(f"Hosford: R0 must be > 0, H >= 0 and the exponent a >= 2 (all finite); got R0={R0}, H={H}, a={a}")
 
     @classmethod
-    def from_mfront_properties(cls, props: dict):
+    def from_mfront_properties(cls, props: dict, hypothesis: str = "3d"):
         """The ``material_properties`` of the multi-material demo: ``young_modulus``, ``poisson_ratio``, ``R0``, ``hardening_slope``,
-        and optionally the exponent ``a`` (10, the behaviour file's value, when absent)."""
+        and optionally the exponent ``a`` (10, the behaviour file's value, when absent).  ``hypothesis``: that of the same call."""
         need, known = set(cls.MFRONT_NAMES), set(cls.MFRONT_NAMES) | {"a"}
         missing, extra = need - set(props), set(props) - known
         if missing or extra:
             raise ValueError(f"Hosford material properties: missing {sorted(missing)}, unknown {sorted(extra)}")
         el = LinearElasticIsotropic(E=float(props["young_modulus"]), nu=float(props["poisson_ratio"]))
-        return cls(el, LinearHardening(float(props["R0"]), float(props["hardening_slope"])), a=float(props.get("a", 10.0)))
+        return cls(el, LinearHardening(float(props["R0"]), float(props["hardening_slope"])), a=float(props.get("a", 10.0)),
+                   hypothesis=hypothesis)
 
     def params(self):
         return [self.elasticity.E, self.elasticity.nu, self.yield_stress.sig0, self.yield_stress.H, self.a]

@@ -336,7 +336,31 @@ enum {
    * algorithmic_bytes_per_point = 312: F 40 in, PK1 40 + tangent 200 + state 32 out (DXM_LAW_OGDEN on the embedded F: 840).
    * params = [alpha, mu, K] as DXM_LAW_OGDEN, with its checks */
   DXM_LAW_OGDEN_PE = 38,   /* id 37 is not assigned */
-  DXM_LAW_COUNT = 39
+  /* (before id 40 the table ended here, with
+   * DXM_LAW_COUNT = 39
+   * and DXM_ABI_VERSION 6, which stays)
+   * DXM_LAW_HOSFORD_LINEAR under the plane-strain hypothesis: the matrix of the reference's multi-material demo on its plane mesh.
+   * Gradient Strain (4) and flux Stress (4), both [xx, yy, zz, sqrt(2) xy]; one tangent block, 4 x 4, row-major, 16 doubles per
+   * point: a general symmetric matrix, not of the form c1 1x1 + c2 I + c3 n x n.  BY DEFINITION the law is DXM_LAW_HOSFORD_LINEAR
+   * evaluated on the strain [xx, yy, zz, sqrt(2) xy, 0, 0], of which are kept: components 0..3 of the stress, the elastic and the
+   * plastic strain (the out-of-plane shears are exactly zero for such a strain) and rows and columns 0..3 of the 6 x 6 tangent (its
+   * coupling to the out-of-plane shears vanishes).  eps_zz is read like the other components (a plane-strain caller passes 0) and
+   * sig_zz is returned, as DXM_LAW_PE_* do.
+   * Internal state variables ElasticStrain (4; written by every update, read by none) and EquivalentPlasticStrain (1); the update
+   * is driven by the hidden state field 2, the plastic strain (4), addressed by dxm_set_state / dxm_get_state exactly as for
+   * DXM_LAW_HOSFORD_LINEAR: 9 SoA slots.
+   * dxm_stats and dxm_set_newton: as DXM_LAW_HOSFORD_LINEAR (residuals as stresses, <= max(tol, rtol seq_trial); n_plastic,
+   * n_not_converged, n_nan, max_local_iters), with its Newton domain.
+   * Only DXM_TANGENT_FULL; the host-buffer forms download the 16 entries as they are and the rows forms move them.  On a
+   * two-dimensional mesh (dxm_mesh_create_plane) the displacement forms evaluate the 4-wide strain and then run the update kernel.
+   * Refused, with a sentence of the law's own and the handle left as it was: packed tangent layouts, per-point parameter fields,
+   * material frames, external state variables, the fused displacement gradient and the displacement forms on a mesh that is not
+   * two-dimensional.  Not served by a custom-hardening build.
+   * algorithmic_bytes_per_point = 304: strain 32 + state 40 in, stress 32 + tangent 128 + state 72 out (DXM_LAW_HOSFORD_LINEAR on
+   * the embedded strain: 544).
+   * params = [E, nu, R0, H, a] as DXM_LAW_HOSFORD_LINEAR, with its checks */
+  DXM_LAW_PE_HOSFORD_LINEAR = 40,   /* id 39 is not assigned */
+  DXM_LAW_COUNT = 41
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2 ps_hosford heat_plane ogden_plane]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2 ps_hosford heat_plane ogden_plane pe_hosford]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -798,6 +798,89 @@ def bench_ogden_plane(a):
     m9.close()
 
 
+def bench_pe_hosford(a):
+    """--laws pe_hosford: law 40 (Hosford on the 4-wide plane-strain strain) next to law 10 OF THIS PROCESS on the same strains,
+    embedded, at the multi-material demo's parameters (E 70e3, nu 0.3, R0 200, H 10, a 10), from the natural state.  Three batch kinds:
+    elastic (seq_trial / R0 in 0.1 ... 0.9), mixed (every point elastic or yielded with probability 1/2) and fully yielded (1.05 ... 3).
+    One JSON line: per kind the kernel ms of both (median of three medians, interleaved), the fraction of 8 TB/s at the counted bytes
+    (304 against 544), the ratio of the 4-wide time to the 6-wide time beside the byte ratio, the plastic counts of both and the
+    largest difference of stress and tangent to law 10 restricted; the resources the build reports are in DESIGN.md.
+    --blocks-per-cu: law 40 at each of these grid sizes as well, on the mixed batch."""
+    import torch
+
+    import dolfinx_materials_amd.materials as jm
+    from dolfinx_materials_amd.conventions import embed_plane_strain
+    from dolfinx_materials_amd.jaxmat import JAXMaterial
+    from helpers import to_device
+    import hosford_plane_ref as hp
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+    E, nu, R0, H, ex = 70e3, 0.3, 200.0, 10.0, 10.0
+
+    def timed(m, g, flux, ct):
+        for _ in range(a.warmup):
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+        for e0, e1 in ev:
+            e0.record()
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+            e1.record()
+        torch.cuda.synchronize()
+        return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+    def behaviour(hypothesis):
+        return jm.HosfordIsotropicHardening(jm.LinearElasticIsotropic(E=E, nu=nu), jm.LinearHardening(R0, H), a=ex, hypothesis=hypothesis)
+
+    m4, m6 = JAXMaterial(behaviour("plane_strain")), JAXMaterial(behaviour("3d"))
+    m4.set_data_manager(n)
+    m6.set_data_manager(n)
+    f4, c4 = torch.empty((n, 4), dtype=torch.float64, device="cuda:0"), torch.empty((n, 16), dtype=torch.float64, device="cuda:0")
+    f6, c6 = torch.empty((n, 6), dtype=torch.float64, device="cuda:0"), torch.empty((n, 36), dtype=torch.float64, device="cuda:0")
+    el = hp.make_inputs("elastic", n, ex, 2041, E=E, nu=nu, R0=R0, H=H, trivial_state=True)[0]
+    yl = hp.make_inputs("generic", n, ex, 2042, E=E, nu=nu, R0=R0, H=H, trivial_state=True)[0]
+    pick = np.random.default_rng(2043).random(n) < 0.5
+    b4, b6 = m4.algorithmic_bytes_per_point, m6.algorithmic_bytes_per_point
+    r = {"law": "pe_hosford", "points": n, "kernel": m4.kernel_name, "six_wide_kernel": m6.kernel_name, "params": [E, nu, R0, H, ex],
+         "algorithmic_bytes_per_point": b4, "six_wide_bytes_per_point": b6, "byte_ratio": round(b4 / b6, 3), "batches": {},
+         "warmup": a.warmup, "reps": a.reps}
+    g4_mixed = None
+    for kind, eps in (("elastic", el), ("mixed", np.where(pick[:, None], yl, el)), ("yielded", yl)):
+        g4, g6 = to_device(eps), to_device(embed_plane_strain(eps))
+        t4, t6 = [], []
+        for _ in range(3):          # interleaved: both kernels see the same drift of the machine
+            t6.append(timed(m6, g6, f6, c6))
+            t4.append(timed(m4, g4, f4, c4))
+        _, s4 = m4.stats()
+        _, s6 = m6.stats()
+        # the restriction, on the device: what law 40 writes against components / rows / columns 0..3 of law 10's outputs
+        dS = float((f4 - f6[:, :4]).abs().max() / f6.abs().max())
+        dC = float((c4.view(n, 4, 4) - c6.view(n, 6, 6)[:, :4, :4]).abs().max() / c6.abs().max())
+        ms4, ms6 = float(np.median(t4)), float(np.median(t6))
+        r["batches"][kind] = {"kernel_ms_repeats": [round(x, 4) for x in t4], "kernel_ms": round(ms4, 4), "frac_of_8TBs": round(b4 * n / ms4 / 1e6 / 8000, 4),
+                              "six_wide_ms_repeats": [round(x, 4) for x in t6], "six_wide_ms": round(ms6, 4),
+                              "six_wide_frac_of_8TBs": round(b6 * n / ms6 / 1e6 / 8000, 4), "ratio_to_six_wide": round(ms4 / ms6, 3),
+                              "ratio_to_byte_scaled_six_wide": round(ms4 / (ms6 * b4 / b6), 3),
+                              "n_plastic": s4["n_plastic"], "six_wide_n_plastic": s6["n_plastic"],
+                              "n_not_converged": s4["n_not_converged"], "six_wide_n_not_converged": s6["n_not_converged"],
+                              "n_nan": s4["n_nan"], "max_local_iters": s4["max_local_iters"],
+                              "max_abs_difference_to_six_wide_restricted": {"stress_over_max_stress": dS, "tangent_over_max_tangent": dC}}
+        if kind == "mixed":
+            g4_mixed = g4
+        del g6
+    if a.blocks_per_cu:
+        sweep = {}
+        for b in a.blocks_per_cu:
+            m4.set_option("blocks_per_cu", b)
+            sweep[b] = round(timed(m4, g4_mixed, f4, c4), 4)
+        m4.set_option("blocks_per_cu", 64)      # the shipped grid again (hosford_plane.hpp)
+        r["mixed_kernel_ms_by_blocks_per_cu"] = sweep
+    print(json.dumps(r), flush=True)
+    m4.close()
+    m6.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -807,13 +890,13 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0, help="also time the plain-C oracle on this many points")
     ap.add_argument("--sym", action="store_true", help="symmetric-packed tangent (small-strain laws)")
     ap.add_argument("--blocks-per-cu", type=int, nargs="+", default=None,
-                    help="ramberg_osgood, plane_strain, ps_j2, ps_hosford, heat_plane, ogden_plane: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
+                    help="ramberg_osgood, plane_strain, ps_j2, ps_hosford, heat_plane, ogden_plane, pe_hosford: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
                          "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "heat_plane" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws or
-                         any(law.startswith("ps_") for law in a.laws) or "plane_strain" in a.laws or "ogden_plane" in a.laws):   # (ps_j2 among them)
+                         any(law.startswith("ps_") for law in a.laws) or "plane_strain" in a.laws or "ogden_plane" in a.laws or "pe_hosford" in a.laws):   # (ps_j2 among them)
         ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal, heat-transfer or logarithmic-strain law")
     import torch
 
@@ -856,6 +939,9 @@ def main():
             continue
         if law == "ogden_plane":   # law 38 beside law 7 of this process on the embedded gradient: one line
             bench_ogden_plane(a)
+            continue
+        if law == "pe_hosford":   # law 40 beside law 10 of this process on the embedded strain, three batch kinds: one line
+            bench_pe_hosford(a)
             continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)
