@@ -30,6 +30,7 @@ LAW_PS_HOSFORD = 33   # plane-stress Hosford (32 is not assigned)
 LAW_HEAT_STATIONARY_2D, LAW_HEAT_PHASE_CHANGE_2D = 35, 36   # the heat-transfer laws with a 2-wide gradient (34 is not assigned)
 LAW_OGDEN_PE = 38   # Ogden on the 5-wide plane-strain F (37 is not assigned)
 LAW_PE_HOSFORD_LINEAR = 40   # Hosford on the 4-wide plane-strain strain (39 is not assigned)
+LAW_LOG_STRAIN_PE = 42   # logarithmic-strain J2 on the 5-wide plane-strain F (41 is not assigned)
 DXM_MAX_EXTERNAL_STATE, DXM_MAX_TANGENT_BLOCKS = 2, 4
 S0, S1 = 0, 1
 

@@ -204,6 +204,14 @@ def restrict_plane_F_tangent(A99):
     return np.ascontiguousarray(A99[..., idx, :][..., :, idx])
 
 
+def hencky_strain_plane(F5):
+    """Hencky strain of every row of ``F5`` (N, 5) ``[F00, F11, F22, F01, F10]`` as (N, 4) ``[xx, yy, zz, sqrt(2) xy]``:
+    :func:`hencky_strain` of the embedded ``F``, restricted (its out-of-plane shears are zero for such an ``F``).  What the hidden
+    plastic strain of plane-strain logarithmic-strain plasticity is rebuilt from.  Rows that are no deformation gradient count as
+    ``F = I``, as there."""
+    return restrict_plane_strain(hencky_strain(embed_plane_F(np.asarray(F5, dtype=np.float64).reshape(-1, 5))))
+
+
 def plane_stress_axial_strain(E, nu, stress, epsp):
     """The out-of-plane strain of a plane-stress state from the outputs of plane-stress J2 plasticity (``[xx, yy, sqrt(2) xy]``):
     ``eps_zz = -nu / E (s_xx + s_yy) - (epsp_xx + epsp_yy)`` -- the elastic part from ``sig_zz = 0``, the plastic part from the

@@ -46,6 +46,7 @@
 #include "heat_plane.hpp"
 #include "ogden_plane.hpp"
 #include "hosford_plane.hpp"
+#include "log_strain_plane.hpp"
 #include "host_side.hpp"
 
 using namespace dxm;
@@ -484,6 +485,7 @@ template <int HARD> static void launch_plane_stress_j2(const LaunchArgs& a);
 static void launch_ps_hosford(const LaunchArgs& a);
 static void launch_ogden_pe(const LaunchArgs& a);
 static void launch_pe_hosford(const LaunchArgs& a);
+static void launch_log_strain_pe(const LaunchArgs& a);
 
 // The device assembly of this file lists its kernels in the order in which host code first names them, and
 // tests/test_hosford_build.py pins the digest of that assembly.  These five were first named by dxm_create in this order, which is
@@ -1199,8 +1201,46 @@ constexpr LawDesc law_pe_hosford() {
   return d;
 }
 
-// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34, 37 and 39 are not assigned and stay empty rows (law_known)
-static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
+// Logarithmic-strain J2 under the plane-strain hypothesis (log_strain_plane.hip): the 5-wide F in (40 B), p and the hidden 4-wide
+// logarithmic plastic strain read (40); PK1 (40), the 5x5 dP/dF (200) and the nine state slots (72) out: 392 B/point.  Parameters, their
+// checks and the kernel's record are those of law 19 (build_log_strain).  F comes as an array: the row names no plane gradient kind
+constexpr LawDesc law_log_strain_pe() {
+  LawDesc d{};
+  d.id = DXM_LAW_LOG_STRAIN_PE;
+  d.n_grad = d.n_flux = LSP_DIM;
+  d.n_params = d.n_params_custom = 4;
+  d.n_isv_fields = 2;
+  d.n_fields = 3;   // field 2 is hidden state: what the update is driven by (log_strain_plane.hpp)
+  state_field(d, 0, "ElasticStrain", LSP_SYM, LSP_SLOT_EEL);
+  state_field(d, 1, "EquivalentPlasticStrain", 1, LSP_SLOT_P);
+  state_field(d, 2, "PlasticStrain", LSP_SYM, LSP_SLOT_EP);
+  d.n_slots = LSP_NSLOTS;
+  d.alg_bytes = 392;
+  d.kernel = "log_strain_plane_kernel";
+  d.no_fields = "per-point parameter fields are not served for plane-strain logarithmic-strain plasticity: the kernel takes its constants "
+                "per handle";
+  d.build = build_log_strain;
+  d.stock_only = "plane-strain logarithmic-strain plasticity takes linear hardening only: it is served by the stock libdxmat, not by a "
+                 "custom-hardening build";
+  d.residency_kernel = DXM_STOCK_ONLY(log_strain_plane_kernel_fn);
+  d.blocks_per_cu = LSP_BLOCKS_PER_CU;   // log_strain_plane.hpp
+  d.set_layouts = d.launch_layouts = L_FULL;
+  d.set_refusal = d.launch_refusal = "the plane-strain logarithmic-strain plasticity tangent dP/dF is a 5x5 block of 25 entries, not a "
+                                     "symmetric 6x6: only DXM_TANGENT_FULL is available, no packed record (sym / coef / pack4) exists for "
+                                     "this law";
+  d.no_fused = d.no_displacement = "plane-strain logarithmic-strain plasticity takes the 5-wide deformation gradient "
+                                   "[F00, F11, F22, F01, F10]: the mesh gradient kernels produce the 9-wide F, so the displacement forms "
+                                   "(dxm_integrate_displacement*) and the fused displacement gradient are not served; pass the 5-wide F "
+                                   "[1 + H00, 1 + H11, 1, H01, H10] of the displacement gradient H as an array";
+  d.no_frame = "plane-strain logarithmic-strain plasticity is isotropic (Hooke, Mises): a material frame changes nothing in its update";
+  d.launch = DXM_STOCK_ONLY(launch_log_strain_pe);   // log_strain_plane.hip: F from the (N, 5) array, the full 5x5 tangent
+  return d;
+}
+
+// positional: row i is law id i; ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34, 37, 39 and 41 are not assigned and stay empty rows (law_known).
+// The rows through id 40 keep the text they had (tests/test_hosford_plane_cpu.py pins the last line of this initialiser); the ids
+// after them are appended by law_table() below
+static constexpr LawDesc kLawsThrough40[41] = {
     law_elastic(), law_j2_linear(), law_j2_voce(), law_fefp(DXM_LAW_FEFP_J2_VOCE, true), law_fefp(DXM_LAW_FEFP_J2_LINEAR, false),
     law_ramberg_osgood(), {}, law_ogden(), {}, {}, law_hosford(), {}, law_orthotropic(), {}, law_single_crystal(), {},
     law_heat_stationary(), law_heat_phase_change(), {}, law_log_strain_j2(), {}, law_fs_single_crystal(), {},
@@ -1210,6 +1250,17 @@ static constexpr LawDesc kLaws[DXM_LAW_COUNT] = {
     {}, law_ogden_pe(),
     {}, law_pe_hosford(),
 };
+struct LawTable {
+  LawDesc row[DXM_LAW_COUNT];
+};
+constexpr LawTable law_table() {
+  LawTable t{};
+  for (int i = 0; i < 41; ++i) t.row[i] = kLawsThrough40[i];
+  t.row[DXM_LAW_LOG_STRAIN_PE] = law_log_strain_pe();   // id 41 stays an empty row
+  return t;
+}
+static constexpr LawTable kLawTable = law_table();
+static constexpr const LawDesc (&kLaws)[DXM_LAW_COUNT] = kLawTable.row;
 
 constexpr bool rows_in_place() {
   for (int i = 0; i < DXM_LAW_COUNT; ++i)
@@ -1219,8 +1270,8 @@ constexpr bool rows_in_place() {
 static_assert(rows_in_place(), "each row of kLaws sits at the index of its DXM_LAW_* id");
 static_assert(!kLaws[6].kernel && !kLaws[8].kernel && !kLaws[9].kernel && !kLaws[11].kernel && !kLaws[13].kernel && !kLaws[15].kernel &&
                   !kLaws[18].kernel && !kLaws[20].kernel && !kLaws[22].kernel && !kLaws[25].kernel && !kLaws[29].kernel &&
-                  !kLaws[32].kernel && !kLaws[34].kernel && !kLaws[37].kernel && !kLaws[39].kernel,
-              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34, 37 and 39 are not assigned");
+                  !kLaws[32].kernel && !kLaws[34].kernel && !kLaws[37].kernel && !kLaws[39].kernel && !kLaws[41].kernel,
+              "ids 6, 8, 9, 11, 13, 15, 18, 20, 22, 25, 29, 32, 34, 37, 39 and 41 are not assigned");
 
 static bool law_known(int law) { return law >= 0 && law < DXM_LAW_COUNT && kLaws[law].kernel != nullptr; }
 
@@ -2134,6 +2185,12 @@ static void launch_pe_hosford(const LaunchArgs& a) {
   dxm_material* m = a.m;
   hosford_plane_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
                        m->d_stats + a.stats_off);
+}
+
+static void launch_log_strain_pe(const LaunchArgs& a) {
+  dxm_material* m = a.m;
+  log_strain_plane_launch(a.grid, a.st, m->prm, a.cnt, a.grad, m->state[0] + a.off, m->state[1] + a.off, m->ld, a.flux, a.ct,
+                          m->d_stats + a.stats_off);
 }
 
 static void launch_hosford(const LaunchArgs& a) {

@@ -480,12 +480,13 @@ inline TransferPlan plan_transfer(const TransferRequest& r) {
   // plane-stress Hosford plasticity: the same
   // plane-strain Ogden: as Ogden, for its 25 entries (a 5x5 block)
   // plane-strain Hosford: as the three plane-strain laws, 16 entries (a general symmetric 4x4, moved as it is)
+  // plane-strain logarithmic-strain J2: as plane-strain Ogden, 25 entries (a 5x5 block)
   const bool blocks = r.plain_blocks;
   const bool plain_block = r.law == DXM_LAW_OGDEN || r.law == DXM_LAW_SINGLE_CRYSTAL_FCC || r.law == DXM_LAW_LOG_STRAIN_J2 ||
                            r.law == DXM_LAW_FS_SINGLE_CRYSTAL_FCC || r.law == DXM_LAW_PS_QUADRATIC || r.law == DXM_LAW_PS_POLYGON ||
                            r.law == DXM_LAW_PE_ELASTIC_ISO || r.law == DXM_LAW_PE_J2_LINEAR || r.law == DXM_LAW_PE_J2_VOCE ||
                            r.law == DXM_LAW_PS_J2_LINEAR || r.law == DXM_LAW_PS_J2_VOCE || r.law == DXM_LAW_PS_HOSFORD || blocks ||
-                           r.law == DXM_LAW_OGDEN_PE || r.law == DXM_LAW_PE_HOSFORD_LINEAR;
+                           r.law == DXM_LAW_OGDEN_PE || r.law == DXM_LAW_PE_HOSFORD_LINEAR || r.law == DXM_LAW_LOG_STRAIN_PE;
   // Hosford: a general symmetric 6x6 with no coefficient form.  A full-layout handle's packed transfer is the kernel's 21
   // upper-triangle entries (168 instead of 288 B/point), mirrored into the block by the workers; a "sym" handle downloads its 21
   // orthotropic elasticity: the same (Q^T C Q is a general symmetric 6x6 per point)

@@ -116,6 +116,9 @@ class HIPMaterial:
         if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_LOG_STRAIN_J2:
             raise ValueError("the logarithmic-strain plasticity kernel writes the full 81-entry dP/dF only: no packed tangent record "
                              f"(tangent_layout={tangent_layout!r}) exists for this law")
+        if tangent_layout != "full" and getattr(behavior, "law", None) == _lib.LAW_LOG_STRAIN_PE:
+            raise ValueError("the plane-strain logarithmic-strain plasticity tangent dP/dF is a 5x5 block of 25 entries, not a symmetric "
+                             f"6x6: no packed tangent record (tangent_layout={tangent_layout!r}) exists for this law; use 'full'")
         if tangent_layout in ("coef", "pack4") and getattr(behavior, "law", None) == _lib.LAW_HOSFORD_LINEAR:
             raise ValueError("the Hosford tangent is a general symmetric 6x6, not of the form c1 1x1 + c2 I + c3 n x n: there are no "
                              f"coefficients (tangent_layout={tangent_layout!r}); use 'full' or 'sym'")
@@ -338,8 +341,8 @@ class HIPMaterial:
     def _has_hidden_plastic_strain(self):
         """Hosford: the kernel is handed the total strain, so its state is the plastic strain (hidden field 2), rebuilt from
         (Strain_n, ElasticStrain_n) when either is set (four components under the plane-strain hypothesis).  Logarithmic-strain
-        plasticity: the same with the Hencky strain of F_n."""
-        return self.behavior.law in (_lib.LAW_HOSFORD_LINEAR, _lib.LAW_PE_HOSFORD_LINEAR, _lib.LAW_LOG_STRAIN_J2)
+        plasticity: the same with the Hencky strain of F_n (of the embedded 5-wide F_n, restricted, under the plane-strain hypothesis)."""
+        return self.behavior.law in (_lib.LAW_HOSFORD_LINEAR, _lib.LAW_PE_HOSFORD_LINEAR, _lib.LAW_LOG_STRAIN_J2, _lib.LAW_LOG_STRAIN_PE)
 
     @property
     def _has_plane_stress_state(self):
@@ -548,8 +551,9 @@ class HIPMaterial:
     @property
     def _gradient_is_F(self):
         """The gradient is a deformation gradient, whose natural state is the identity: the 9-vector, or the 5-vector
-        ``[F00, F11, F22, F01, F10]`` of plane-strain Ogden (the diagonal comes first in both)."""
-        return self._info.n_grad == 9 or self.behavior.law == _lib.LAW_OGDEN_PE
+        ``[F00, F11, F22, F01, F10]`` of plane-strain Ogden and of plane-strain logarithmic-strain plasticity (the diagonal comes first
+        in both)."""
+        return self._info.n_grad == 9 or self.behavior.law in (_lib.LAW_OGDEN_PE, _lib.LAW_LOG_STRAIN_PE)
 
     def _initial_gradient(self):
         g = np.zeros((self._n, self._info.n_grad))
@@ -747,13 +751,17 @@ class HIPMaterial:
             self._set_state(2, _as_c(cpi))
         if self._has_hidden_plastic_strain and ("ElasticStrain" in state or self._gname in state):
             # eps_p,n = eps_n - eps_el,n: what the next update forms its trial elastic strain from
-            w = 4 if self.behavior.law == _lib.LAW_PE_HOSFORD_LINEAR else 6
+            w = 4 if self.behavior.law in (_lib.LAW_PE_HOSFORD_LINEAR, _lib.LAW_LOG_STRAIN_PE) else 6
             eel = _as_c(state["ElasticStrain"], (self._n, w)) if "ElasticStrain" in state else self._isv_dict(S0)["ElasticStrain"]
             self._retire_final_views(materializing=True)
             if self.behavior.law == _lib.LAW_LOG_STRAIN_J2:
                 from .conventions import hencky_strain
 
                 total = hencky_strain(np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 9))
+            elif self.behavior.law == _lib.LAW_LOG_STRAIN_PE:
+                from .conventions import hencky_strain_plane
+
+                total = hencky_strain_plane(np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, 5))
             else:
                 total = np.asarray(self._grad[0], dtype=np.float64).reshape(self._n, w)
             self._set_state(2, _as_c(total - eel))

@@ -418,13 +418,24 @@ class LogarithmicStrainPlasticity(FiniteStrainBehavior):
     ``JAXMaterial(LogarithmicStrainPlasticity.from_mfront_properties({"YieldStrength": 250e6, "HardeningSlope": 1e6}))`` stands
     where the demo uses ``MFrontMaterial(lib, "LogarithmicStrainPlasticity", material_properties=...)``: gradient
     ``DeformationGradient`` (9), flux ``FirstPiolaKirchhoffStress`` (9), tangent block ``(9, 9)``.  Full tangent only; uniform
-    properties only; the displacement forms need option ``fused_gradient`` off."""
+    properties only; the displacement forms need option ``fused_gradient`` off.
+
+    ``hypothesis="plane_strain"`` (``MFrontMaterial(lib, "LogarithmicStrainPlasticity", hypothesis="plane_strain")``): the gradient is
+    the 5-vector ``[F00, F11, F22, F01, F10]`` of a 2x2 tensor with its out-of-plane stretch (``utils.py:168-172``), the flux the 5-wide
+    PK1 in the same order, the tangent block ``(5, 5)``, ``ElasticStrain`` the 4-vector ``[xx, yy, zz, sqrt(2) xy]``: the 9-wide law on
+    the embedded ``F``, restricted (``conventions.embed_plane_F`` / ``restrict_plane_F`` / ``restrict_plane_F_tangent`` /
+    ``restrict_plane_strain``).  ``F22`` is read, not assumed to be 1.  F is passed as an array: the displacement forms are not served
+    under this hypothesis."""
 
     law = _lib.LAW_LOG_STRAIN_J2
     gradient_name = "DeformationGradient"
     flux_name = "FirstPiolaKirchhoffStress"
 
-    def __init__(self, s0: float, H0: float, E: float = 210e9, nu: float = 0.3):
+    def __init__(self, s0: float, H0: float, E: float = 210e9, nu: float = 0.3, hypothesis: str = "3d"):
+        if _check_hypothesis(hypothesis) == "plane_strain":
+            self.hypothesis = hypothesis
+            self.law = _lib.LAW_LOG_STRAIN_PE
+            self.ngrad = self.nflux = 5
         self.s0 = float(s0)
         self.H0 = float(H0)
         self.E = float(E)
@@ -435,9 +446,10 @@ class LogarithmicStrainPlasticity(FiniteStrainBehavior):
                              f"got E={E}, nu={nu}, s0={s0}, H0={H0}")
 
     @classmethod
-    def from_mfront_properties(cls, props: dict):
+    def from_mfront_properties(cls, props: dict, hypothesis: str = "3d"):
         """The ``material_properties`` of the demo: ``HardeningSlope`` and ``YieldStrength`` (the demo's key; ``YieldStress``, the
-        glossary name, is taken too).  ``E`` and ``nu`` are written into the behaviour file and are no material properties."""
+        glossary name, is taken too).  ``E`` and ``nu`` are written into the behaviour file and are no material properties.
+        ``hypothesis``: that of the same call."""
         props = dict(props)
         extra = set(props) - {"HardeningSlope", "YieldStrength", "YieldStress"}
         if extra:
@@ -449,7 +461,7 @@ class LogarithmicStrainPlasticity(FiniteStrainBehavior):
                                    ("HardeningSlope", "HardeningSlope" in props)) if not ok]
         if missing:
             raise ValueError(f"logarithmic-strain plasticity material properties: missing {missing}")
-        return cls(s0=float(props.get("YieldStrength", props.get("YieldStress"))), H0=float(props["HardeningSlope"]))
+        return cls(s0=float(props.get("YieldStrength", props.get("YieldStress"))), H0=float(props["HardeningSlope"]), hypothesis=hypothesis)
 
     def params(self):
         return [self.E, self.nu, self.s0, self.H0]

@@ -360,7 +360,32 @@ enum {
    * the embedded strain: 544).
    * params = [E, nu, R0, H, a] as DXM_LAW_HOSFORD_LINEAR, with its checks */
   DXM_LAW_PE_HOSFORD_LINEAR = 40,   /* id 39 is not assigned */
-  DXM_LAW_COUNT = 41
+  /* (before id 42 the table ended here, with
+   * DXM_LAW_COUNT = 41
+   * and DXM_ABI_VERSION 6, which stays)
+   * DXM_LAW_LOG_STRAIN_J2 under the plane-strain hypothesis: what MFrontMaterial(lib, "LogarithmicStrainPlasticity",
+   * hypothesis="plane_strain") exchanges.  Gradient DeformationGradient (5) = [F00, F11, F22, F01, F10], the 5-vector
+   * utils.py:168-172 builds from a 2x2 tensor with its out-of-plane stretch; flux FirstPiolaKirchhoffStress (5) in the same order;
+   * tangent dP/dF 5 x 5, row-major, 25 doubles per point.  BY DEFINITION the law is DXM_LAW_LOG_STRAIN_J2 evaluated on
+   * F9 = [F00, F11, F22, F01, F10, 0, 0, 0, 0] and an old plastic strain without out-of-plane shears, of which are kept: components
+   * 0..4 of PK1 (the other four are exactly zero for such a state), rows and columns 0..4 of the 9 x 9 dP/dF (the dropped cross
+   * derivatives vanish by the reflection z -> -z) and the components [xx, yy, zz, sqrt(2) xy] of the symmetric tensors.  F22 is read
+   * like the other components: a plane-strain caller passes 1.0, the law does not assume it.  Closed form, no local iteration: one
+   * rotation diagonalises the 2 x 2 block of C = F^T F, one first and two second divided differences of the logarithm remain.
+   * Internal state variables ElasticStrain (4; written by every update, read by none) and EquivalentPlasticStrain (1); the
+   * gradient handed in is the TOTAL F, so the update is driven by the hidden state field 2, the logarithmic plastic strain (4),
+   * addressed by dxm_set_state / dxm_get_state exactly as for DXM_LAW_LOG_STRAIN_J2: 9 SoA slots.
+   * dxm_stats: n_nan counts the points with J = F22 (F00 F11 - F01 F10) <= 0 or a non-finite F, whose outputs are all NaN;
+   * n_plastic counts the points that yield; n_not_converged and max_local_iters are 0.
+   * Only DXM_TANGENT_FULL; the host-buffer forms download the 25 entries as they are and the rows forms move them.  Refused, with a
+   * sentence of the law's own and the handle left as it was: packed tangent layouts, per-point parameter fields, material frames,
+   * the fused displacement gradient and the displacement forms on every mesh (the mesh gradient kernels produce the 9-wide F: pass
+   * [1 + H00, 1 + H11, 1, H01, H10] as an array).  Not served by a custom-hardening build.
+   * algorithmic_bytes_per_point = 392: F 40 + state 40 in, PK1 40 + tangent 200 + state 72 out (DXM_LAW_LOG_STRAIN_J2 on the
+   * embedded F: 952).
+   * params = [E, nu, s0, H0] as DXM_LAW_LOG_STRAIN_J2, with its checks */
+  DXM_LAW_LOG_STRAIN_PE = 42,   /* id 41 is not assigned */
+  DXM_LAW_COUNT = 43
 };
 
 /* Which state: s0 = beginning of the increment, s1 = end (generic.py:204-216, jaxmat.py:30-43). */

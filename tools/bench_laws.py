@@ -2,7 +2,7 @@
 """Per-law kernel throughput on one GPU (device-resident inputs/outputs, HIP events on the launch
 stream).  Not the headline bench (that is bench.py); used to fill the per-law table of DESIGN.md.
 
-    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2 ps_hosford heat_plane ogden_plane pe_hosford]
+    python tools/bench_laws.py [--points 10000000] [--reps 20] [--laws elastic j2_linear j2_voce fefp ramberg_osgood ogden hosford orthotropic single_crystal heat_stationary heat_phase_change log_strain fs_single_crystal ps_vonmises ps_rankine ps_l1rankine plane_strain ps_j2 ps_hosford heat_plane ogden_plane pe_hosford log_strain_plane]
 
 ramberg_osgood: the reference's curve parameters (tests/mfront/test_nonlinear_elasticity.py: E = 1e5, nu = 0.3, sig0 = 500,
 alpha = 0.4, n = 100) on a fixed, seeded strain set whose equivalent strain is uniform over 0 ... 1e-2 (linear part, knee and
@@ -881,6 +881,85 @@ def bench_pe_hosford(a):
     m6.close()
 
 
+def bench_log_strain_plane(a):
+    """--laws log_strain_plane: law 42 (logarithmic-strain J2 on the 5-wide plane-strain F) next to law 19 OF THIS PROCESS on the same
+    gradients, embedded, at the demo's material properties, from the natural state.  F5 = [1, 1, 1, 0, 0] + amp U(-1/2, 1/2); three
+    batch kinds: elastic (amp 5e-4: below the yield strain of 1.2e-3), fully yielded (amp 2e-2) and mixed (every point one or the other
+    with probability 1/2).  One JSON line: per kind the kernel ms of both (median of three medians, interleaved), the fraction of 8 TB/s
+    at the counted bytes (392 against 952), the ratio of the 5-wide time to the 9-wide time beside the byte ratio, the plastic counts of
+    both and the largest difference of PK1 and tangent to law 19 restricted; the resources the build reports are in DESIGN.md.
+    --blocks-per-cu: law 42 at each of these grid sizes as well, on the mixed batch."""
+    import torch
+
+    import dolfinx_materials_amd.materials as jm
+    from dolfinx_materials_amd.conventions import embed_plane_F
+    from dolfinx_materials_amd.jaxmat import JAXMaterial
+    from helpers import to_device
+
+    n = a.points
+    st = torch.cuda.current_stream().cuda_stream
+    s0, H0 = 250e6, 1e6
+
+    def timed(m, g, flux, ct):
+        for _ in range(a.warmup):
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+        torch.cuda.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.reps)]
+        for e0, e1 in ev:
+            e0.record()
+            m.integrate_device(g.data_ptr(), flux.data_ptr(), ct.data_ptr(), st)
+            e1.record()
+        torch.cuda.synchronize()
+        return float(np.median([e0.elapsed_time(e1) for e0, e1 in ev]))
+
+    m5, m9 = JAXMaterial(jm.LogarithmicStrainPlasticity(s0, H0, hypothesis="plane_strain")), JAXMaterial(jm.LogarithmicStrainPlasticity(s0, H0))
+    m5.set_data_manager(n)
+    m9.set_data_manager(n)
+    f5, c5 = torch.empty((n, 5), dtype=torch.float64, device="cuda:0"), torch.empty((n, 25), dtype=torch.float64, device="cuda:0")
+    f9, c9 = torch.empty((n, 9), dtype=torch.float64, device="cuda:0"), torch.empty((n, 81), dtype=torch.float64, device="cuda:0")
+    eye = np.array([1.0, 1.0, 1.0, 0.0, 0.0])[None]
+    u = np.random.default_rng(2051).random((n, 5)) - 0.5
+    pick = np.random.default_rng(2052).random(n) < 0.5
+    b5, b9 = m5.algorithmic_bytes_per_point, m9.algorithmic_bytes_per_point
+    r = {"law": "log_strain_plane", "points": n, "kernel": m5.kernel_name, "nine_wide_kernel": m9.kernel_name, "params": [210e9, 0.3, s0, H0],
+         "algorithmic_bytes_per_point": b5, "nine_wide_bytes_per_point": b9, "byte_ratio": round(b5 / b9, 3), "batches": {},
+         "warmup": a.warmup, "reps": a.reps}
+    g5_mixed = None
+    for kind, amp in (("elastic", 5e-4), ("mixed", np.where(pick, 2e-2, 5e-4)[:, None]), ("yielded", 2e-2)):
+        F5 = eye + amp * u
+        g5, g9 = to_device(F5), to_device(embed_plane_F(F5))
+        del F5
+        t5, t9 = [], []
+        for _ in range(3):          # interleaved: both kernels see the same drift of the machine
+            t9.append(timed(m9, g9, f9, c9))
+            t5.append(timed(m5, g5, f5, c5))
+        _, s5 = m5.stats()
+        _, s9 = m9.stats()
+        # the restriction, on the device: what law 42 writes against components / rows / columns 0..4 of law 19's outputs
+        dP = float((f5 - f9[:, :5]).abs().max() / f9.abs().max())
+        dA = float((c5.view(n, 5, 5) - c9.view(n, 9, 9)[:, :5, :5]).abs().max() / c9.abs().max())
+        ms5, ms9 = float(np.median(t5)), float(np.median(t9))
+        r["batches"][kind] = {"kernel_ms_repeats": [round(x, 4) for x in t5], "kernel_ms": round(ms5, 4), "frac_of_8TBs": round(b5 * n / ms5 / 1e6 / 8000, 4),
+                              "nine_wide_ms_repeats": [round(x, 4) for x in t9], "nine_wide_ms": round(ms9, 4),
+                              "nine_wide_frac_of_8TBs": round(b9 * n / ms9 / 1e6 / 8000, 4), "ratio_to_nine_wide": round(ms5 / ms9, 3),
+                              "ratio_to_byte_scaled_nine_wide": round(ms5 / (ms9 * b5 / b9), 3),
+                              "n_plastic": s5["n_plastic"], "nine_wide_n_plastic": s9["n_plastic"], "n_nan": s5["n_nan"], "nine_wide_n_nan": s9["n_nan"],
+                              "max_abs_difference_to_nine_wide_restricted": {"P_over_max_P": dP, "A_over_max_A": dA}}
+        if kind == "mixed":
+            g5_mixed = g5
+        del g9
+    if a.blocks_per_cu:
+        sweep = {}
+        for b in a.blocks_per_cu:
+            m5.set_option("blocks_per_cu", b)
+            sweep[b] = round(timed(m5, g5_mixed, f5, c5), 4)
+        m5.set_option("blocks_per_cu", 256)      # the shipped grid again (log_strain_plane.hpp)
+        r["mixed_kernel_ms_by_blocks_per_cu"] = sweep
+    print(json.dumps(r), flush=True)
+    m5.close()
+    m9.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=10_000_000)
@@ -890,13 +969,14 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0, help="also time the plain-C oracle on this many points")
     ap.add_argument("--sym", action="store_true", help="symmetric-packed tangent (small-strain laws)")
     ap.add_argument("--blocks-per-cu", type=int, nargs="+", default=None,
-                    help="ramberg_osgood, plane_strain, ps_j2, ps_hosford, heat_plane, ogden_plane, pe_hosford: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
+                    help="ramberg_osgood, plane_strain, ps_j2, ps_hosford, heat_plane, ogden_plane, pe_hosford, log_strain_plane: time the kernel at each of these grid sizes (dxm option blocks_per_cu) as well")
     ap.add_argument("--param-fields", type=int, nargs="+", default=None, metavar="K",
                     help="j2_linear / j2_voce: also time the kernel with K bound per-point parameter streams (1 ... 4 | 5)")
     a = ap.parse_args()
     if a.cpu_sample and ("ramberg_osgood" in a.laws or "ogden" in a.laws or "hosford" in a.laws or "orthotropic" in a.laws or "single_crystal" in a.laws or
                          "heat_stationary" in a.laws or "heat_phase_change" in a.laws or "heat_plane" in a.laws or "log_strain" in a.laws or "fs_single_crystal" in a.laws or
-                         any(law.startswith("ps_") for law in a.laws) or "plane_strain" in a.laws or "ogden_plane" in a.laws or "pe_hosford" in a.laws):   # (ps_j2 among them)
+                         any(law.startswith("ps_") for law in a.laws) or "plane_strain" in a.laws or "ogden_plane" in a.laws or "pe_hosford" in a.laws or
+                         "log_strain_plane" in a.laws):   # (ps_j2 among them)
         ap.error("--cpu-sample: the plain-C oracle (oracle/oracle_c.c) has no Ramberg-Osgood, Ogden, Hosford, orthotropic, single-crystal, heat-transfer or logarithmic-strain law")
     import torch
 
@@ -942,6 +1022,9 @@ def main():
             continue
         if law == "pe_hosford":   # law 40 beside law 10 of this process on the embedded strain, three batch kinds: one line
             bench_pe_hosford(a)
+            continue
+        if law == "log_strain_plane":   # law 42 beside law 19 of this process on the embedded gradient, three batch kinds: one line
+            bench_log_strain_plane(a)
             continue
         if law == "ramberg_osgood":
             ro_eps = ramberg_osgood_strains(n)

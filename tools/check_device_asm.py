@@ -5,7 +5,7 @@ hosford,orthotropic}.hip), on the cross-compiler alone:
 1. the resources of every kernel, read from -Rpass-analysis=kernel-resource-usage: no scratch and no spilled VGPR anywhere, and
    the kernels with per-point parameter fields within the bounds of the uniform J2 kernels (at most 128 VGPRs, the same static LDS,
    exactly 32 instantiations);
-   With --all-units the same for the units added since (LATER_UNITS and PLANE_FORM_UNITS below), whose kernels need not keep to the
+   With --all-units the same for the units added since (LATER_UNITS, PLANE_FORM_UNITS and PLANE_F_UNITS below), whose kernels need not keep to the
    bounds of the J2 kernels;
 2. (--parent REV) the device assembly of every unit is byte for byte what the sources of git revision REV give (but for the
    compilation-unit id, which hashes the source file's path); the parent's resource figures are printed beside the tree's.
@@ -37,6 +37,9 @@ LATER_UNITS = ("small_strain_clean", "single_crystal", "heat_transfer", "log_str
 # the plane-strain forms of laws 7 and 10 (--all-units walks them after LATER_UNITS, in the same way).  A list of its own:
 # tests/test_ogden_plane_build.py pins LATER_UNITS to the units that existed before ogden_plane
 PLANE_FORM_UNITS = ("ogden_plane", "hosford_plane")
+# the plane-strain form of law 19, walked after them in the same way.  Again a list of its own: tests/test_hosford_plane_build.py
+# pins PLANE_FORM_UNITS to the two units above
+PLANE_F_UNITS = ("log_strain_plane",)
 MAX_VGPRS = 128
 J2_STATIC_LDS = 30848     # small_strain.hpp: 4 waves x (64 x 6 + 64 x 9) doubles + the 4 x 4 status words
 
@@ -105,13 +108,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", default=None, help="git revision whose device assembly must be reproduced")
     ap.add_argument("--write-digests", default=None, help="with --parent: write the parent's digests to this JSON file")
-    ap.add_argument("--all-units", action="store_true", help="also the units added after the first six: " + ", ".join(LATER_UNITS + PLANE_FORM_UNITS))
+    ap.add_argument("--all-units", action="store_true", help="also the units added after the first six: " + ", ".join(LATER_UNITS + PLANE_FORM_UNITS + PLANE_F_UNITS))
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         new = build_units(CSRC, tmp, "tree")
         later_new, later_old = {}, {}
         if a.all_units:
-            later_new = build_units(CSRC, tmp, "tree", LATER_UNITS + PLANE_FORM_UNITS)
+            later_new = build_units(CSRC, tmp, "tree", LATER_UNITS + PLANE_FORM_UNITS + PLANE_F_UNITS)
         old = None
         if a.parent:
             src = os.path.join(tmp, "parent")
@@ -120,7 +123,7 @@ def main():
             subprocess.run(["tar", "-x", "-C", src], input=tar.stdout, check=True)
             old = build_units(os.path.join(src, "dolfinx_materials_amd", "csrc"), tmp, "parent")
             if a.all_units:
-                there = tuple(u for u in LATER_UNITS + PLANE_FORM_UNITS if os.path.exists(os.path.join(src, "dolfinx_materials_amd", "csrc", u + ".hip")))
+                there = tuple(u for u in LATER_UNITS + PLANE_FORM_UNITS + PLANE_F_UNITS if os.path.exists(os.path.join(src, "dolfinx_materials_amd", "csrc", u + ".hip")))
                 later_old = build_units(os.path.join(src, "dolfinx_materials_amd", "csrc"), tmp, "parent", there)
 
     fmt = lambda r: (f"VGPRs {r['vgprs']:3d}  AGPRs {r['agprs']}  SGPRs {r['sgprs']:3d}  scratch {r['scratch']}  spilled VGPRs {r['vgpr_spill']}  "   # noqa: E731
@@ -138,7 +141,7 @@ def main():
     # the later units: resources, and the parent's assembly where the parent has the unit (a line format of their own: the lines of
     # the first six are counted by tests)
     later_same = True
-    for unit in LATER_UNITS + PLANE_FORM_UNITS if a.all_units else ():
+    for unit in LATER_UNITS + PLANE_FORM_UNITS + PLANE_F_UNITS if a.all_units else ():
         table = later_new[unit][1]
         print(f"== {unit}: {len(table)} kernels")
         for name in sorted(table):
