@@ -176,6 +176,12 @@ SYMBOLS = {
          C.c_int],
     ),
     "dxm_mesh_scalar_gradient_device": (C.c_int, [_h, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dxm_mesh_create_axisymmetric": (
+        _h,
+        [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+         C.c_void_p, C.c_int, C.c_int],
+    ),
+    "dxm_mesh_axisymmetric_gradient_device": (C.c_int, [_h, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dxm_mesh_destroy": (C.c_int, [_h]),
     "dxm_mesh_npoints": (C.c_int64, [_h]),
     "dxm_mesh_displacement_size": (C.c_int64, [_h]),

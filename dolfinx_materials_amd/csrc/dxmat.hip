@@ -43,6 +43,7 @@
 #include "plane_stress_j2.hpp"
 #include "plane_stress_hosford.hpp"
 #include "plane_gradient.hpp"
+#include "axisym_gradient.hpp"
 #include "heat_plane.hpp"
 #include "ogden_plane.hpp"
 #include "hosford_plane.hpp"
@@ -2990,6 +2991,11 @@ struct dxm_mesh {
   // at the Gauss points, (nqp, nd), beside their derivatives.  Read by heat_plane.hip only: every kind of dxm_mesh_gradient_device refuses
   bool scalar = false;
   double* d_phi = nullptr;
+  // a meridian mesh (dxm_mesh_create_axisymmetric): column 0 of the coordinates is r, column 1 is z.  A displacement mesh with the
+  // value tables of the field (d_phi) and of the geometry (d_gphi, (nqp, geom_nv)) beside the derivative tables: what
+  // axisym_gradient.hip reads for the hoop term u_r / r.  Every kind of dxm_mesh_gradient_device refuses
+  bool axisym = false;
+  double* d_gphi = nullptr;
 };
 
 // triangles through dxm_mesh_create_simplex, triangles and quadrilaterals through dxm_mesh_create_plane
@@ -3112,17 +3118,19 @@ dxm_mesh* dxm_mesh_create_simplex(int tdim, const double* coords, int64_t n_vert
   return mesh;
 }
 
-// dxm_mesh_create_plane (components 2, phi null) and dxm_mesh_create_plane_scalar (components 1, with the value table phi)
+// dxm_mesh_create_plane (components 2, phi null), dxm_mesh_create_plane_scalar (components 1, with the value table phi) and
+// dxm_mesh_create_axisymmetric (components 2, axisym: with the value tables phi and geom_phi)
 static dxm_mesh* plane_mesh_create(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
                                    const int32_t* dofmap, int nd, int64_t n_dofs, const double* geom_dphi, const double* phi,
-                                   const double* dphi, int nqp, int device, int components) {
+                                   const double* dphi, int nqp, int device, int components, bool axisym = false,
+                                   const double* geom_phi = nullptr) {
   const bool scalar = components == 1;
   // every check runs on the host before a device is asked for: the kernels are never launched on indices that were not checked
   if (nv != 3 && nv != 4) {
     fail(-1, "a plane mesh has nv = 3 (triangles) or nv = 4 (bilinear quadrilaterals) vertices per cell, not %d", nv);
     return nullptr;
   }
-  if (!coords || !geom_conn || !dofmap || !geom_dphi || !dphi || (scalar && !phi) || n_vertices <= 0 || n_cells <= 0 || nd < nv ||
+  if (!coords || !geom_conn || !dofmap || !geom_dphi || !dphi || (scalar && !phi) || (axisym && (!phi || !geom_phi)) || n_vertices <= 0 || n_cells <= 0 || nd < nv ||
       nd > PLANE_GRAD_MAX_ND || n_dofs <= 0 || nqp <= 0 || nqp > PLANE_GRAD_MAX_NQP) {
     fail(-1, "invalid plane mesh arguments");
     return nullptr;
@@ -3162,6 +3170,24 @@ static dxm_mesh* plane_mesh_create(const double* coords, int64_t n_vertices, con
       }
     }
   }
+  if (axisym) {   // after det J: a NaN in a table would reach every point; then r at every Gauss point, the divisor of the hoop term
+    const struct { const char* name; const double* tab; int64_t len; } tabs[4] = {
+        {"phi", phi, (int64_t)nqp * nd}, {"dphi", dphi, (int64_t)nqp * nd * 2}, {"geom_phi", geom_phi, (int64_t)nqp * nv},
+        {"geom_dphi", geom_dphi, (int64_t)nqp * nv * 2}};
+    for (const auto& t : tabs)
+      for (int64_t k = 0; k < t.len; ++k)
+        if (!std::isfinite(t.tab[k])) { fail(-1, "table %s: entry %lld is not finite", t.name, (long long)k); return nullptr; }
+    for (int64_t c = 0; c < n_cells; ++c)
+      for (int q = 0; q < nqp; ++q) {
+        double rad = 0.0;
+        for (int v = 0; v < nv; ++v) rad += coords[3 * (int64_t)geom_conn[c * nv + v]] * geom_phi[(int64_t)q * nv + v];
+        if (!(rad > 0.0) || !std::isfinite(rad)) {
+          fail(-1, "cell %lld: r = %g at Gauss point %d: an axisymmetric mesh lies on one side of the axis (r > 0 at every Gauss "
+                   "point), with no Gauss point on it", (long long)c, rad, q);
+          return nullptr;
+        }
+      }
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
     fail(-2, "no usable HIP device %d (libdxmat has no CPU fallback)", device);
@@ -3171,6 +3197,7 @@ static dxm_mesh* plane_mesh_create(const double* coords, int64_t n_vertices, con
   mesh->nodes_per_cell = 0;
   mesh->plane = true;
   mesh->scalar = scalar;
+  mesh->axisym = axisym;
   mesh->device = device;
   mesh->n_nodes = n_vertices;
   mesh->n_cells = n_cells;
@@ -3193,9 +3220,13 @@ static dxm_mesh* plane_mesh_create(const double* coords, int64_t n_vertices, con
   ok = ok && upload_from_host(mesh->d_dofmap, dofmap, sizeof(int32_t) * nd * n_cells, nullptr) == 0;
   ok = ok && upload_from_host(mesh->d_gdphi, geom_dphi, sizeof(double) * nqp * nv * 2, nullptr) == 0;
   ok = ok && upload_from_host(mesh->d_dphi, dphi, sizeof(double) * nqp * nd * 2, nullptr) == 0;
-  if (scalar) {
+  if (scalar || axisym) {
     ok = ok && hipMalloc(&mesh->d_phi, sizeof(double) * nqp * nd) == hipSuccess;
     ok = ok && upload_from_host(mesh->d_phi, phi, sizeof(double) * nqp * nd, nullptr) == 0;
+  }
+  if (axisym) {
+    ok = ok && hipMalloc(&mesh->d_gphi, sizeof(double) * nqp * nv) == hipSuccess;
+    ok = ok && upload_from_host(mesh->d_gphi, geom_phi, sizeof(double) * nqp * nv, nullptr) == 0;
   }
   if (!ok) {
     fail(-3, "device allocation / upload of the mesh failed");
@@ -3217,6 +3248,13 @@ dxm_mesh* dxm_mesh_create_plane_scalar(const double* coords, int64_t n_vertices,
   return plane_mesh_create(coords, n_vertices, geom_conn, nv, n_cells, dofmap, nd, n_dofs, geom_dphi, phi, dphi, nqp, device, 1);
 }
 
+dxm_mesh* dxm_mesh_create_axisymmetric(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
+                                       const int32_t* dofmap, int nd, int64_t n_dofs, const double* geom_phi, const double* geom_dphi,
+                                       const double* phi, const double* dphi, int nqp, int device) {
+  return plane_mesh_create(coords, n_vertices, geom_conn, nv, n_cells, dofmap, nd, n_dofs, geom_dphi, phi, dphi, nqp, device, 2, true,
+                           geom_phi);
+}
+
 int dxm_mesh_destroy(dxm_mesh* mesh) {
   if (!mesh) return 0;
   RelaxedCaptureMode relaxed;
@@ -3228,6 +3266,7 @@ int dxm_mesh_destroy(dxm_mesh* mesh) {
   if (mesh->d_dphi) (void)hipFree(mesh->d_dphi);
   if (mesh->d_gdphi) (void)hipFree(mesh->d_gdphi);
   if (mesh->d_phi) (void)hipFree(mesh->d_phi);
+  if (mesh->d_gphi) (void)hipFree(mesh->d_gphi);
   if (mesh->grad_done) (void)hipEventDestroy(mesh->grad_done);
   delete mesh;
   return 0;
@@ -3244,6 +3283,9 @@ int dxm_mesh_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, doub
   if (mesh->scalar)
     return fail(-1, "a scalar mesh (dxm_mesh_create_plane_scalar) holds one value per dof, not a displacement: it has no strain or "
                     "deformation gradient of any kind; dxm_mesh_scalar_gradient_device evaluates grad(T) and T on it");
+  if (mesh->axisym)
+    return fail(-1, "an axisymmetric mesh (dxm_mesh_create_axisymmetric) has a hoop term u_r / r in every strain and deformation "
+                    "gradient, which none of these kinds holds: dxm_mesh_axisymmetric_gradient_device evaluates its four kinds");
   if (kind < 0 || kind > 3)
     return fail(-1, "gradient kind must be 0 (strain), 1 (F), 2 (plane-strain 4-vector) or 3 (in-plane 3-vector)");
   if (kind >= 2 && !mesh_2d(mesh))
@@ -3334,6 +3376,92 @@ int dxm_mesh_scalar_gradient_device(dxm_mesh* mesh, const double* t_dev, double*
   HIP_TRY(scalar_gradient_launch((hipStream_t)hip_stream, scalar_source(mesh, t_dev), mesh->n_cells * mesh->qp.nqp, grad_dev, value_dev));
   return 0;
 #endif
+}
+
+// ---- a meridian mesh: the gradients with the hoop term u_r / r, and the displacement forms of the laws that read them -------------
+int dxm_mesh_axisymmetric_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, double* grad_dev, double* radius_dev,
+                                          void* hip_stream) {
+  if (!mesh || !u_dev || !grad_dev) return fail(-1, "null argument");
+  if (!mesh->axisym)
+    return fail(-1, "dxm_mesh_axisymmetric_gradient_device needs an axisymmetric mesh (dxm_mesh_create_axisymmetric): the gradients "
+                    "of this mesh are those of dxm_mesh_gradient_device");
+  if (kind < 0 || kind > 3)
+    return fail(-1, "axisymmetric gradient kind must be 0 (4-vector [rr, zz, tt, sqrt(2) rz]), 1 (5-wide F), 2 (6-wide strain) or 3 "
+                    "(9-wide F)");
+  if ((kind == 0 || kind == 2) && ((uintptr_t)grad_dev & 15))
+    return fail(-1, "the gradient device array must be 16-byte aligned for axisymmetric gradient kinds 0 and 2");
+#ifdef DXM_CUSTOM_HARDENING
+  return fail(-1, "the axisymmetric gradient kernels (a mesh of dxm_mesh_create_axisymmetric) are served by the stock libdxmat, not by "
+                  "a custom-hardening build, which is dxmat.hip alone");
+#else
+  DEVICE_GUARD(mesh);
+  AxisymSource s{};
+  s.coords = mesh->d_coords; s.conn = mesh->d_conn; s.dofmap = mesh->d_dofmap; s.gphi = mesh->d_gphi; s.gdphi = mesh->d_gdphi;
+  s.phi = mesh->d_phi; s.dphi = mesh->d_dphi; s.u = u_dev;
+  s.npts = mesh->n_cells * mesh->qp.nqp; s.nqp = mesh->qp.nqp; s.nv = mesh->geom_nv; s.nd = mesh->nd;
+  HIP_TRY(axisym_gradient_launch(kind, (hipStream_t)hip_stream, s, grad_dev, radius_dev));
+  return 0;
+#endif
+}
+
+// which kind the law's row asks an axisymmetric mesh for (*kind), or the refusal of the pairing, the handle left as it was.  The slots
+// of MGIS's axisymmetric hypothesis are those of its plane-strain one, so the 4-wide rows take kind 0 and the 6- / 9-wide laws the
+// embedded kinds; the rows are told apart by what they state themselves, not by their ids
+static int axisym_pairing(const dxm_material* m, const dxm_mesh* mesh, int* kind) {
+  const LawDesc& d = kLaws[m->law];
+  if (d.nodal_scalar)
+    return fail(-1, "an axisymmetric mesh (dxm_mesh_create_axisymmetric) carries a displacement (u_r, u_z): the two-dimensional "
+                    "heat-transfer laws read a scalar field and take a scalar mesh (dxm_mesh_create_plane_scalar) or grad(T) as an "
+                    "array, not this mesh (law %d)", m->law);
+  if (d.plane_kind == GRAD_IN_PLANE3)
+    return fail(-1, "plane stress and axisymmetry exclude each other: law %d takes the in-plane 3-vector [xx, yy, sqrt(2) xy] and has no "
+                    "hoop component, an axisymmetric mesh (dxm_mesh_create_axisymmetric) serves the 4-wide plane-strain rows and the "
+                    "6- and 9-wide laws", m->law);
+  if (d.no_displacement && !d.plane_kind) return fail(-1, "%s", d.no_displacement);   // as on every other mesh (the 5-wide rows: kind 1, then the array form)
+  if (mesh->device != m->device) return fail(-1, "mesh and material live on different devices");
+  if (dxm_mesh_npoints(mesh) != m->n) return fail(-1, "mesh has %lld Gauss points, material %lld",
+                                                   (long long)dxm_mesh_npoints(mesh), (long long)m->n);
+  *kind = d.plane_kind == GRAD_PLANE_STRAIN4 ? AXI_STRAIN4 : d.n_grad == 9 ? AXI_F9 : AXI_STRAIN6;
+  if (d.n_grad != AXISYM_GRAD_WIDTH[*kind])   // the scratch array holds rows of n_grad doubles: no kernel writes a wider row into it
+    return fail(-1, "law %d reads a gradient of %d components: an axisymmetric mesh evaluates rows of 4, 6 or 9 for the displacement forms",
+                m->law, d.n_grad);
+  return 0;
+}
+
+// dxm_integrate_displacement / _rows on an axisymmetric mesh: the gradient kernel into the handle's scratch, then the update kernel
+// (no fused form: fused_gradient makes no difference)
+static int integrate_axisym_host(dxm_material* m, dxm_mesh* mesh, const double* u_host, double* flux_aos, double* isv_aos, double* ct_aos,
+                                 dxm_stats* stats, const int64_t* rows) {
+  int kind = 0;
+  if (int rc = axisym_pairing(m, mesh, &kind)) return rc;
+  DEVICE_GUARD(m);
+  m->last_upload = DXM_UPLOAD_NONE;   // no gradient array crosses PCIe in this form
+  if (int rc = ensure_host_path_buffers(m, true)) return rc;
+  hipStream_t st = m->own_stream;
+  if (int rc = sync_last(m)) return rc;
+  if (int rc = upload_from_host(mesh->d_u, u_host, sizeof(double) * mesh->u_len, st)) return rc;
+  if (int rc = dxm_mesh_axisymmetric_gradient_device(mesh, mesh->d_u, kind, m->d_grad, nullptr, st)) return rc;
+  // the displacement upload and the gradient array are produced on own_stream; chunks on the second stream wait for it
+  if (!mesh->grad_done) HIP_TRY(hipEventCreateWithFlags(&mesh->grad_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(mesh->grad_done, st));
+  auto upload = [&](int64_t, int64_t, hipStream_t s) -> int {
+    if (s != st) HIP_TRY(hipStreamWaitEvent(s, mesh->grad_done, 0));
+    return 0;
+  };
+  return run_and_download(m, upload, flux_aos, isv_aos, ct_aos, stats, nullptr, nullptr, rows);
+}
+
+// dxm_integrate_displacement_device on an axisymmetric mesh: two kernels on the caller's stream through the handle's gradient scratch
+static int integrate_axisym_device(dxm_material* m, dxm_mesh* mesh, const double* u_dev, double dt, double* flux_dev, double* ct_dev,
+                                   void* hip_stream) {
+  int kind = 0;
+  if (int rc = axisym_pairing(m, mesh, &kind)) return rc;
+  if (int rc = take_dt(m, dt)) return rc;
+  if (m->n > 0 && (!u_dev || !flux_dev || !ct_dev)) return fail(-1, "null device pointer");
+  DEVICE_GUARD(m);
+  if (!m->d_grad) HIP_TRY(hipMalloc(&m->d_grad, sizeof(double) * m->n * kLaws[m->law].n_grad));
+  if (int rc = dxm_mesh_axisymmetric_gradient_device(mesh, u_dev, kind, m->d_grad, nullptr, hip_stream)) return rc;
+  return launch(m, m->d_grad, flux_dev, ct_dev, (hipStream_t)hip_stream);
 }
 
 // a scalar mesh and a law that reads a scalar field belong together: every other pairing is refused, the handle left as it was
@@ -3433,6 +3561,7 @@ static int integrate_nodal_device(dxm_material* m, dxm_mesh* mesh, const double*
 static int integrate_displacement_host(dxm_material* m, dxm_mesh* mesh, const double* u_host, double* flux_aos, double* isv_aos,
                                        double* ct_aos, dxm_stats* stats, const int64_t* rows) {
   if (!m || !mesh || !u_host) return fail(-1, "null argument");
+  if (mesh->axisym) return integrate_axisym_host(m, mesh, u_host, flux_aos, isv_aos, ct_aos, stats, rows);   // a meridian mesh: its own gradient kernel
   if (nodal_pairing(m, mesh)) return integrate_nodal_host(m, mesh, u_host, flux_aos, isv_aos, ct_aos, stats, rows);   // a scalar field's nodal values
   const bool plane_law = kLaws[m->law].plane_kind && mesh_2d(mesh);   // a 2-D law on a 2-D mesh: gradient kernel, then update kernel
   if (kLaws[m->law].no_displacement && !plane_law) return fail(-1, "%s", kLaws[m->law].no_displacement);
@@ -3479,6 +3608,7 @@ int dxm_integrate_displacement_rows(dxm_material* m, dxm_mesh* mesh, const doubl
 int dxm_integrate_displacement_device(dxm_material* m, dxm_mesh* mesh, const double* u_dev, double dt,
                                       double* flux_dev, double* ct_dev, void* hip_stream) {
   if (!m || !mesh) return fail(-1, "null argument");
+  if (mesh->axisym) return integrate_axisym_device(m, mesh, u_dev, dt, flux_dev, ct_dev, hip_stream);   // a meridian mesh: its own gradient kernel
   if (nodal_pairing(m, mesh)) return integrate_nodal_device(m, mesh, u_dev, dt, flux_dev, ct_dev, hip_stream);   // a scalar field's nodal values
   const bool plane_law = kLaws[m->law].plane_kind && mesh_2d(mesh);   // the 2-D laws have no fused form: the option makes no difference
   if (kLaws[m->law].no_displacement && !plane_law) return fail(-1, "%s", kLaws[m->law].no_displacement);

@@ -1,6 +1,7 @@
 """Device-side gradient evaluation for first-order hexahedra / tetrahedra, for Lagrange elements of any order on
 straight-sided simplices and for plane meshes of triangles or bilinear quadrilaterals (``dxm_mesh_*`` of ``include/dxmat.h``); a scalar
-field on a plane mesh (:class:`PlaneScalarMesh`: the temperature and its gradient, for the two-dimensional heat-transfer laws).
+field on a plane mesh (:class:`PlaneScalarMesh`: the temperature and its gradient, for the two-dimensional heat-transfer laws); a
+displacement on a meridian mesh (:class:`AxisymmetricMesh`: the gradients with the hoop term ``u_r / r`` of the axisymmetric hypothesis).
 
 The step before the hot path in the reference is ``QuadratureExpression.eval`` ->
 ``fem.Expression.eval`` (``quadrature_function.py:45-51``): dolfinx tabulates the UFL gradient at
@@ -562,3 +563,157 @@ class PlaneScalarMesh(_DeviceMesh):
         if cells is not None:
             geom_conn, dofmap = geom_conn[np.asarray(cells)], dofmap[np.asarray(cells)]
         return cls(np.asarray(mesh.geometry.x), geom_conn, dofmap, n_dofs, geom_dphi, phi, dphi, device=device)
+
+
+# ---- axisymmetric meshes: the meridian half plane (r, z) ----------------------------------------------------------------------------
+def axisymmetric_radii(coords, geom_conn, geom_phi):
+    """``r = sum_v r_v geom_phi[q, v]`` at the Gauss points of a meridian mesh, (n_cells * nqp), summed in the table's local order
+    from 0.0 as the library's check and the kernel do: what :meth:`AxisymmetricMesh.radii` returns.  No GPU."""
+    r = np.asarray(coords, dtype=np.float64)[np.asarray(geom_conn), 0]
+    geom_phi = np.asarray(geom_phi, dtype=np.float64)
+    rad = np.zeros((r.shape[0], geom_phi.shape[0]))
+    for v in range(r.shape[1]):
+        rad = rad + r[:, v, None] * geom_phi[None, :, v]
+    return rad.reshape(-1)
+
+
+class AxisymmetricMesh(_DeviceMesh):
+    """Lagrange displacement ``(u_r, u_z)`` of any order on a MERIDIAN mesh of triangles or bilinear quadrilaterals
+    (``dxm_mesh_create_axisymmetric``): column 0 of ``coords`` is ``r``, column 1 is ``z``.  This is the reference's
+    ``hypothesis="axisymmetric"``.  Under MGIS that hypothesis has the slots of the plane-strain one -- ``[rr, zz, tt, sqrt(2) rz]`` for a
+    symmetric tensor, ``[F_rr, F_zz, F_tt, F_rz, F_zr]`` for ``F`` -- and an isotropic behaviour does nothing different; what changes is
+    the caller's gradient, ``eps_tt = u_r / r`` and ``F_tt = 1 + u_r / r``.  So the hypothesis lives on the MESH: a behaviour built with
+    ``hypothesis="plane_strain"`` (or a ``"3d"`` one) on this mesh IS the axisymmetric law; the string ``"axisymmetric"`` itself is
+    still refused by the behaviours.
+
+    Arguments as for :class:`PlaneMesh`, plus the VALUES of the shape functions at the Gauss points: ``geom_phi`` (nqp, nv) of the
+    geometry's (for ``r``) and ``phi`` (nqp, nd) of the field's (for ``u_r``).  The library checks, before it touches a device, every
+    index, ``det J``, every table entry and ``r > 0`` at every Gauss point: the mesh lies on one side of the axis.
+
+    The mesh goes where a :class:`PlaneMesh` goes (``HIPMaterial.integrate_displacement*``,
+    ``QuadratureMap.register_device_gradient``): the 4-wide plane-strain laws, the 6-wide and the 9-wide laws.  The 5-wide laws (Ogden and
+    logarithmic-strain plasticity under plane strain) take kind 1 of :meth:`axisymmetric_gradient_device` followed by the array form;
+    the plane-stress and heat-transfer laws are refused.  :meth:`gradient_device` refuses.  :meth:`radii` gives ``r`` at the Gauss
+    points for the measure ``2 pi r w |det J|`` (assembly is the caller's)."""
+
+    tdim = 2
+    #: the gradients of this mesh carry the hoop term: :meth:`axisymmetric_gradient_device`, not :meth:`gradient_device`
+    axisymmetric = True
+
+    def __init__(self, coords, geom_conn, dofmap, n_dofs, geom_phi, geom_dphi, phi, dphi, device=0):
+        self._lib = _lib.load()
+        geom_conn = np.ascontiguousarray(geom_conn, dtype=np.int32)
+        coords = np.asarray(coords, dtype=np.float64)
+        if coords.shape[1] == 2:
+            coords = np.concatenate([coords, np.zeros((len(coords), 1))], axis=1)
+        coords = np.ascontiguousarray(coords)
+        dofmap = np.ascontiguousarray(dofmap, dtype=np.int32)
+        geom_phi = np.ascontiguousarray(geom_phi, dtype=np.float64)
+        geom_dphi = np.ascontiguousarray(geom_dphi, dtype=np.float64)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        dphi = np.ascontiguousarray(dphi, dtype=np.float64)
+        if dphi.ndim != 3 or dphi.shape[1] != dofmap.shape[1] or dphi.shape[2] != 2 or len(dofmap) != len(geom_conn):
+            raise ValueError("dphi must be (nqp, nd, 2) with nd = dofmap.shape[1]; one dofmap row per cell")
+        if phi.shape != dphi.shape[:2]:
+            raise ValueError("phi must be (nqp, nd), the values beside the derivatives dphi (nqp, nd, 2)")
+        if geom_dphi.shape != (dphi.shape[0], geom_conn.shape[1], 2):
+            raise ValueError("geom_dphi must be (nqp, nv, 2) with nv = geom_conn.shape[1] and the nqp of dphi")
+        if geom_phi.shape != geom_dphi.shape[:2]:
+            raise ValueError("geom_phi must be (nqp, nv), the values beside the derivatives geom_dphi (nqp, nv, 2)")
+        self.n_nodes, self.n_cells, self.nqp = coords.shape[0], geom_conn.shape[0], dphi.shape[0]
+        self.nv, self.nd, self.n_dofs, self.device = geom_conn.shape[1], dofmap.shape[1], int(n_dofs), int(device)
+        h = self._lib.dxm_mesh_create_axisymmetric(coords.ctypes.data, self.n_nodes, geom_conn.ctypes.data, self.nv, self.n_cells,
+                                                   dofmap.ctypes.data, self.nd, self.n_dofs, geom_phi.ctypes.data, geom_dphi.ctypes.data,
+                                                   phi.ctypes.data, dphi.ctypes.data, self.nqp, self.device)
+        if not h:
+            raise _lib.DxmError(f"dxm_mesh_create_axisymmetric failed: {_lib.last_error()}")
+        self._handle = h
+        self._radii = axisymmetric_radii(coords, geom_conn, geom_phi)
+
+    def gradient_device(self, u_ptr, kind, grad_ptr, stream=0):
+        """Refused with the library's sentence: no kind of ``dxm_mesh_gradient_device`` holds the hoop term.  Use
+        :meth:`axisymmetric_gradient_device`."""
+        super().gradient_device(u_ptr, kind, grad_ptr, stream)
+
+    def axisymmetric_gradient_device(self, u_ptr, kind, grad_ptr, radius_ptr=0, stream=0):
+        """Device pointers, asynchronous on ``stream``.  With ``H[i][a] = du_i / dX_a`` in ``(r, z)``, ``hoop = u_r / r`` and
+        ``s = sqrt(2) / 2``, ``kind`` (numbered by this entry point alone)
+
+        * 0: ``[H00, H11, hoop, s (H01 + H10)]``, the strain of the ``hypothesis="plane_strain"`` laws (4);
+        * 1: ``[1 + H00, 1 + H11, 1 + hoop, H01, H10]``, the ``F`` of the 5-wide laws (5);
+        * 2: ``[H00, H11, hoop, s (H01 + H10), 0, 0]``, the Mandel strain of the 6-wide laws (6);
+        * 3: ``[1 + H00, 1 + H11, 1 + hoop, H01, H10, 0, 0, 0, 0]``, the ``F`` of the 9-wide laws (9).
+
+        ``grad_ptr`` holds ``npoints`` rows (16-byte aligned for kinds 0 and 2); unless ``radius_ptr`` is 0, ``r`` at the Gauss points
+        goes into its ``npoints`` doubles."""
+        _lib.check(self._lib.dxm_mesh_axisymmetric_gradient_device(self._handle, int(u_ptr), int(kind), int(grad_ptr),
+                                                                   int(radius_ptr) or None, int(stream) or None))
+
+    def radii(self):
+        """``r`` at the Gauss points, host array (npoints), from the tables alone (no GPU): the measure of the hypothesis is
+        ``2 pi r w |det J|``."""
+        return self._radii.copy()
+
+    @classmethod
+    def lagrange(cls, coords, cells, degree=1, quadrature_degree=None, device=0):
+        """Stand-alone constructor (no dolfinx), the mirror of :meth:`PlaneMesh.lagrange`: a first- or second-order displacement on
+        the vertex mesh ``(coords, cells)`` of triangles or quadrilaterals in the ``(r, z)`` half plane, the same dof numbering, points
+        and default quadrature degrees.  Returns ``(mesh, dof_coords)``."""
+        coords, cells = np.asarray(coords, dtype=np.float64), np.asarray(cells)
+        if degree not in (1, 2):
+            raise ValueError("AxisymmetricMesh.lagrange: degree 1 or 2 (hand any other table to AxisymmetricMesh directly)")
+        if cells.shape[1] == 3:
+            pts = simplex_quadrature(2, 2 * (degree - 1) if quadrature_degree is None else quadrature_degree)
+            geom_phi, geom_dphi = lagrange_simplex_values(2, 1, pts), lagrange_simplex_table(2, 1, pts)
+            phi, dphi = lagrange_simplex_values(2, degree, pts), lagrange_simplex_table(2, degree, pts)
+            dofmap, n_dofs, edges = p2_dofmap(cells) if degree == 2 else (cells, len(coords), None)
+            inner = np.empty((0, coords.shape[1]))
+        elif cells.shape[1] == 4:
+            pts = quad_quadrature(2 * degree if quadrature_degree is None else quadrature_degree)
+            geom_phi, geom_dphi = lagrange_quad_values(1, pts), lagrange_quad_table(1, pts)
+            phi, dphi = lagrange_quad_values(degree, pts), lagrange_quad_table(degree, pts)
+            dofmap, n_dofs, edges = q2_dofmap(cells) if degree == 2 else (cells, len(coords), None)
+            inner = coords[cells].mean(axis=1)            # the bilinear image of (1/2, 1/2)
+        else:
+            raise ValueError("AxisymmetricMesh.lagrange: cells with 3 (triangles) or 4 (quadrilaterals) vertices")
+        mesh = cls(coords, cells, dofmap, n_dofs, geom_phi, geom_dphi, phi, dphi, device=device)
+        if degree == 1:
+            return mesh, coords.copy()
+        return mesh, np.concatenate([coords, 0.5 * (coords[edges[:, 0]] + coords[edges[:, 1]]), inner], axis=0)
+
+    @classmethod
+    def from_dolfinx(cls, V, quadrature_degree, device=0, cells=None):
+        """From a dolfinx vector Lagrange space (any order, block size 2; ``cells``: those of one ``QuadratureMap`` instead of all)
+        on a first-order triangle or quadrilateral mesh whose ``x`` is ``r`` and whose ``y`` is ``z``, as
+        :meth:`PlaneMesh.from_dolfinx`: point ``c * nqp + q`` is row ``c * nqp + q`` of the quadrature Functions and ``u.x.array`` is
+        the vector to hand to ``integrate_displacement``.  UNTESTED without dolfinx."""
+        import basix
+
+        mesh = V.mesh
+        if mesh.topology.dim != 2 or V.dofmap.index_map_bs != 2:
+            raise ValueError("AxisymmetricMesh.from_dolfinx needs a vector Lagrange space with block size 2 on a two-dimensional mesh")
+        dofmap = np.asarray(V.dofmap.list, dtype=np.int32)
+        n_cells = dofmap.shape[0] if dofmap.ndim == 2 else len(dofmap) // len(V.dofmap.cell_dofs(0))
+        dofmap = dofmap.reshape(n_cells, -1)
+        geom_conn = np.asarray(mesh.geometry.dofmap, dtype=np.int32).reshape(n_cells, -1)
+        nv = geom_conn.shape[1]
+        if nv not in (3, 4):
+            raise ValueError("AxisymmetricMesh.from_dolfinx needs a first-order triangle or quadrilateral geometry (no curved cells)")
+        cell = basix.CellType.triangle if nv == 3 else basix.CellType.quadrilateral
+        pts, _ = basix.make_quadrature(cell, int(quadrature_degree))
+        pts = np.asarray(pts)
+
+        def tables(element, nd):
+            tab = np.asarray(element.tabulate(1, pts))
+            if tab.ndim == 4:
+                tab = tab[..., 0]
+            if tab.shape[2] != nd:      # blocked element tabulated with its block: the scalar basis is every second function
+                tab = tab[:, :, ::2]
+            return np.ascontiguousarray(tab[0]), np.ascontiguousarray(tab[1:3].transpose(1, 2, 0))
+
+        geom_phi, geom_dphi = tables(basix.create_element(basix.ElementFamily.P, cell, 1), nv)
+        phi, dphi = tables(V.element.basix_element, dofmap.shape[1])
+        n_dofs = V.dofmap.index_map.size_local + V.dofmap.index_map.num_ghosts
+        if cells is not None:
+            geom_conn, dofmap = geom_conn[np.asarray(cells)], dofmap[np.asarray(cells)]
+        return cls(np.asarray(mesh.geometry.x), geom_conn, dofmap, n_dofs, geom_phi, geom_dphi, phi, dphi, device=device)

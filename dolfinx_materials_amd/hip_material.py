@@ -1164,6 +1164,10 @@ class HIPMaterial:
         ``quadrature_function.py:45-51``).  The 4-wide plane-strain laws and the 3-wide plane-stress laws take a two-dimensional
         mesh (``mesh.tdim == 2``), whose gradient kernel writes their 4- or 3-wide strain; any other mesh is refused for them.
 
+        On a :class:`~dolfinx_materials_amd.gradient.AxisymmetricMesh` (``u`` holds ``(u_r, u_z)`` per dof) the strain carries the hoop
+        term ``u_r / r``: a ``hypothesis="plane_strain"`` behaviour, or a 6- or 9-wide one, on that mesh is the reference's
+        ``hypothesis="axisymmetric"`` law.  The plane-stress, heat-transfer and 5-wide laws are refused there.
+
         The heat-transfer laws of ``hypothesis="plane_strain"`` take a :class:`~dolfinx_materials_amd.gradient.PlaneScalarMesh` and the
         NODAL TEMPERATURE as ``u`` (``T.x.array``): gradient and temperature of a point are those of the interpolated field, and the
         material's own ``Temperature`` (``update_external_state_variable``) is neither read nor changed by such a call."""
@@ -1212,8 +1216,9 @@ class HIPMaterial:
         the displacement vector (``mesh.displacement_size`` doubles), ``flux_ptr`` / ``ct_ptr`` device arrays as for
         :meth:`integrate_device`; asynchronous on ``stream``.  For hex8 meshes with 8 Gauss points per
         cell, tet4 meshes and Lagrange simplex meshes the gradient is evaluated inside the update kernel; on a
-        :class:`~dolfinx_materials_amd.gradient.PlaneMesh`, and for the 4-wide and 3-wide laws on every two-dimensional mesh, the
-        gradient kernel fills the handle's scratch array and the update kernel follows on the same stream."""
+        :class:`~dolfinx_materials_amd.gradient.PlaneMesh` or :class:`~dolfinx_materials_amd.gradient.AxisymmetricMesh`, and for the
+        4-wide and 3-wide laws on every two-dimensional mesh, the gradient kernel fills the handle's scratch array and the update
+        kernel follows on the same stream."""
         self._host_mirrors_left_behind()
         self._chk(self._lib.dxm_integrate_displacement_device(
             self._require(), mesh._handle, int(u_ptr), self._dt(dt), int(flux_ptr), int(ct_ptr), int(stream) or None))

@@ -361,7 +361,11 @@ class AcceleratedUpdate:
 
         With a heat-transfer material of ``hypothesis="plane_strain"`` the mesh is a ``gradient.PlaneScalarMesh`` and the callable
         returns the nodal temperature (``lambda: T.x.array``): ``update()`` then runs through the nodal form, the kernel interpolates
-        ``T`` and ``grad(T)`` at its points, and a registered ``Temperature`` variable is not uploaded."""
+        ``T`` and ``grad(T)`` at its points, and a registered ``Temperature`` variable is not uploaded.
+
+        A ``gradient.AxisymmetricMesh`` goes where a ``gradient.PlaneMesh`` goes: with a ``hypothesis="plane_strain"`` material (or a
+        6- / 9-wide one) the update is the reference's ``hypothesis="axisymmetric"`` one, the strain carrying ``u_r / r``; the measure
+        ``2 pi r`` of the forms is the caller's (``mesh.radii()``)."""
         plan = self._accel_plan()
         if mesh.npoints != plan.npoints or not (plan.identity or plan.row_outputs):
             raise ValueError("device gradient evaluation needs a mesh object with exactly the cells of this map, in its order")

@@ -789,10 +789,26 @@ dxm_mesh* dxm_mesh_create_plane(const double* coords, int64_t n_vertices, const 
 dxm_mesh* dxm_mesh_create_plane_scalar(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
                                        const int32_t* dofmap, int nd, int64_t n_dofs,
                                        const double* geom_dphi, const double* phi, const double* dphi, int nqp, int device);
+/* An AXISYMMETRIC mesh: the same cells in the meridian half plane, column 0 of coords is r, column 1 is z, and the two components
+ * per dof are (u_r, u_z).  Under MGIS's axisymmetric hypothesis a symmetric tensor is [rr, zz, tt, sqrt(2) rz] and F is
+ * [F_rr, F_zz, F_tt, F_rz, F_zr]: the slots of the plane-strain hypothesis, with the hoop terms eps_tt = u_r / r, F_tt = 1 + u_r / r
+ * where plane strain has 0 and 1.  So the hypothesis lives on the MESH: a DXM_LAW_PE_* handle, or a 6- / 9-wide one, on this mesh is
+ * the axisymmetric law.  The arguments are those of dxm_mesh_create_plane plus the VALUES of the shape functions at the Gauss
+ * points: geom_phi (nqp, nv) of the geometry's (for r) and phi (nqp, nd) of the field's (for u_r).  Checked on the host, in this
+ * order and with the sentences of dxm_mesh_create_plane, before a device is asked for: the arguments; the indices; det J; every
+ * entry of the four tables finite; r = sum_v r_v geom_phi[q][v] finite and > 0 at every Gauss point (the message names the cell: the
+ * mesh must lie on one side of the axis, with no Gauss point on it); the device last.  dxm_mesh_displacement_size = 2 n_dofs.
+ * The mesh serves dxm_mesh_axisymmetric_gradient_device and the displacement forms; it refuses every kind of
+ * dxm_mesh_gradient_device and dxm_mesh_scalar_gradient_device.  Straight-sided (first-order) cells only.  A custom-hardening build
+ * creates such a mesh and refuses its gradient. */
+dxm_mesh* dxm_mesh_create_axisymmetric(const double* coords, int64_t n_vertices, const int32_t* geom_conn, int nv, int64_t n_cells,
+                                       const int32_t* dofmap, int nd, int64_t n_dofs,
+                                       const double* geom_phi, const double* geom_dphi, const double* phi, const double* dphi,
+                                       int nqp, int device);
 int dxm_mesh_destroy(dxm_mesh* mesh);
 int64_t dxm_mesh_npoints(const dxm_mesh* mesh);
 /* doubles in the displacement vector the mesh expects (3 per node; tdim per dof for dxm_mesh_create_simplex; 2 per dof for
- * dxm_mesh_create_plane; 1 per dof for dxm_mesh_create_plane_scalar) */
+ * dxm_mesh_create_plane and dxm_mesh_create_axisymmetric; 1 per dof for dxm_mesh_create_plane_scalar) */
 int64_t dxm_mesh_displacement_size(const dxm_mesh* mesh);
 /* kind 0: Mandel strain (6); kind 1: deformation gradient F = I + grad u (9); on two-dimensional meshes only
  * (dxm_mesh_create_plane, dxm_mesh_create_simplex with tdim 2; any other mesh refuses them), with H[i][a] = du_i / dX_a and
@@ -807,6 +823,25 @@ int dxm_mesh_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, doub
  * run in the dofmap's local order: the update kernels of the nodal forms evaluate the same text and deliver the same bits.  A mesh
  * that carries a displacement refuses (< 0, message); a refused call writes nothing. */
 int dxm_mesh_scalar_gradient_device(dxm_mesh* mesh, const double* t_dev, double* grad_dev, double* value_dev, void* hip_stream);
+/* On an axisymmetric mesh (dxm_mesh_create_axisymmetric; any other mesh is refused: its gradients are those of
+ * dxm_mesh_gradient_device), with H[i][a] = du_i / dX_a in (r, z), hoop = u_r / r and s = sqrt(2)/2; the kinds are numbered by this
+ * entry point alone:
+ *   kind 0: [H00, H11, hoop, s (H01 + H10)]                                 (npoints, 4)  the strain of the DXM_LAW_PE_* rows
+ *   kind 1: [1 + H00, 1 + H11, 1 + hoop, H01, H10]                          (npoints, 5)  the F of DXM_LAW_OGDEN_PE / DXM_LAW_LOG_STRAIN_PE
+ *   kind 2: [H00, H11, hoop, s (H01 + H10), 0, 0]                           (npoints, 6)  the Mandel strain of the 6-wide laws
+ *   kind 3: [1 + H00, 1 + H11, 1 + hoop, H01, H10, 0, 0, 0, 0]              (npoints, 9)  the F of the 9-wide laws
+ * u_dev (2 n_dofs doubles) and grad_dev are device memory; grad_dev 16-byte aligned for kinds 0 and 2.  Unless radius_dev is NULL,
+ * r at the Gauss points goes into radius_dev (npoints): the measure of the hypothesis is 2 pi r w |det J|.  Asynchronous on
+ * hip_stream and capturable.  The sums run in the tables' local order (products fused with their sums, as in the plane gradient
+ * kernels): a restatement in that order agrees at rounding level.  A refused call (< 0, message) writes nothing.
+ * The displacement forms below accept such a mesh: this kernel fills the handle's scratch array, the update kernel follows on the
+ * same stream (no fused form; the option fused_gradient makes no difference).  The kind follows the law's gradient width: the
+ * 4-wide plane-strain rows kind 0, the 6-wide laws kind 2, the 9-wide laws kind 3.  Refused, the handle left usable: the 3-wide
+ * plane-stress rows (plane stress and axisymmetry exclude each other), the heat-transfer laws (a scalar mesh), DXM_LAW_OGDEN_PE and
+ * DXM_LAW_LOG_STRAIN_PE (their rows' own sentence: evaluate kind 1, then call the array form), every law that takes no displacement
+ * on any mesh, a device mismatch and a point-count mismatch. */
+int dxm_mesh_axisymmetric_gradient_device(dxm_mesh* mesh, const double* u_dev, int kind, double* grad_dev, double* radius_dev,
+                                          void* hip_stream);
 /* dxm_integrate with the gradient computed on the device from the host displacement vector
  * u_host (dxm_mesh_displacement_size doubles): uploads u, evaluates the law's gradient, runs the constitutive update,
  * downloads flux / isv / tangent (any may be NULL).  mesh npoints must equal the handle's. */

@@ -40,6 +40,9 @@ PLANE_FORM_UNITS = ("ogden_plane", "hosford_plane")
 # the plane-strain form of law 19, walked after them in the same way.  Again a list of its own: tests/test_hosford_plane_build.py
 # pins PLANE_FORM_UNITS to the two units above
 PLANE_F_UNITS = ("log_strain_plane",)
+# the gradient kernels of an axisymmetric mesh.  Not walked by --all-units, whose unit lists tests pin; tests/test_axisym_gradient_build.py
+# reads the unit's resources with device_asm() / resource_table() above
+AXISYM_UNITS = ("axisym_gradient",)
 MAX_VGPRS = 128
 J2_STATIC_LDS = 30848     # small_strain.hpp: 4 waves x (64 x 6 + 64 x 9) doubles + the 4 x 4 status words
 
